@@ -16,7 +16,10 @@ ranks; `value` = PBS executed by all ranks / that time.
   eq_ignore_case  cfg 5   4096-char buffers, character positions sharded
   le              cfg 5   4096-char buffers, character positions sharded
 All exchanges are ncclAllGather calls issued by the library itself on the context's HIP stream (fhs_dist_*).
-The default run also times configs 3-5 once each at their fixed BASELINE sizes over the same N ranks ("configs").
+A plain run sets up, warms up, times the K steps and prints the line (`--dump-outputs DIR` also writes the last timed
+step's results).  `--full` adds everything else after the timed steps: repeats for the median, single-op latency, the
+other arithmetics, configs 3-5 once each at their fixed BASELINE sizes over the same N ranks ("configs"), the size
+sweeps, the as-written DAG shapes and the CPU baseline.
 """
 import argparse
 import json
@@ -73,12 +76,12 @@ def parse():
     ap.add_argument("--no-balance", action="store_true",
                     help="level-skewed batching without round alignment of the launch groups (fhs_set_tick_balance off)")
     ap.add_argument("--skip-single-op", action="store_true", help="skip single-op latency / end-to-end / as-written")
-    ap.add_argument("--skip-extras", action="store_true", help="skip the configs 3-5 section of the default run")
+    ap.add_argument("--skip-extras", action="store_true", help="skip the configs 3-5 section of a --full run")
     ap.add_argument("--as-written-replace-1024", action="store_true",
                     help="with --as-written-fullsize: also config 4 itself as written (replace 5 -> 5 on 1024 characters, the "
                          "O(n^2) bubble: ~27 M bootstraps, about five minutes)")
     ap.add_argument("--as-written-fullsize", action="store_true",
-                    help="also RUN the reference-order (as written) DAGs of configs 3-5 at full size on the GPU -- find 256, "
+                    help="with --full: also RUN the reference-order (as written) DAGs of configs 3-5 at full size on the GPU -- find 256, "
                          "eq_ignore_case 4096, le 4096, replace 256: about two minutes -- and compare with the fused results; "
                          "without it the line quotes the figures recorded in profiles/r04_as_written_fullsize.json")
     ap.add_argument("--skip-sweep", action="store_true", help="skip the contains sweep over 64 / 256 / 1024 / 4096 characters")
@@ -92,6 +95,14 @@ def parse():
     ap.add_argument("--extras-out", default=None,
                     help="where the full record goes (default: bench_extras.json next to bench.py + a copy under gpurun_out/); "
                          "stdout carries only the compact contract line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run everything beyond the headline figure: repeats for the median, "
+                         "single-op latency and host timers, the other arithmetics, a larger batch, configs 3-5, the size "
+                         "sweeps, as-written DAG shapes and the CPU baseline (without it a run only sets up, warms up, "
+                         "times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step to DIR/*.npy (float64): the ciphertexts as signed "
+                         "torus fractions and their decryptions")
     ap.add_argument("--inject-fault", choices=["raise", "hang"], default=None, help=argparse.SUPPRESS)   # tests only:
     # the last rank fails / hangs right after the timed measurement (tests/test_gpu_bench_contract.py)
     a = ap.parse_args()
@@ -270,7 +281,7 @@ class Workload:
         """what `ms_per_op` means: the step's wall time over its independent strings"""
         if self.n_strings <= 1:
             return ""
-        return "; ms_per_op is AMORTISED over %d independent strings per step%s -- one op alone = single_op_latency_ms" % (
+        return "; ms_per_op is AMORTISED over %d independent strings per step%s -- one op alone = single_op_latency_ms (--full)" % (
             self.n_strings, " (level-skewed batching)" if skew else "")
 
     def describe(self):
@@ -580,6 +591,37 @@ def emit(full, args, safety):
         safety["line_out"] = True
 
 
+DUMP_CT_BYTES = 56 << 20    # --dump-outputs: at most this much of ciphertext; beyond it a fixed, seeded sample of rows
+
+
+def dump_outputs(path, ck, outs, write=True):
+    """--dump-outputs: the results of the last timed step as a caller receives them, one row per encrypted character
+    (4 blocks of 2049 u64 words), all float64.  ciphertexts.npy holds every word as a signed torus fraction (int64 / 2^64:
+    close words stay close), ciphertexts_hi32.npy and ciphertexts_lo32.npy its upper and lower 32 bits (exact: two builds
+    agree bit for bit or not), plaintexts.npy the client's decryption of each row, result_lengths.npy the rows of each
+    result; a sample of rows is listed in ciphertext_rows.npy.  Every rank downloads (a download may be collective); only
+    `write` ranks write."""
+    import numpy as np
+    from fhestring_amd.api import BIG_CT
+    rows = [np.ascontiguousarray(o.download(), np.uint64).reshape(-1, 4, BIG_CT) for o in outs]
+    if not write:
+        return
+    cts = np.concatenate(rows) if rows else np.zeros((0, 4, BIG_CT), np.uint64)
+    arrays = {"plaintexts": np.array([ck.decrypt_char_raw(c) for c in cts], np.float64),
+              "result_lengths": np.array([len(r) for r in rows], np.float64)}
+    per_row = 3 * 4 * BIG_CT * 8                      # three float64 arrays per ciphertext word
+    if len(cts) * per_row > DUMP_CT_BYTES:
+        keep = np.sort(np.random.default_rng(SEED).choice(len(cts), DUMP_CT_BYTES // per_row, replace=False))
+        arrays["ciphertext_rows"] = keep.astype(np.float64)
+        cts = cts[keep]
+    arrays["ciphertexts"] = cts.view(np.int64).astype(np.float64) * 2.0 ** -64
+    arrays["ciphertexts_hi32"] = (cts >> np.uint64(32)).astype(np.float64)
+    arrays["ciphertexts_lo32"] = (cts & np.uint64(0xFFFFFFFF)).astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
 def main():
     """Runs the bench; in a multi-GPU run a failure (or a hang) AFTER the contract's timed measurement costs the extra
     legs, not the headline line (see `safety` in _main)."""
@@ -711,7 +753,7 @@ def _main(safety, args):
               "exact_mb2": "blind_rotate_ntt_mb2_kernel"}
     ARITH_NAME = {"fft": "f64-FFT", "exact": "exact-NTT", "mb2": "f64-FFT, two key bits per external product",
                   "exact_mb2": "exact-NTT, two key bits per external product"}
-    extras_mb = args.arith == "fft" and not args.skip_extras and args.op == "contains" and world == 1
+    extras_mb = args.full and args.arith == "fft" and not args.skip_extras and args.op == "contains" and world == 1
     want_mb2 = args.arith in ("mb2", "exact_mb2") or extras_mb
     if want_mb2:
         pair_key = ck.bsk_mb2()
@@ -847,6 +889,8 @@ def _main(safety, args):
     dt, outs, st, kt = timed(args.steps)
     ex1 = [D.stats() for D in dists if D is not None]
     wl.check(outs)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ck, outs, write=rank == 0)
     # Multi-GPU safety net: the contract's figures are complete at this point.  What follows (repeats, the other
     # arithmetic, configs 3-5 in their sharded formulations) has never run over real xGMI: if any of it raises on one
     # rank or hangs in a collective, rank 0 still prints the headline line (marked "incomplete") instead of nothing.
@@ -937,7 +981,8 @@ def _main(safety, args):
     # as many steps per repeat as the contract's timed region (round 4: 6-step repeats amortised the drain of the last
     # steps' narrow levels over fewer steps and read 7 % below `value` for that reason alone)
     n_rep_steps = args.steps if SKEW else max(P, min(args.steps, 2 * P))
-    for _ in range(args.repeats):
+    n_rep = args.repeats if args.full else 0
+    for _ in range(n_rep):
         d, _, _, _ = timed(n_rep_steps)
         rep_ms.append(d / n_rep_steps * 1e3)
 
@@ -945,7 +990,7 @@ def _main(safety, args):
     # reference's own timer src/main.rs:103-114), and the as-written (reference-order) DAG of the same op
     stage[0] = "single-op latency"
     single = None
-    if rank == 0 and world == 1 and not args.skip_single_op:
+    if args.full and rank == 0 and world == 1 and not args.skip_single_op:
         sk = sks[0]
         one = Workload(args, ck, [sk], [None], 0, 1, strings=1)
         keep = one.step(0); sk.flush(); sync()
@@ -1034,7 +1079,7 @@ def _main(safety, args):
     # the other arithmetic on the same workload (secondary figure, fewer steps)
     stage[0] = "the other arithmetic (timed steps + barrier)"
     secondary = None
-    if not args.skip_secondary:
+    if args.full and not args.skip_secondary:
         other = "exact" if args.arith == "fft" else "fft"
         set_arith(other)
         for _ in range(P):
@@ -1045,7 +1090,7 @@ def _main(safety, args):
         secondary = {"arithmetic": other, "pbs_local": float(st2["pbs_executed"]), "dt": dt2, "steps": n2, "kt": kt2}
         set_arith(args.arith)
 
-    # the same workload in the two-bits-per-product arithmetic (default run only; its own object in the JSON line)
+    # the same workload in the two-bits-per-product arithmetic (--full, contains only; its own object in the JSON line)
     stage[0] = "two-bit arithmetic"
     multi_bit = None
     if args.arith == "fft" and want_mb2:
@@ -1076,10 +1121,10 @@ def _main(safety, args):
         multi_bit["exact"] = {"pbs_local": float(st4["pbs_executed"]), "dt": dt4, "steps": n4, "kt": kt4}
         set_arith(args.arith)
 
-    # the same workload with twice the strings per step (one GPU, default run): how much of the gap to the kernel-only
+    # the same workload with twice the strings per step (one GPU, --full): how much of the gap to the kernel-only
     # rate is batch size (narrow-level drain, keyswitch and the emptier last round of a launch group weigh half as much)
     larger = None
-    if args.op == "contains" and SKEW and world == 1 and not args.skip_extras and args.mode == "fused":
+    if args.full and args.op == "contains" and SKEW and world == 1 and not args.skip_extras and args.mode == "fused":
         big = Workload(args, ck, sks[:1], dists[:1], rank, world, strings=2 * args.strings)
         saved = wl
         wl = big
@@ -1093,9 +1138,9 @@ def _main(safety, args):
         wl = saved
         del big
 
-    # BASELINE configs 3-5 at their fixed sizes, once each over the same ranks (default run only)
+    # BASELINE configs 3-5 at their fixed sizes, once each over the same ranks (--full only)
     extras = None
-    if args.op == "contains" and not args.skip_extras and args.mode == "fused":
+    if args.full and args.op == "contains" and not args.skip_extras and args.mode == "fused":
         extras = {}
         for op in ("find_enc", "replace", "eq_ignore_case", "le"):
             stage[0] = "configs 3-5: %s (sharded exchange + barrier)" % op
@@ -1268,7 +1313,7 @@ def _main(safety, args):
     # the reference-order DAGs of configs 3-5 EXECUTED at full size: measured ms beside the planner's
     # shapes below, each result compared with the fused DAG's on the same ciphertexts and with Python
     aw_full = None
-    if args.as_written_fullsize and world == 1 and rank == 0:
+    if args.full and args.as_written_fullsize and world == 1 and rank == 0:
         aw_full = {}
         sk0 = sks[0]
         aw_cases = [("cfg3_find_encrypted_256", "find_enc", 256), ("cfg4_replace_256", "replace", 256),
@@ -1350,7 +1395,7 @@ def _main(safety, args):
     stage[0] = "final all_reduce of the figures"
     if dist is not None:
         vec = [dt, float(pbs_local)] + ([secondary["dt"], secondary["pbs_local"]] if secondary else [0.0, 0.0])
-        vec += rep_ms + [0.0] * (args.repeats - len(rep_ms))
+        vec += rep_ms + [0.0] * (n_rep - len(rep_ms))
         if extras:
             for op in ("find_enc", "replace", "eq_ignore_case", "le"):
                 vec += [extras[op]["ms_local"], extras[op]["pbs_local"]]
@@ -1361,9 +1406,9 @@ def _main(safety, args):
         dt, pbs_total = float(tmax[0]), float(tsum[1])
         if secondary:
             secondary["dt"], secondary["pbs_total"] = float(tmax[2]), float(tsum[3])
-        rep_ms = [float(x) for x in tmax[4:4 + args.repeats]]
+        rep_ms = [float(x) for x in tmax[4:4 + n_rep]]
         if extras:
-            base = 4 + args.repeats
+            base = 4 + n_rep
             for i, op in enumerate(("find_enc", "replace", "eq_ignore_case", "le")):
                 extras[op]["ms"], extras[op]["pbs"] = float(tmax[base + 2 * i]), float(tsum[base + 2 * i + 1])
     else:
@@ -1439,8 +1484,6 @@ def _main(safety, args):
             line["single_op"] = single
             line["end_to_end_ms"] = single["end_to_end_ms"]
             line["two_queued_ms_per_op"] = single["two_queued_ms_per_op"]
-        else:
-            line["single_op_latency_ms"] = dt / args.steps * 1e3
         ksw = kt[1]
         if ksw["n"]:
             # the second kernel of a launch group, on the matrix cores: (rows x 10 240) x (10 240 x 743) in 8 i8 byte planes
@@ -1530,7 +1573,7 @@ def _main(safety, args):
                 for k in ("end_to_end_ms", "end_to_end_split_ms", "two_queued_ms_per_op"):
                     if k in e:
                         line["configs"][names[op]][k] = e[k]
-        if args.cpu_pbs != 0:
+        if args.full and args.cpu_pbs != 0:
             line["cpu_baseline"] = cpu_baseline(args.cpu_pbs, single["level_widths"] if single else None)
             if extras:
                 rate = line["cpu_baseline"]["value"]

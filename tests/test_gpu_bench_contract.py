@@ -1,4 +1,5 @@
-"""bench.py prints ONE JSON line with the contract's keys (driver contract + roofline + cpu_baseline)."""
+"""bench.py prints ONE JSON line with the contract's keys (driver contract + roofline; + cpu_baseline and the other legs
+with --full)."""
 import json
 import os
 import subprocess
@@ -66,7 +67,7 @@ def _check_roofline(r, may_be_stale=True):
 
 
 def test_bench_json_line_contract(tmp_path):
-    line, d = _run("--cpu-pbs", "64", "--repeats", "5", tmp_path=tmp_path)
+    line, d = _run("--full", "--cpu-pbs", "64", "--repeats", "5", tmp_path=tmp_path)
     # (1) the compact line the driver parses: every contract key, roofline + cpu_baseline, the four configs, small
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "ms_per_op", "single_op_latency_ms"):
@@ -173,6 +174,56 @@ def test_bench_other_ops(op):
     assert op.split("_")[0] in d["config"]["workload"]
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A run without --full times the steps and prints the headline, nothing else: `value` and `ms_per_step` describe the
+    same timed region, which fits in the run's wall time.  --dump-outputs writes the results of a timed step: they decrypt
+    to what the seeded workload asks, the 32-bit halves are the exact words, and the same arguments give the same files
+    whatever the number of steps and warm-ups.  (Every step recomputes the same batch, so which step was dumped cannot be
+    told from the files.)"""
+    import random
+    import time
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rnd = random.Random(bench.SEED + bench.OPS.index("contains"))      # Workload.setup: 16 strings, m = 4, hit in string 0
+    strs = [bench.rand_text(rnd, 64) for _ in range(16)]
+    off = rnd.randint(0, 64 - 4)
+    want = [float(strs[0][off:off + 4] in s_) for s_ in strs]
+    got = []
+    for steps, warmup in ((2, 1), (3, 2)):
+        d_out = os.path.join(str(tmp_path), "out%d" % steps)
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup),
+               "--dump-outputs", d_out]
+        t0 = time.perf_counter()
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        wall = time.perf_counter() - t0
+        assert out.returncode == 0, out.stderr[-3000:]
+        line = _parse_line(out.stdout)
+        assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0 and line["value"] > 10_000
+        assert line["unit"] == "PBS/s" and line["dtype"] == "f64" and line["higher_is_better"] is True
+        assert steps * line["ms_per_step"] * 1e-3 < wall
+        assert abs(line["value"] * line["ms_per_step"] * 1e-3 - line["pbs_per_op"] * 16) < 1e-3 * line["pbs_per_op"] * 16
+        assert abs(line["ms_per_op"] * 16 - line["ms_per_step"]) < 1e-4 * line["ms_per_step"]
+        for k in ("cpu_baseline", "configs", "other_arithmetic", "median_ms_per_step", "two_queued_ms_per_op",
+                  "single_op_latency_ms", "end_to_end_ms"):
+            assert line.get(k) is None, k
+        names = ("ciphertexts", "ciphertexts_hi32", "ciphertexts_lo32", "plaintexts", "result_lengths")
+        arrays = {n: np.load(os.path.join(d_out, n + ".npy")) for n in names}
+        assert sorted(os.listdir(d_out)) == sorted(n + ".npy" for n in names)
+        assert all(a.dtype == np.float64 for a in arrays.values())
+        ct, hi, lo = arrays["ciphertexts"], arrays["ciphertexts_hi32"], arrays["ciphertexts_lo32"]
+        assert ct.shape == hi.shape == lo.shape == (16, 4, 2049)
+        assert -0.5 <= ct.min() and ct.max() < 0.5 and ct.std() > 0.1
+        assert 0 <= hi.min() and hi.max() < 2 ** 32 and 0 <= lo.min() and lo.max() < 2 ** 32
+        words = hi.astype(np.uint64) << np.uint64(32) | lo.astype(np.uint64)
+        assert np.array_equal(words.view(np.int64).astype(np.float64) * 2.0 ** -64, ct)
+        assert arrays["plaintexts"].tolist() == want
+        assert arrays["result_lengths"].tolist() == [1.0] * 16
+        got.append(arrays)
+    for n in got[0]:
+        assert np.array_equal(got[0][n], got[1][n]), n
+
+
 @pytest.mark.parametrize("extra", [[], ["--op", "find_enc"], ["--op", "replace", "--chars", "96"]],
                          ids=["contains_skewed", "find_enc", "replace_level_parallel"])
 def test_bench_two_ranks_on_one_gpu(extra):
@@ -223,12 +274,12 @@ def test_bench_starts_its_own_ranks_for_gpus_2():
     env = dict(os.environ, FHS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--cpu-pbs", "0", "--skip-secondary", "--skip-extras", "--repeats", "0"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1"]     # a plain run
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     d = _parse_line(out.stdout, gloo_noise=True)
-    assert d["n_gpus"] == 2 and d["steps"] == 4 and d["value"] > 1000
+    assert d["n_gpus"] == 2 and d["steps"] == 4 and d["value"] > 1000 and "incomplete" not in d
+    assert d["ms_per_step"] > 0 and "median_ms_per_step" not in d and "configs" not in d
     assert d["config"]["exchange"]["allgather_calls_per_step"] > 0
     assert "torch.distributed.run" in out.stderr           # ... and says on stderr what it started
 
@@ -242,7 +293,7 @@ def test_bench_keeps_the_headline_when_a_later_leg_fails_on_one_rank(fault):
     env = dict(os.environ, FHS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-           "--cpu-pbs", "0", "--skip-secondary", "--skip-extras", "--repeats", "1", "--watchdog", "6",
+           "--full", "--cpu-pbs", "0", "--skip-secondary", "--skip-extras", "--repeats", "1", "--watchdog", "6",
            "--inject-fault", fault]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode != 0, out.stdout[-2000:]
@@ -265,7 +316,7 @@ def test_as_written_dags_at_full_size_match_the_fused_ones(tmp_path):
     tens of thousands of dependency levels, about two minutes of GPU -- each decrypting like the fused DAG on the same
     ciphertexts and like Python; the measured times replace the extrapolations beside `as_written_dag_shapes`."""
     side = os.path.join(str(tmp_path), "bench_extras.json")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-pbs", "0",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-pbs", "0",
                           "--repeats", "0", "--skip-secondary", "--skip-single-op", "--skip-sweep", "--as-written-fullsize",
                           "--extras-out", side],
                          capture_output=True, text=True, timeout=1500, cwd=ROOT)
