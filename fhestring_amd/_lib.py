@@ -323,6 +323,25 @@ def _declare(L):
     L.fhs_load_server_key_file.restype = i
     L.fhs_client_secret_keys.argtypes = [vp, vp, vp]
     L.fhs_client_secret_keys.restype = i
+    # compressed (seeded) ciphertexts and server keys
+    L.fhs_client_encrypt_str_compressed.argtypes = [vp, C.c_char_p, sz, sz, vp, vp]
+    L.fhs_client_encrypt_str_compressed.restype = i
+    L.fhs_expand_compressed_str.argtypes = [vp, vp, sz, sz, vp]
+    L.fhs_expand_compressed_str.restype = i
+    L.fhs_upload_string_compressed.argtypes = [vp, vp, vp, sz, sz, vp]
+    L.fhs_upload_string_compressed.restype = i
+    L.fhs_client_compressed_server_key.argtypes = [vp, vp, vp, vp]
+    L.fhs_client_compressed_server_key.restype = i
+    L.fhs_client_save_compressed_server_key.argtypes = [vp, C.c_char_p]
+    L.fhs_client_save_compressed_server_key.restype = i
+    L.fhs_expand_compressed_server_key.argtypes = [vp, vp, vp, vp, vp]
+    L.fhs_expand_compressed_server_key.restype = i
+    L.fhs_load_compressed_server_key.argtypes = [vp, vp, vp, vp]
+    L.fhs_load_compressed_server_key.restype = i
+    L.fhs_load_compressed_server_key_file.argtypes = [vp, C.c_char_p]
+    L.fhs_load_compressed_server_key_file.restype = i
+    L.fhs_debug_chacha20_device.argtypes = [vp, vp, C.c_uint32, vp, vp, sz]
+    L.fhs_debug_chacha20_device.restype = i
 
 
 class CaptureRec(C.Structure):

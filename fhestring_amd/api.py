@@ -78,6 +78,23 @@ class Context:
         assert bsk.size == 742 * 4 * 2048 and ksk.size == 2048 * 5 * 743
         self._check(self._L.fhs_load_server_key(self._h, _ptr(bsk), _ptr(ksk)))
 
+    def load_compressed_server_key(self, seed, bsk_bodies, ksk_bodies):
+        """fhs_load_compressed_server_key: the seeded masks are regenerated on the device."""
+        seed = np.ascontiguousarray(seed, np.uint32)
+        bsk_bodies = np.ascontiguousarray(bsk_bodies, np.uint64)
+        ksk_bodies = np.ascontiguousarray(ksk_bodies, np.uint64)
+        assert seed.size == 8 and bsk_bodies.size == 742 * 2 * 2048 and ksk_bodies.size == 2048 * 5
+        self._check(self._L.fhs_load_compressed_server_key(self._h, _ptr(seed), _ptr(bsk_bodies), _ptr(ksk_bodies)))
+
+    def chacha20_device(self, key, counter, nonce, n):
+        """fhs_debug_chacha20_device: n 64-bit draws of the device ChaCha20 (the values of fhs_chacha20_stream)."""
+        key = np.ascontiguousarray(key, np.uint32)
+        nonce = np.ascontiguousarray(nonce, np.uint32)
+        assert key.size == 8 and nonce.size == 3
+        out = np.zeros(n, np.uint64)
+        self._check(self._L.fhs_debug_chacha20_device(self._h, _ptr(key), int(counter), _ptr(nonce), _ptr(out), n))
+        return out
+
     def blind_rotate_batch(self, ks, lut_idx, luts):
         """fhs_debug_blind_rotate_batch: blind rotation + sample extraction from given keyswitched LWEs [B, 743]."""
         ks = np.ascontiguousarray(ks, np.uint64).reshape(-1, 743)
@@ -266,6 +283,32 @@ class MyClientKey:
         self._L.fhs_client_decrypt_str(self._h, _ptr(chars), chars.shape[0], buf, C.byref(n))
         return buf.raw[:n.value].decode("ascii")
 
+    def encrypt_compressed(self, string, padding):
+        """fhs_client_encrypt_str_compressed: the string's masks come from a fresh public seed, only the bodies are kept
+        (32 B per character instead of 65 568 B)."""
+        data = string.encode("ascii") if isinstance(string, str) else bytes(string)
+        seed = np.zeros(8, np.uint32)
+        bodies = np.empty((len(data) + padding, 4), np.uint64)
+        rc = self._L.fhs_client_encrypt_str_compressed(self._h, data, len(data), int(padding), _ptr(seed), _ptr(bodies))
+        if rc != 0:
+            raise AssertionError("The input string must only contain ascii letters and not include null characters")
+        return CompressedFheString(seed, bodies)
+
+    def compressed_server_key(self):
+        """fhs_client_compressed_server_key: (seed[8] u32, bsk_bodies[742][2][2048], ksk_bodies[2048][5]) of a second
+        server key of this client whose masks come from the public seed (generated on first use)."""
+        seed = np.zeros(8, np.uint32)
+        bb = np.empty((742, 2, 2048), np.uint64)
+        kb = np.empty((2048, 5), np.uint64)
+        if self._L.fhs_client_compressed_server_key(self._h, _ptr(seed), _ptr(bb), _ptr(kb)) != 0:
+            raise FhsError("fhs_client_compressed_server_key failed")
+        return seed, bb, kb
+
+    def save_compressed_server_key(self, path):
+        """fhs_client_save_compressed_server_key: kind 4 key file (seed + bodies, 24 395 872 B)."""
+        if self._L.fhs_client_save_compressed_server_key(self._h, str(path).encode()) != 0:
+            raise FhsError("cannot write compressed key file %s" % path)
+
     # reference-shaped API (server key needed to place ciphertexts on the device)
     def encrypt(self, string, padding, public_parameters=None, server_key=None):   # :45-65
         # the ciphertext only lives until fhs_upload_string has staged it: one scratch buffer per client, grown on demand
@@ -393,6 +436,69 @@ class FheString:
         return out
 
 
+class CompressedFheString:
+    """A seeded FheString: the public seed (8 x u32) and the body of every block ([n][4] u64); the masks follow from the
+    seed (include/fhestring_hip.h, "compressed ciphertexts").  Serialised form: magic FHSCSTR1, n (u64), seed, bodies."""
+
+    MAGIC = b"FHSCSTR1"
+
+    def __init__(self, seed, bodies):
+        self.seed = np.ascontiguousarray(seed, np.uint32).reshape(8)
+        self.bodies = np.ascontiguousarray(bodies, np.uint64).reshape(-1, 4)
+
+    def __len__(self):
+        return self.bodies.shape[0]
+
+    @property
+    def nbytes(self):
+        return 48 + self.bodies.nbytes
+
+    def to_bytes(self):
+        return self.MAGIC + np.uint64(len(self)).tobytes() + self.seed.tobytes() + self.bodies.tobytes()
+
+    @classmethod
+    def from_bytes(cls, data):
+        data = bytes(data)
+        if data[:8] != cls.MAGIC or len(data) < 48:
+            raise ValueError("not a compressed FheString")
+        n = int(np.frombuffer(data, np.uint64, 1, 8)[0])
+        if len(data) != 48 + 32 * n:
+            raise ValueError("compressed FheString of %d characters needs %d bytes, got %d" % (n, 48 + 32 * n, len(data)))
+        return cls(np.frombuffer(data, np.uint32, 8, 16), np.frombuffer(data, np.uint64, 4 * n, 48))
+
+    def _window(self, first_char, count):
+        if count is None:
+            count = len(self) - first_char
+        assert 0 <= first_char and 0 <= count and first_char + count <= len(self)
+        return first_char, count
+
+    def expand(self, first_char=0, count=None):
+        """fhs_expand_compressed_str: characters [first_char, first_char + count) as classic [count][4][2049] words."""
+        first_char, count = self._window(first_char, count)
+        out = np.empty((count, 4, BIG_CT), np.uint64)
+        bodies = np.ascontiguousarray(self.bodies[first_char:first_char + count])
+        if lib().fhs_expand_compressed_str(_ptr(self.seed), _ptr(bodies), count, first_char, _ptr(out)) != 0:
+            raise FhsError("fhs_expand_compressed_str failed")
+        return out
+
+    def decompress(self, server_key, first_char=0, count=None):
+        """Expands characters [first_char, first_char + count) on the server key's GPU -> FheString."""
+        return server_key.upload_compressed_string(self, first_char, count)
+
+
+def expand_compressed_server_key(seed, bsk_bodies, ksk_bodies):
+    """fhs_expand_compressed_server_key: host expansion to the standard-domain (bsk, ksk) of fhs_load_server_key."""
+    seed = np.ascontiguousarray(seed, np.uint32)
+    bsk_bodies = np.ascontiguousarray(bsk_bodies, np.uint64)
+    ksk_bodies = np.ascontiguousarray(ksk_bodies, np.uint64)
+    assert seed.size == 8 and bsk_bodies.size == 742 * 2 * 2048 and ksk_bodies.size == 2048 * 5
+    bsk = np.empty(742 * 4 * 2048, np.uint64)
+    ksk = np.empty(2048 * 5 * 743, np.uint64)
+    if lib().fhs_expand_compressed_server_key(_ptr(seed), _ptr(bsk_bodies), _ptr(ksk_bodies), _ptr(bsk), _ptr(ksk)) != 0:
+        raise FhsError("fhs_expand_compressed_server_key failed")
+    return bsk, ksk
+
+
 class FheSplit:
     """Vec<FheString> + pattern_found (src/ciphertext/fhesplit.rs:5-8)."""
 
@@ -461,6 +567,16 @@ class MyServerKey:
         return cls(ctx)
 
     @classmethod
+    def from_compressed_key_file(cls, path, device_id=0, arith=0, multibit_key_path=None):
+        """Kind 4 file (MyClientKey.save_compressed_server_key): the seeded masks are regenerated on the device."""
+        ctx = Context(device_id)
+        ctx.set_arithmetic(arith)
+        ctx._check(ctx._L.fhs_load_compressed_server_key_file(ctx._h, str(path).encode()))
+        if multibit_key_path is not None:
+            ctx._check(ctx._L.fhs_load_multibit_key_file(ctx._h, str(multibit_key_path).encode()))
+        return cls(ctx)
+
+    @classmethod
     def from_raw_keys(cls, bsk, ksk, device_id=0, arith=0, bsk_mb2=None):
         ctx = Context(device_id)
         ctx.set_arithmetic(arith)
@@ -489,6 +605,16 @@ class MyServerKey:
         hs = (C.c_uint64 * max(1, n))()
         self.ctx._check(self.ctx._L.fhs_upload_string(self.ctx._h, _ptr(chars), n, hs))
         return FheString([FheAsciiChar(self, hs[i]) for i in range(n)])
+
+    def upload_compressed_string(self, cstr, first_char=0, count=None):
+        """fhs_upload_string_compressed: characters [first_char, first_char + count) of a CompressedFheString, expanded
+        on the GPU straight into this context's blocks."""
+        first_char, count = cstr._window(first_char, count)
+        bodies = np.ascontiguousarray(cstr.bodies[first_char:first_char + count])
+        hs = (C.c_uint64 * max(1, count))()
+        self.ctx._check(self.ctx._L.fhs_upload_string_compressed(self.ctx._h, _ptr(cstr.seed), _ptr(bodies), count,
+                                                                 first_char, hs))
+        return FheString([FheAsciiChar(self, hs[i]) for i in range(count)])
 
     def import_device(self, d_ptr):
         return FheAsciiChar(self, self.ctx._L.fhs_import_device(self.ctx._h, C.c_void_p(d_ptr)))

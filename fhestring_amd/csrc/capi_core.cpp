@@ -4,6 +4,7 @@
 
 #include "capi_internal.h"
 #include "luts.h"
+#include "seeded_kernels.h"
 
 extern "C" {
 
@@ -105,6 +106,44 @@ int fhs_load_server_key_file(fhs_ctx *ctx, const char *path) {
     if (fhs_read_server_key_file(path, bsk, ksk) != FHS_OK)
         return ctx->eng.ctx.fail(FHS_ERR_STATE, "cannot read key file (missing, truncated or wrong parameters)");
     return fhs_load_server_key(ctx, bsk.data(), ksk.data());
+}
+
+int fhs_load_compressed_server_key(fhs_ctx *ctx, const uint32_t seed[8], const uint64_t *bsk_bodies,
+                                   const uint64_t *ksk_bodies) {
+    if (!ctx) return FHS_ERR_ARG;
+    int rc = ctx->eng.ctx.load_compressed_server_key(seed, bsk_bodies, ksk_bodies);
+    if (rc) return rc;
+    return ctx->eng.on_key_loaded();
+}
+
+int fhs_read_compressed_server_key_file(const char *path, uint32_t seed[8], std::vector<uint64_t> &bsk_bodies,
+                                        std::vector<uint64_t> &ksk_bodies);
+
+int fhs_load_compressed_server_key_file(fhs_ctx *ctx, const char *path) {
+    if (!ctx || !path) return FHS_ERR_ARG;
+    uint32_t seed[8];
+    std::vector<uint64_t> bb, kb;
+    if (fhs_read_compressed_server_key_file(path, seed, bb, kb) != FHS_OK)
+        return ctx->eng.ctx.fail(FHS_ERR_STATE, "cannot read compressed key file (missing, truncated, not kind 4 or wrong parameters)");
+    return fhs_load_compressed_server_key(ctx, seed, bb.data(), kb.data());
+}
+
+int fhs_debug_chacha20_device(fhs_ctx *ctx, const uint32_t key[8], uint32_t counter, const uint32_t nonce[3], uint64_t *out,
+                              size_t n) {
+    if (!ctx || !key || !nonce || (n && !out)) return FHS_ERR_ARG;
+    auto &c = ctx->eng.ctx;
+    if (ctx->eng.planner) return c.fail(FHS_ERR_STATE, "planner context: nothing is computed");
+    if (n == 0) return FHS_OK;
+    if (hipSetDevice(c.device) != hipSuccess) return c.fail(FHS_ERR_HIP, "hipSetDevice failed");
+    fhs::SeedKey k;
+    for (int i = 0; i < 8; i++) k.w[i] = key[i];
+    uint64_t *d = nullptr;
+    hipError_t e = hipMalloc(&d, n * 8);
+    if (e == hipSuccess) e = fhs::launch_chacha20_stream(k, counter, nonce, d, n, c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (e == hipSuccess) e = hipMemcpy(out, d, n * 8, hipMemcpyDeviceToHost);
+    if (d) (void)hipFree(d);
+    return e == hipSuccess ? FHS_OK : c.hip_fail(e, "device keystream");
 }
 
 int fhs_pbs_batch(fhs_ctx *ctx, const uint64_t *in, const uint32_t *lut_idx, const uint64_t *luts,

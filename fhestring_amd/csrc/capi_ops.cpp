@@ -78,6 +78,16 @@ int fhs_upload_string(fhs_ctx *c, const uint64_t *blocks, size_t n, fhs_char_t *
     for (size_t i = 0; i < n; i++) out[i] = c->eng.new_char(&b[4 * i]);
     return FHS_OK;
 }
+int fhs_upload_string_compressed(fhs_ctx *c, const uint32_t seed[8], const uint64_t *bodies, size_t n, size_t first_char,
+                                 fhs_char_t *out) {
+    if (!c || !seed || (n && (!bodies || !out)) || first_char > ((size_t)1 << 60) || n > ((size_t)1 << 60)) return bad(c);
+    if (!c->eng.planner && hipSetDevice(c->eng.ctx.device) != hipSuccess) return c->eng.ctx.fail(FHS_ERR_HIP, "hipSetDevice failed");
+    std::vector<Bid> b(4 * n);
+    if (c->eng.from_compressed_many(seed, bodies, 4 * n, 4 * (uint64_t)first_char, b.data()))
+        return c->eng.ctx.fail(FHS_ERR_HIP, "compressed upload failed (device allocation, copy or expansion launch)");
+    for (size_t i = 0; i < n; i++) out[i] = c->eng.new_char(&b[4 * i]);
+    return FHS_OK;
+}
 fhs_char_t fhs_import_device(fhs_ctx *c, const uint64_t *d_blocks) {
     if (!c || !d_blocks) { bad(c); return 0; }
     Bid b[4] = {0, 0, 0, 0};

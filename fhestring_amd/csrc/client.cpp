@@ -171,12 +171,18 @@ ChaKey key_from_seed(uint64_t seed) {
 
 struct fhs_client {
     uint64_t seed = 0;            // only meaningful for insecure seeded clients (0 otherwise); kept in key files
+    bool insecure = false;        // fhs_client_create_insecure_seeded: public seeds are derived from `seed` (tests)
     ChaKey key{};
     std::vector<uint64_t> lwe_sk, glwe_sk, bsk, ksk;
     std::vector<uint64_t> bsk_mb2;   // pair key of FHS_ARITH_F64_FFT_MB2, generated on first use
     std::mutex mb2_mu;
     Rng enc_mask, enc_noise;      // encryption streams: public masks and noise never share a stream
     std::atomic<uint64_t> str_calls{0};   // fhs_client_encrypt_str: every call (and every character of it) has its own streams
+    std::atomic<uint64_t> cstr_calls{0};  // fhs_client_encrypt_str_compressed: the same, in a noise-stream range of its own
+    // compressed server key (fhs_client_compressed_server_key), generated on first use
+    ChaKey cseed{};
+    std::vector<uint64_t> cbsk_bodies, cksk_bodies;
+    std::mutex csk_mu;
 };
 
 namespace {
@@ -358,7 +364,9 @@ int fhs_client_create(fhs_client **out) {   // MyClientKey::from_params (client_
 }
 int fhs_client_create_insecure_seeded(uint64_t seed, fhs_client **out) {   // tests / benchmarks / identical keys on every rank
     if (!out) return FHS_ERR_ARG;
-    return client_create_with_key(key_from_seed(seed), seed, out);
+    const int rc = client_create_with_key(key_from_seed(seed), seed, out);
+    if (rc == FHS_OK) (*out)->insecure = true;
+    return rc;
 }
 void fhs_client_destroy(fhs_client *ck) { delete ck; }
 const uint64_t *fhs_client_bsk(const fhs_client *ck) { return ck ? ck->bsk.data() : nullptr; }
@@ -428,7 +436,7 @@ KeyFileHeader make_header(uint64_t kind) {
 }
 bool header_ok(const KeyFileHeader &h) {
     const KeyFileHeader w = make_header(h.kind);
-    return std::memcmp(&h, &w, sizeof(h)) == 0 && (h.kind == 1 || h.kind == 2 || h.kind == 3);
+    return std::memcmp(&h, &w, sizeof(h)) == 0 && (h.kind == 1 || h.kind == 2 || h.kind == 3 || h.kind == 4);
 }
 bool write_all(FILE *f, const void *p, size_t n) { return std::fwrite(p, 1, n, f) == n; }
 bool read_all(FILE *f, void *p, size_t n) { return std::fread(p, 1, n, f) == n; }
@@ -502,7 +510,7 @@ int fhs_read_server_key_file(const char *path, std::vector<uint64_t> &bsk, std::
     FILE *f = std::fopen(path, "rb");
     if (!f) return FHS_ERR_STATE;
     KeyFileHeader h;
-    bool ok = read_all(f, &h, sizeof(h)) && header_ok(h) && h.kind != 3;
+    bool ok = read_all(f, &h, sizeof(h)) && header_ok(h) && (h.kind == 1 || h.kind == 2);
     if (ok && h.kind == 1) ok = std::fseek(f, 8 + (LWE_N + POLY_N) * 8, SEEK_CUR) == 0;
     if (ok) {
         bsk.resize((size_t)LWE_N * 4 * POLY_N); ksk.resize((size_t)BIG_N * KS_LEVEL * SMALL_CT);
@@ -516,6 +524,184 @@ int fhs_client_secret_keys(const fhs_client *ck, uint64_t *lwe_sk, uint64_t *glw
     if (!ck || !lwe_sk || !glwe_sk) return FHS_ERR_ARG;
     std::memcpy(lwe_sk, ck->lwe_sk.data(), LWE_N * 8);
     std::memcpy(glwe_sk, ck->glwe_sk.data(), POLY_N * 8);
+    return FHS_OK;
+}
+
+}  // extern "C"
+
+// ---- compressed (seeded) ciphertexts and server keys: the convention of include/fhestring_hip.h -------------------
+namespace {
+
+ChaKey seed_key(const uint32_t seed[8]) {
+    ChaKey k;
+    for (int i = 0; i < 8; i++) k.w[i] = seed[i];
+    return k;
+}
+// Public seed of a compressed object: 32 bytes of OS entropy.  An insecure seeded client derives it from its 64-bit
+// seed, a tag per kind of object and the call number instead (reproducible tests) -- never from its ChaCha key.
+bool public_seed(const fhs_client *ck, uint64_t tag, uint64_t call, ChaKey &out) {
+    if (!ck->insecure) return os_entropy(&out, sizeof(out));
+    out = key_from_seed(ck->seed ^ tag);
+    out.w[6] ^= (uint32_t)call;
+    out.w[7] ^= (uint32_t)(call >> 32);
+    return true;
+}
+constexpr uint64_t SEED_TAG_STR = 0x5345454453545231ull, SEED_TAG_KEY = 0x534545444b455931ull;
+// Secret noise streams (DOM_NOISE) of compressed objects, disjoint from every other range of the client:
+//   7 (encrypt_char), 1000 + i (BSK), 100000 + i (KSK), 2000000 + g (pair key), STR_STREAM_BASE + (call << 24) + i
+//   (classic strings, [2^62, 2^63)).  Compressed strings: CSTR_STREAM_BASE + (call << 24) + character, [2^63, 2^63 + 2^62)
+//   for call < 2^38; the compressed server key: 4000000 + i (BSK, key bit i), 5000000 + i (KSK, row i).
+constexpr uint64_t CSTR_STREAM_BASE = 1ull << 63;
+constexpr uint64_t CBSK_NOISE_BASE = 4000000, CKSK_NOISE_BASE = 5000000;
+
+// sum_j draw_j * s_j over n draws of `mask`, s binary; the draws are streamed through a small buffer, never stored whole
+uint64_t streamed_dot(Rng &mask, const uint64_t *s, int n) {
+    uint64_t tmp[64], acc = 0;
+    for (int j = 0; j < n; j += 64) {
+        const int k = std::min(64, n - j);
+        mask.fill(tmp, (size_t)k);
+        for (int q = 0; q < k; q++) acc += tmp[q] & ((uint64_t)0 - s[j + q]);
+    }
+    return acc;
+}
+
+void keygen_compressed(fhs_client *ck) {
+    ck->cbsk_bodies.assign(FHS_CBSK_BODY_WORDS, 0);
+    ck->cksk_bodies.assign(FHS_CKSK_BODY_WORDS, 0);
+    const uint64_t qmask = ~((1ull << BSK_QUANT_BITS) - 1), qhalf = 1ull << (BSK_QUANT_BITS - 1);
+    const ChaKey seed = ck->cseed;
+    // BSK: the rows of keygen's GGSW_i(lwe_sk[i]) with seeded masks
+    for_each_char(LWE_N, [&](size_t i) {
+        std::vector<uint64_t> mask(POLY_N), prod(POLY_N);
+        Rng e(ck->key, CBSK_NOISE_BASE + i, DOM_NOISE);
+        for (int row = 0; row < 2; row++) {
+            Rng g(seed, 2 * i + row, FHS_DOM_SEEDED_BSK);
+            for (int n = 0; n < POLY_N; n++) mask[n] = g.next() & qmask;
+            mul_binary(mask.data(), ck->glwe_sk.data(), prod.data());
+            uint64_t *body = ck->cbsk_bodies.data() + (i * 2 + row) * POLY_N;
+            for (int n = 0; n < POLY_N; n++) {
+                uint64_t m;
+                if (row == 0) m = (uint64_t)0 - ((ck->lwe_sk[i] * ck->glwe_sk[n]) << (64 - PBS_BASE_LOG));
+                else m = n == 0 ? ck->lwe_sk[i] << (64 - PBS_BASE_LOG) : 0;
+                body[n] = (prod[n] + e.noise(GLWE_NOISE) + m + qhalf) & qmask;
+            }
+        }
+    });
+    // KSK: ksk[i][l] = LWE_small(glwe_sk[i] * 2^(64 - 3(l+1))) with seeded masks
+    for_each_char(BIG_N, [&](size_t i) {
+        Rng e(ck->key, CKSK_NOISE_BASE + i, DOM_NOISE);
+        for (int l = 0; l < KS_LEVEL; l++) {
+            Rng g(seed, (uint64_t)KS_LEVEL * i + l, FHS_DOM_SEEDED_KSK);
+            const uint64_t acc = streamed_dot(g, ck->lwe_sk.data(), LWE_N);
+            ck->cksk_bodies[i * KS_LEVEL + l] =
+                acc + e.noise(LWE_NOISE) + (ck->glwe_sk[i] << (64 - KS_BASE_LOG * (l + 1)));
+        }
+    });
+}
+bool compressed_server_key(fhs_client *ck) {
+    std::lock_guard<std::mutex> lk(ck->csk_mu);
+    if (!ck->cbsk_bodies.empty()) return true;
+    if (!public_seed(ck, SEED_TAG_KEY, 0, ck->cseed)) return false;
+    keygen_compressed(ck);
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fhs_client_encrypt_str_compressed(fhs_client *ck, const char *s, size_t len, size_t padding, uint32_t seed_out[8],
+                                      uint64_t *bodies) {
+    if (!ck || (len && !s) || !seed_out || !bodies) return FHS_ERR_ARG;
+    for (size_t i = 0; i < len; i++)
+        if ((unsigned char)s[i] >= 128 || s[i] == 0) return FHS_ERR_ARG;
+    const size_t n = len + padding;
+    if (n > STR_MAX_CHARS) return FHS_ERR_LIMIT;
+    const uint64_t call = ck->cstr_calls.fetch_add(1);
+    ChaKey seed;
+    if (!public_seed(ck, SEED_TAG_STR, call, seed)) return FHS_ERR_STATE;
+    for_each_char(n, [&](size_t i) {
+        Rng noise(ck->key, CSTR_STREAM_BASE + (call << 24) + i, DOM_NOISE);
+        const uint8_t v = i < len ? (uint8_t)s[i] : 0;
+        for (int b = 0; b < 4; b++) {
+            Rng mask(seed, 4 * i + b, FHS_DOM_SEEDED_STR);
+            const uint64_t acc = streamed_dot(mask, ck->glwe_sk.data(), BIG_N);
+            bodies[4 * i + b] = acc + noise.noise(GLWE_NOISE) + ((uint64_t)((v >> (2 * b)) & 3) << DELTA_LOG);
+        }
+    });
+    for (int i = 0; i < 8; i++) seed_out[i] = seed.w[i];
+    return FHS_OK;
+}
+
+int fhs_expand_compressed_str(const uint32_t seed[8], const uint64_t *bodies, size_t n, size_t first_char, uint64_t *out) {
+    if (!seed || (n && (!bodies || !out))) return FHS_ERR_ARG;
+    const ChaKey k = seed_key(seed);
+    for_each_char(n, [&](size_t i) {
+        for (int b = 0; b < 4; b++) {
+            uint64_t *ct = out + i * FHS_CHAR_WORDS + (size_t)b * BIG_CT;
+            Rng mask(k, 4 * (first_char + i) + b, FHS_DOM_SEEDED_STR);
+            mask.fill(ct, BIG_N);
+            ct[BIG_N] = bodies[4 * i + b];
+        }
+    });
+    return FHS_OK;
+}
+
+int fhs_client_compressed_server_key(fhs_client *ck, uint32_t seed_out[8], uint64_t *bsk_bodies, uint64_t *ksk_bodies) {
+    if (!ck || !seed_out || !bsk_bodies || !ksk_bodies) return FHS_ERR_ARG;
+    if (!compressed_server_key(ck)) return FHS_ERR_STATE;
+    for (int i = 0; i < 8; i++) seed_out[i] = ck->cseed.w[i];
+    std::memcpy(bsk_bodies, ck->cbsk_bodies.data(), FHS_CBSK_BODY_WORDS * 8);
+    std::memcpy(ksk_bodies, ck->cksk_bodies.data(), FHS_CKSK_BODY_WORDS * 8);
+    return FHS_OK;
+}
+
+int fhs_client_save_compressed_server_key(fhs_client *ck, const char *path) {
+    if (!ck || !path) return FHS_ERR_ARG;
+    if (!compressed_server_key(ck)) return FHS_ERR_STATE;
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return FHS_ERR_STATE;
+    const KeyFileHeader h = make_header(4);
+    bool ok = write_all(f, &h, sizeof(h)) && write_all(f, ck->cseed.w, 32) &&
+              write_all(f, ck->cbsk_bodies.data(), FHS_CBSK_BODY_WORDS * 8) &&
+              write_all(f, ck->cksk_bodies.data(), FHS_CKSK_BODY_WORDS * 8);
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? FHS_OK : FHS_ERR_STATE;
+}
+// reads a kind 4 file (used by fhs_load_compressed_server_key_file in capi_core.cpp)
+int fhs_read_compressed_server_key_file(const char *path, uint32_t seed[8], std::vector<uint64_t> &bsk_bodies,
+                                        std::vector<uint64_t> &ksk_bodies) {
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return FHS_ERR_STATE;
+    KeyFileHeader h;
+    bool ok = read_all(f, &h, sizeof(h)) && header_ok(h) && h.kind == 4;
+    if (ok) {
+        bsk_bodies.resize(FHS_CBSK_BODY_WORDS);
+        ksk_bodies.resize(FHS_CKSK_BODY_WORDS);
+        ok = read_all(f, seed, 32) && read_all(f, bsk_bodies.data(), bsk_bodies.size() * 8) &&
+             read_all(f, ksk_bodies.data(), ksk_bodies.size() * 8) && std::fgetc(f) == EOF;
+    }
+    std::fclose(f);
+    return ok ? FHS_OK : FHS_ERR_STATE;
+}
+
+int fhs_expand_compressed_server_key(const uint32_t seed[8], const uint64_t *bsk_bodies, const uint64_t *ksk_bodies,
+                                     uint64_t *bsk, uint64_t *ksk) {
+    if (!seed || !bsk_bodies || !ksk_bodies || !bsk || !ksk) return FHS_ERR_ARG;
+    const ChaKey k = seed_key(seed);
+    const uint64_t qmask = ~((1ull << BSK_QUANT_BITS) - 1);
+    for_each_char((size_t)LWE_N * 2, [&](size_t p) {          // GGSW row p = 2i + r
+        uint64_t *mask = bsk + p * 2 * POLY_N;
+        Rng g(k, p, FHS_DOM_SEEDED_BSK);
+        for (int n = 0; n < POLY_N; n++) mask[n] = g.next() & qmask;
+        std::memcpy(mask + POLY_N, bsk_bodies + p * POLY_N, POLY_N * 8);
+    });
+    for_each_char((size_t)BIG_N * KS_LEVEL, [&](size_t r) {   // row r = 5i + l
+        uint64_t *ct = ksk + r * SMALL_CT;
+        Rng g(k, r, FHS_DOM_SEEDED_KSK);
+        g.fill(ct, LWE_N);
+        ct[LWE_N] = ksk_bodies[r];
+    });
     return FHS_OK;
 }
 

@@ -1,10 +1,17 @@
 #include "context.h"
+#include "seeded_kernels.h"
+#include "../../include/fhestring_hip.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <thread>
 
 namespace fhs {
+
+namespace {
+constexpr size_t KSK_BYTES = (size_t)BIG_N * KS_LEVEL * SMALL_CT * sizeof(uint64_t);
+constexpr size_t BSK_BYTES = (size_t)LWE_N * 4 * POLY_N * sizeof(uint64_t);
+}  // namespace
 
 #define HIP_TRY(expr, what)                                \
     do {                                                   \
@@ -171,20 +178,61 @@ void Context::shutdown() {
 int Context::load_server_key(const uint64_t *bsk, const uint64_t *ksk) {
     if (!bsk || !ksk) return fail(-1, "null key pointer");
     HIP_TRY(hipSetDevice(device), "hipSetDevice");
+    uint64_t *d_ksk = nullptr;
+    HIP_TRY(hipMalloc(&d_ksk, KSK_BYTES), "hipMalloc ksk staging");
+    hipError_t e = hipMemcpy(d_ksk, ksk, KSK_BYTES, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !d_bsk_std) e = hipMalloc(&d_bsk_std, BSK_BYTES);
+    if (e == hipSuccess) e = hipMemcpy(d_bsk_std, bsk, BSK_BYTES, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(d_ksk);
+        return hip_fail(e, "copy server key");
+    }
+    const int rc = install_server_key(bsk, d_ksk);
+    (void)hipFree(d_ksk);
+    return rc;
+}
+
+// Compressed server key: the masks are regenerated on the device from the public seed (seeded_kernels.hip) into the
+// standard-domain BSK and a KSK staging buffer; the exact arithmetic's key is converted on the host from a read-back copy.
+int Context::load_compressed_server_key(const uint32_t seed[8], const uint64_t *bsk_bodies, const uint64_t *ksk_bodies) {
+    if (!seed || !bsk_bodies || !ksk_bodies) return fail(-1, "null key pointer");
+    HIP_TRY(hipSetDevice(device), "hipSetDevice");
+    SeedKey key;
+    for (int i = 0; i < 8; i++) key.w[i] = seed[i];
+    const size_t bb = FHS_CBSK_BODY_WORDS * 8, kb = FHS_CKSK_BODY_WORDS * 8;
+    uint64_t *d_ksk = nullptr, *d_bodies = nullptr;
+    std::vector<uint64_t> bsk((size_t)LWE_N * 4 * POLY_N);
+    hipError_t e = hipMalloc(&d_ksk, KSK_BYTES);
+    if (e == hipSuccess) e = hipMalloc(&d_bodies, bb + kb);
+    if (e == hipSuccess && !d_bsk_std) e = hipMalloc(&d_bsk_std, BSK_BYTES);
+    if (e == hipSuccess) e = hipMemcpy(d_bodies, bsk_bodies, bb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_bodies + FHS_CBSK_BODY_WORDS, ksk_bodies, kb, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_expand_seeded_bsk(key, d_bodies, d_bsk_std, stream);
+    if (e == hipSuccess) e = launch_expand_seeded_ksk(key, d_bodies + FHS_CBSK_BODY_WORDS, d_ksk, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = hipMemcpy(bsk.data(), d_bsk_std, BSK_BYTES, hipMemcpyDeviceToHost);
+    if (d_bodies) (void)hipFree(d_bodies);
+    if (e != hipSuccess) {
+        if (d_ksk) (void)hipFree(d_ksk);
+        return hip_fail(e, "compressed server key expansion");
+    }
+    const int rc = install_server_key(bsk.data(), d_ksk);
+    (void)hipFree(d_ksk);
+    return rc;
+}
+
+// The shared tail of both key loads: d_bsk_std holds the standard-domain BSK (`bsk`: a host copy of it), d_ksk the KSK.
+int Context::install_server_key(const uint64_t *bsk, const uint64_t *d_ksk) {
     // a pair key belongs to the server key it was generated with: a new server key invalidates it
     if (d_bsk_mb) { (void)hipFree(d_bsk_mb); d_bsk_mb = nullptr; }
     if (d_bsk_ntt_mb) { (void)hipFree(d_bsk_ntt_mb); d_bsk_ntt_mb = nullptr; }
-    const size_t ksk_bytes = (size_t)BIG_N * KS_LEVEL * SMALL_CT * sizeof(uint64_t);
     const size_t bsk_ntt_doubles = (size_t)LWE_N * 4 * 2 * POLY_N;
     if (!d_bsk_ntt) HIP_TRY(hipMalloc(&d_bsk_ntt, bsk_ntt_doubles * sizeof(double)), "hipMalloc bsk");
     {   // the KSK is only kept as byte planes in MFMA fragment order (ks_kernels.hip)
-        uint64_t *d_ksk = nullptr;
-        HIP_TRY(hipMalloc(&d_ksk, ksk_bytes), "hipMalloc ksk staging");
-        hipError_t e = hipMemcpy(d_ksk, ksk, ksk_bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess && !d_ksk_planes) e = hipMalloc(&d_ksk_planes, ks_planes_bytes());
+        hipError_t e = hipSuccess;
+        if (!d_ksk_planes) e = hipMalloc(&d_ksk_planes, ks_planes_bytes());
         if (e == hipSuccess) e = launch_ksk_to_planes(d_ksk, d_ksk_planes, stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        (void)hipFree(d_ksk);
         HIP_TRY(e, "ksk -> byte planes");
     }
     {
@@ -218,12 +266,8 @@ int Context::load_server_key(const uint64_t *bsk, const uint64_t *ksk) {
         if (fu != ht.fwd_uni || iu != ht.inv_uni || c != ht.crt_c)
             return fail(-3, "ntt_consts.inc does not match the derived twiddle tables (regenerate it)");
     }
-    {   // the standard-domain key stays on the device (48.6 MB of 288 GB): the Fourier-domain key is built from it with the
-        // device's own forward transform -- now if the f64 arithmetic is selected, otherwise the first time it is
-        const size_t n = (size_t)LWE_N * 4 * POLY_N;
-        if (!d_bsk_std) HIP_TRY(hipMalloc(&d_bsk_std, n * sizeof(uint64_t)), "hipMalloc bsk (standard domain)");
-        HIP_TRY(hipMemcpy(d_bsk_std, bsk, n * sizeof(uint64_t), hipMemcpyHostToDevice), "copy bsk (standard domain)");
-    }
+    // the standard-domain key stays on the device (48.6 MB of 288 GB): the Fourier-domain key is built from it with the
+    // device's own forward transform -- now if the f64 arithmetic is selected, otherwise the first time it is
     if (d_bsk_fft) {          // a new key invalidates the Fourier-domain form of the old one
         (void)hipFree(d_bsk_fft);
         d_bsk_fft = nullptr;

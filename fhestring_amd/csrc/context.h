@@ -93,6 +93,9 @@ class Context {
     int hip_fail(hipError_t e, const char *what);
 
     int load_server_key(const uint64_t *bsk, const uint64_t *ksk);
+    // seeded masks expanded on the device (fhs_load_compressed_server_key), then the same tail as load_server_key
+    int load_compressed_server_key(const uint32_t seed[8], const uint64_t *bsk_bodies, const uint64_t *ksk_bodies);
+    int install_server_key(const uint64_t *bsk, const uint64_t *d_ksk);
     int build_fft_key();
     // all device pointers; enqueues KS+MS then blind rotation on `s`
     int pbs_batch_device(const uint64_t *d_in, const uint32_t *d_lut_idx, const uint64_t *d_luts,

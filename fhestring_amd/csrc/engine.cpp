@@ -1,5 +1,6 @@
 #include "engine.h"
 #include "../../include/fhestring_hip.h"
+#include "seeded_kernels.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -222,6 +223,55 @@ int Engine::from_host_many(const uint64_t *cts, size_t count, Bid *out) {
         if (hipMemcpyAsync(upload_dev_, upload_pin_, words * 8, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) return undo(done + n);
         (void)hipEventRecord(upload_done_, ctx.stream);
         if (launch_scatter_blocks(upload_dev_, reinterpret_cast<uint64_t *const *>(upload_dev_ + n * BIG_CT), (int)n, ctx.stream) != hipSuccess)
+            return undo(done + n);
+        done += n;
+    }
+    return 0;
+}
+
+int Engine::from_compressed_many(const uint32_t seed[8], const uint64_t *bodies, size_t count, uint64_t first_block,
+                                 Bid *out) {
+    for (size_t i = 0; i < count; i++) out[i] = 0;
+    auto undo = [&](size_t n) {
+        for (size_t i = 0; i < n; i++) release(out[i]);
+        for (size_t i = 0; i < count; i++) out[i] = 0;
+        return -1;
+    };
+    auto add = [&](size_t i, uint64_t *d) {
+        Bid id = new_node();
+        nodes_[id].kind = BlockNode::MAT;
+        nodes_[id].dev = d;
+        out[i] = id;
+    };
+    if (planner) {
+        for (size_t i = 0; i < count; i++) {
+            uint64_t *d = alloc_block();
+            add(i, d);
+            if (trace_plan) { trace_.push_back(TR_UPLOAD); trace_.push_back((uint64_t)(uintptr_t)d); }
+        }
+        return 0;
+    }
+    (void)hipSetDevice(ctx.device);
+    SeedKey key;
+    for (int i = 0; i < 8; i++) key.w[i] = seed[i];
+    // staging: [n bodies][n destination pointers] (16 B per block) in the pinned buffer of from_host_many, which holds at
+    // least 260 full rows (533 k words): 4096 blocks per pass
+    constexpr size_t MAX_BATCH = 4096;
+    for (size_t done = 0; done < count;) {
+        const size_t n = std::min(MAX_BATCH, count - done);
+        if (!ensure_staging(1)) return undo(done);
+        (void)hipEventSynchronize(upload_done_);     // the previous copy has left the pinned buffer
+        std::memcpy(upload_pin_, bodies + done, n * 8);
+        for (size_t k = 0; k < n; k++) {
+            uint64_t *d = alloc_block();
+            if (!d) return undo(done + k);
+            add(done + k, d);
+            upload_pin_[n + k] = (uint64_t)(uintptr_t)d;
+        }
+        if (hipMemcpyAsync(upload_dev_, upload_pin_, 2 * n * 8, hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
+            return undo(done + n);
+        (void)hipEventRecord(upload_done_, ctx.stream);
+        if (launch_expand_seeded_blocks(key, first_block + done, upload_dev_, (int)n, ctx.stream) != hipSuccess)
             return undo(done + n);
         done += n;
     }

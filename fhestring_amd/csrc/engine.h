@@ -73,6 +73,10 @@ class Engine {
     // `count` ciphertexts of 2049 words each, back to back on the host: one copy through a pinned staging buffer and one
     // scatter launch into the pool blocks instead of one pageable copy (~10 us) per block
     int from_host_many(const uint64_t *cts, size_t count, Bid *out);
+    // The seeded twin (fhs_upload_string_compressed): `count` blocks of a compressed string, global block indices
+    // first_block .. first_block + count - 1, bodies[count].  Only body and destination pointer cross the bus; the
+    // masks are regenerated from the seed straight into the pool blocks (seeded_kernels.hip).
+    int from_compressed_many(const uint32_t seed[8], const uint64_t *bodies, size_t count, uint64_t first_block, Bid *out);
     Bid from_device(const uint64_t *d_ct);      // D2D copy
     Bid lin(const Term *terms, size_t n, int konst);
     Bid pbs(Bid x, int lut);

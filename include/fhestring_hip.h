@@ -462,7 +462,8 @@ int fhs_client_secret_keys(const fhs_client *ck, uint64_t *lwe_sk /*[742]*/, uin
 /* ---- key files (the reference derives serde traits at client_key.rs:9 and
  * server_key/mod.rs:13 but never calls them).  Little-endian: 64-byte header {magic "FHSKEY01", kind,
  * lwe_n, poly_n, ks_levels, ks_base_log, pbs_base_log, bsk_quant_bits}, then raw u64 arrays.
- * kind 1 = client key (secret keys + server key), kind 2 = server key only (bsk, ksk). */
+ * kind 1 = client key (secret keys + server key), kind 2 = server key only (bsk, ksk), kind 4 = compressed server key
+ * (below). */
 int fhs_client_save(const fhs_client *ck, const char *path, int server_key_only);
 int fhs_client_load(const char *path, fhs_client **out);             /* kind 1 files only */
 int fhs_load_server_key_file(fhs_ctx *ctx, const char *path);        /* kind 1 or 2 */
@@ -470,6 +471,65 @@ int fhs_load_server_key_file(fhs_ctx *ctx, const char *path);        /* kind 1 o
  * beside a kind 1 / 2 file and is loaded after it, converted for the arithmetic selected at that moment */
 int fhs_client_save_multibit_key(fhs_client *ck, const char *path);
 int fhs_load_multibit_key_file(fhs_ctx *ctx, const char *path);
+
+/* ---- compressed (seeded) ciphertexts and server keys --------------------------------------------------------
+ * The uniform mask of an LWE / GGSW row is drawn from a PUBLIC 256-bit seed, so only the body travels; the server
+ * regenerates the mask (on the GPU: fhs_upload_string_compressed, fhs_load_compressed_server_key).  The seeded-stream
+ * convention: every seeded row has its own ChaCha20 stream (RFC 8439 block function, the client generator's layout)
+ *   key = the seed as uint32_t[8];  st[12] = block counter, from 0;  st[13] = domain;  st[14] / st[15] = stream id
+ *   low / high;  draw k = keystream words (2k, 2k + 1), low word first (fhs_chacha20_stream's k-th value)
+ * and
+ *   string, character i (global index), block b   domain 4, stream 4i + b   draws 0..2047 = mask words 0..2047,
+ *                                                                            the body (word 2048) is sent
+ *   BSK, key bit i, GGSW row r                     domain 5, stream 2i + r   draws 0..2047, each & ~63 (the 58-bit
+ *                                                                            grid) = the row's mask polynomial; the
+ *                                                                            row's body polynomial is sent
+ *   KSK, row i, level l                            domain 6, stream 5i + l   draws 0..741 = ct[0..741], ct[742] sent
+ * Expanded layouts are exactly those of fhs_upload_string's input and of fhs_client_bsk / fhs_client_ksk.  Noise is
+ * the classic encryption's (secret streams of the client, never reused), so a compressed upload counts as one fresh
+ * encryption in the noise bookkeeping.  A seed reveals no secret generator state: it is OS entropy (an insecure seeded
+ * client derives it from its 64-bit seed and the call number, never from its secret generator key).
+ * Sizes: a character is 4 bodies (32 B) instead of 65 568 B, a string adds its 32-byte seed; the server key (kind 4
+ * file) is 24 395 872 B instead of 109 MB.  Results are not compressed. */
+#define FHS_DOM_SEEDED_STR 4
+#define FHS_DOM_SEEDED_BSK 5
+#define FHS_DOM_SEEDED_KSK 6
+#define FHS_SEED_WORDS 8                                   /* uint32_t words of a seed */
+#define FHS_CSTR_BODY_WORDS 4                              /* u64 words per character of a compressed string */
+#define FHS_CBSK_BODY_WORDS ((size_t)742 * 2 * 2048)       /* [742][2 rows][2048] */
+#define FHS_CKSK_BODY_WORDS ((size_t)2048 * 5)             /* [2048][5] */
+#define FHS_CKEY_FILE_BYTES ((size_t)64 + 32 + 742 * 2 * 2048 * 8 + 2048 * 5 * 8)   /* kind 4 key file */
+/* fhs_client_encrypt_str, compressed: same validation and limits; a fresh seed per call (seed_out) and
+ * bodies[(len+padding)][4].  The mask is streamed into the dot product and never stored. */
+int fhs_client_encrypt_str_compressed(fhs_client *ck, const char *s, size_t len, size_t padding, uint32_t seed_out[8],
+                                      uint64_t *bodies);
+/* Host reference expansion (public data only): characters first_char .. first_char + n - 1 of a compressed string,
+ * bodies[n][4] = THOSE characters' bodies -> out[n][4][2049].  first_char: a rank's window of a sharded string
+ * (fhs_dist_plan_windows). */
+int fhs_expand_compressed_str(const uint32_t seed[8], const uint64_t *bodies, size_t n, size_t first_char, uint64_t *out);
+/* Device expansion straight into the context's ciphertext blocks (16 B per block cross the bus: body and destination):
+ * the seeded twin of fhs_upload_string, same arguments as fhs_expand_compressed_str.  A planner context records the
+ * uploads and computes nothing. */
+int fhs_upload_string_compressed(fhs_ctx *ctx, const uint32_t seed[8], const uint64_t *bodies, size_t n, size_t first_char,
+                                 fhs_char_t *out);
+/* A second valid server key of the client, compressed (generated on first call and kept, like the pair key): its masks
+ * come from a public seed, its noise from secret streams of its own.  fhs_client_bsk / fhs_client_ksk do not change. */
+int fhs_client_compressed_server_key(fhs_client *ck, uint32_t seed_out[8], uint64_t *bsk_bodies /*[742][2][2048]*/,
+                                     uint64_t *ksk_bodies /*[2048][5]*/);
+/* kind 4 key file: header, seed (32 B), BSK bodies, KSK bodies.  fhs_client_load, fhs_load_server_key_file and
+ * fhs_load_multibit_key_file refuse it. */
+int fhs_client_save_compressed_server_key(fhs_client *ck, const char *path);
+/* Host reference expansion of a compressed server key to the standard-domain bsk[742][2][2][2048], ksk[2048][5][743]. */
+int fhs_expand_compressed_server_key(const uint32_t seed[8], const uint64_t *bsk_bodies, const uint64_t *ksk_bodies,
+                                     uint64_t *bsk, uint64_t *ksk);
+/* Expands on the device into what fhs_load_server_key fills (same pair-key invalidation, same arithmetic rules). */
+int fhs_load_compressed_server_key(fhs_ctx *ctx, const uint32_t seed[8], const uint64_t *bsk_bodies,
+                                   const uint64_t *ksk_bodies);
+int fhs_load_compressed_server_key_file(fhs_ctx *ctx, const char *path);   /* kind 4 only */
+/* Diagnostic: n draws of the DEVICE ChaCha20 from (key, counter, nonce) -- the same values as fhs_chacha20_stream,
+ * including the counter's carry into nonce[0] (+0x100 per wrap). */
+int fhs_debug_chacha20_device(fhs_ctx *ctx, const uint32_t key[8], uint32_t counter, const uint32_t nonce[3], uint64_t *out,
+                              size_t n);
 
 #ifdef __cplusplus
 }
