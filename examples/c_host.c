@@ -161,6 +161,23 @@ int main(int argc, char **argv) {
            FHS_NOISE_BUDGET_SUM_C2);
     ok &= st.max_input_sum_c2 <= FHS_NOISE_BUDGET_SUM_C2;
 
+    {   /* packed result download: the string comes back as one 16-bit GLWE per 512 characters instead of 65 568 B per
+         * character; the server only needs the client's packing key (1 MB) */
+        size_t mw = 0, bw = 0, len = 0;
+        fhs_packed_bytes(n, &mw, &bw);
+        uint16_t *mask16 = malloc((mw ? mw : 1) * sizeof(uint16_t)), *body16 = malloc((bw ? bw : 1) * sizeof(uint16_t));
+        char *got = calloc(n + 1, 1);
+        if (!mask16 || !body16 || !got) die("malloc", -1);
+        TRY(fhs_load_packing_key(ctx, fhs_client_packing_key(ck)));
+        TRY(fhs_download_string_packed(ctx, s, n, mask16, body16));
+        TRY(fhs_client_decrypt_packed_str(ck, mask16, body16, n, got, &len));
+        got[len] = 0;
+        ok &= report_str("download_packed", got, text);
+        printf("packed bytes: %llu instead of %llu\n", (unsigned long long)(2 * (mw + bw)),
+               (unsigned long long)(n * CHAR_WORDS * sizeof(uint64_t)));
+        free(mask16); free(body16); free(got);
+    }
+
     for (size_t i = 0; i < n; i++) TRY(fhs_release(ctx, s[i]));
     for (size_t i = 0; i < np; i++) TRY(fhs_release(ctx, p[i]));
     free(s); free(p);

@@ -18,7 +18,7 @@ _lib = None
 
 
 class FhsError(RuntimeError):
-    pass
+    code = None   # the FHS_ERR_* value where the error came from a library call that returned one
 
 
 def hip_runtimes():
@@ -342,6 +342,33 @@ def _declare(L):
     L.fhs_load_compressed_server_key_file.restype = i
     L.fhs_debug_chacha20_device.argtypes = [vp, vp, C.c_uint32, vp, vp, sz]
     L.fhs_debug_chacha20_device.restype = i
+    # packed result download
+    L.fhs_client_packing_key.argtypes = [vp]
+    L.fhs_client_packing_key.restype = u64p
+    L.fhs_client_save_packing_key.argtypes = [vp, C.c_char_p]
+    L.fhs_client_save_packing_key.restype = i
+    L.fhs_load_packing_key.argtypes = [vp, vp]
+    L.fhs_load_packing_key.restype = i
+    L.fhs_load_packing_key_file.argtypes = [vp, C.c_char_p]
+    L.fhs_load_packing_key_file.restype = i
+    L.fhs_packed_bytes.argtypes = [sz, C.POINTER(sz), C.POINTER(sz)]
+    L.fhs_packed_bytes.restype = None
+    L.fhs_download_string_packed.argtypes = [vp, vp, sz, vp, vp]
+    L.fhs_download_string_packed.restype = i
+    L.fhs_debug_download_string_packed64.argtypes = [vp, vp, sz, vp, vp, vp, vp]
+    L.fhs_debug_download_string_packed64.restype = i
+    L.fhs_pack_host.argtypes = [vp, vp, sz, vp, vp]
+    L.fhs_pack_host.restype = i
+    L.fhs_pack_switch16.argtypes = [vp, vp, sz, vp, vp]
+    L.fhs_pack_switch16.restype = i
+    L.fhs_debug_pack_node.argtypes = [vp, i, vp, vp, vp]
+    L.fhs_debug_pack_node.restype = i
+    L.fhs_client_decrypt_packed_str.argtypes = [vp, vp, vp, sz, C.c_char_p, C.POINTER(sz)]
+    L.fhs_client_decrypt_packed_str.restype = i
+    L.fhs_client_decrypt_packed_blocks.argtypes = [vp, vp, vp, sz, vp]
+    L.fhs_client_decrypt_packed_blocks.restype = i
+    L.fhs_client_encrypt_blocks.argtypes = [vp, vp, sz, vp]
+    L.fhs_client_encrypt_blocks.restype = i
 
 
 class CaptureRec(C.Structure):

@@ -8,6 +8,8 @@ from ._lib import FhsError, lib, check_single_hip_runtime
 BIG_CT = 2049
 SMALL_CT = 743
 POLY_N = 2048
+PACK_GROUP = 2048                     # blocks per packed GLWE (FHS_PACK_GROUP)
+PACK_KEY_WORDS = 11 * 3 * 2 * 2048    # FHS_PACK_KEY_WORDS
 
 
 def _ptr(a):
@@ -48,7 +50,9 @@ class Context:
 
     def _check(self, rc):
         if rc != 0:
-            raise FhsError("fhs error %d: %s" % (rc, self._L.fhs_last_error(self._h).decode()))
+            err = FhsError("fhs error %d: %s" % (rc, self._L.fhs_last_error(self._h).decode()))
+            err.code = rc
+            raise err
 
     ARITH_EXACT_NTT = 0
     ARITH_F64_FFT = 1
@@ -110,6 +114,12 @@ class Context:
         bsk_mb2 = np.ascontiguousarray(bsk_mb2, np.uint64)
         assert bsk_mb2.size == 371 * 3 * 4 * 2048
         self._check(self._L.fhs_load_multibit_key(self._h, _ptr(bsk_mb2)))
+
+    def load_packing_key(self, key):
+        """fhs_load_packing_key: the 11 automorphism keyswitch keys of the packed download, after load_server_key."""
+        key = np.ascontiguousarray(key, np.uint64)
+        assert key.size == PACK_KEY_WORDS
+        self._check(self._L.fhs_load_packing_key(self._h, _ptr(key)))
 
     def pbs_batch(self, cts, lut_idx, luts):
         cts = np.ascontiguousarray(cts, np.uint64).reshape(-1, BIG_CT)
@@ -309,6 +319,39 @@ class MyClientKey:
         if self._L.fhs_client_save_compressed_server_key(self._h, str(path).encode()) != 0:
             raise FhsError("cannot write compressed key file %s" % path)
 
+    def packing_key(self):
+        """fhs_client_packing_key: the automorphism keyswitch keys of the packed result download (generated on first
+        use, ~1 MB)."""
+        return np.ctypeslib.as_array(self._L.fhs_client_packing_key(self._h), shape=(PACK_KEY_WORDS,))
+
+    def save_packing_key(self, path):
+        """fhs_client_save_packing_key: kind 5 key file; it travels beside a kind 1 / 2 / 4 file."""
+        if self._L.fhs_client_save_packing_key(self._h, str(path).encode()) != 0:
+            raise FhsError("cannot write packing key file %s" % path)
+
+    def encrypt_blocks_raw(self, values):
+        """fhs_client_encrypt_blocks (diagnostic): one block per value mod 32, carry bits included: [n][2049]."""
+        values = np.ascontiguousarray(values, np.uint8)
+        out = np.empty((values.size, BIG_CT), np.uint64)
+        if self._L.fhs_client_encrypt_blocks(self._h, _ptr(values), values.size, _ptr(out)) != 0:
+            raise FhsError("fhs_client_encrypt_blocks failed")
+        return out
+
+    def decrypt_packed_blocks(self, p):
+        """Every block of a PackedFheString mod 32 (message, carry and padding bits): [4 n] u8."""
+        out = np.zeros(4 * len(p), np.uint8)
+        if self._L.fhs_client_decrypt_packed_blocks(self._h, _ptr(p.mask16), _ptr(p.body16), 4 * len(p), _ptr(out)) != 0:
+            raise FhsError("fhs_client_decrypt_packed_blocks failed")
+        return out
+
+    def decrypt_packed(self, p):
+        """fhs_client_decrypt_packed_str: MyClientKey.decrypt on a PackedFheString (truncates at the first NUL)."""
+        buf = C.create_string_buffer(len(p) + 1)
+        n = C.c_size_t()
+        if self._L.fhs_client_decrypt_packed_str(self._h, _ptr(p.mask16), _ptr(p.body16), len(p), buf, C.byref(n)) != 0:
+            raise FhsError("fhs_client_decrypt_packed_str failed")
+        return buf.raw[:n.value].decode("ascii")
+
     # reference-shaped API (server key needed to place ciphertexts on the device)
     def encrypt(self, string, padding, public_parameters=None, server_key=None):   # :45-65
         # the ciphertext only lives until fhs_upload_string has staged it: one scratch buffer per client, grown on demand
@@ -486,6 +529,79 @@ class CompressedFheString:
         return server_key.upload_compressed_string(self, first_char, count)
 
 
+class PackedFheString:
+    """A result string as it leaves the server packed: one 2048 x u16 GLWE mask per group of 512 characters and one u16
+    body per block (include/fhestring_hip.h, "packed result download").  Serialised form: magic FHSPSTR1, n (u64), masks,
+    bodies: 16 + 4096 * ceil(4 n / 2048) + 8 n bytes."""
+
+    MAGIC = b"FHSPSTR1"
+
+    def __init__(self, n_chars, mask16, body16):
+        self.n_chars = int(n_chars)
+        mask16, body16 = np.ascontiguousarray(mask16, np.uint16), np.ascontiguousarray(body16, np.uint16)
+        if mask16.size != self.groups(self.n_chars) * POLY_N or body16.size != 4 * self.n_chars:
+            raise ValueError("packed FheString of %d characters needs %d groups and %d bodies" %
+                             (self.n_chars, self.groups(self.n_chars), 4 * self.n_chars))
+        self.mask16 = mask16.reshape(self.groups(self.n_chars), POLY_N)
+        self.body16 = body16.reshape(4 * self.n_chars)
+
+    @staticmethod
+    def groups(n_chars):
+        return (4 * n_chars + PACK_GROUP - 1) // PACK_GROUP
+
+    @classmethod
+    def empty(cls, n_chars):
+        return cls(n_chars, np.zeros((cls.groups(n_chars), POLY_N), np.uint16), np.zeros(4 * n_chars, np.uint16))
+
+    def __len__(self):
+        return self.n_chars
+
+    @property
+    def nbytes(self):
+        return 16 + self.mask16.nbytes + self.body16.nbytes
+
+    def to_bytes(self):
+        return self.MAGIC + np.uint64(self.n_chars).tobytes() + self.mask16.tobytes() + self.body16.tobytes()
+
+    @classmethod
+    def from_bytes(cls, data):
+        data = bytes(data)
+        if data[:8] != cls.MAGIC or len(data) < 16:
+            raise ValueError("not a packed FheString")
+        n = int(np.frombuffer(data, np.uint64, 1, 8)[0])
+        g = cls.groups(n)
+        need = 16 + 2 * POLY_N * g + 8 * n
+        if n > (1 << 24) or len(data) != need:
+            raise ValueError("packed FheString of %d characters needs %d bytes, got %d" % (n, need, len(data)))
+        return cls(n, np.frombuffer(data, np.uint16, POLY_N * g, 16), np.frombuffer(data, np.uint16, 4 * n, 16 + 2 * POLY_N * g))
+
+
+def pack_host(key, blocks):
+    """fhs_pack_host: host reference of the packing; blocks [n][2049] -> 64-bit GLWEs (mask64, body64) [groups][2048]."""
+    key = np.ascontiguousarray(key, np.uint64)
+    blocks = np.ascontiguousarray(blocks, np.uint64).reshape(-1, BIG_CT)
+    assert key.size == PACK_KEY_WORDS
+    n = blocks.shape[0]
+    g = (n + PACK_GROUP - 1) // PACK_GROUP
+    mask64, body64 = np.zeros((g, POLY_N), np.uint64), np.zeros((g, POLY_N), np.uint64)
+    if lib().fhs_pack_host(_ptr(key), _ptr(blocks), n, _ptr(mask64), _ptr(body64)) != 0:
+        raise FhsError("fhs_pack_host failed")
+    return mask64, body64
+
+
+def pack_switch16(mask64, body64, n_blocks):
+    """fhs_pack_switch16: the storage switch of the host reference -> PackedFheString (n_blocks a multiple of 4) or, for
+    any other block count, the raw (mask16, body16)."""
+    mask64 = np.ascontiguousarray(mask64, np.uint64)
+    body64 = np.ascontiguousarray(body64, np.uint64)
+    g = (n_blocks + PACK_GROUP - 1) // PACK_GROUP
+    assert mask64.size == g * POLY_N and body64.size == g * POLY_N
+    mask16, body16 = np.zeros((g, POLY_N), np.uint16), np.zeros(n_blocks, np.uint16)
+    if lib().fhs_pack_switch16(_ptr(mask64), _ptr(body64), n_blocks, _ptr(mask16), _ptr(body16)) != 0:
+        raise FhsError("fhs_pack_switch16 failed")
+    return PackedFheString(n_blocks // 4, mask16, body16) if n_blocks % 4 == 0 else (mask16, body16)
+
+
 def expand_compressed_server_key(seed, bsk_bodies, ksk_bodies):
     """fhs_expand_compressed_server_key: host expansion to the standard-domain (bsk, ksk) of fhs_load_server_key."""
     seed = np.ascontiguousarray(seed, np.uint32)
@@ -615,6 +731,28 @@ class MyServerKey:
         self.ctx._check(self.ctx._L.fhs_upload_string_compressed(self.ctx._h, _ptr(cstr.seed), _ptr(bodies), count,
                                                                  first_char, hs))
         return FheString([FheAsciiChar(self, hs[i]) for i in range(count)])
+
+    def load_packing_key(self, key=None, path=None):
+        """fhs_load_packing_key (a MyClientKey, or the words of MyClientKey.packing_key()) / fhs_load_packing_key_file
+        (a kind 5 file): enables download_packed."""
+        if path is not None:
+            self.ctx._check(self.ctx._L.fhs_load_packing_key_file(self.ctx._h, str(path).encode()))
+        else:
+            self.ctx.load_packing_key(key.packing_key() if isinstance(key, MyClientKey) else key)
+
+    def download_packed(self, fhe_string, wide=False):
+        """fhs_download_string_packed: the string ring-packed on the GPU, 16 bits per word -> PackedFheString.
+        wide=True (diagnostic) also returns the 64-bit packed GLWEs (mask64, body64) before the storage switch."""
+        chars = list(fhe_string.chars if isinstance(fhe_string, FheString) else fhe_string)
+        p = PackedFheString.empty(len(chars))
+        if not wide:
+            self.ctx._check(self.ctx._L.fhs_download_string_packed(self.ctx._h, _harr(chars), len(chars), _ptr(p.mask16),
+                                                                   _ptr(p.body16)))
+            return p
+        mask64, body64 = np.zeros(p.mask16.shape, np.uint64), np.zeros(p.mask16.shape, np.uint64)
+        self.ctx._check(self.ctx._L.fhs_debug_download_string_packed64(self.ctx._h, _harr(chars), len(chars), _ptr(p.mask16),
+                                                                       _ptr(p.body16), _ptr(mask64), _ptr(body64)))
+        return p, mask64, body64
 
     def import_device(self, d_ptr):
         return FheAsciiChar(self, self.ctx._L.fhs_import_device(self.ctx._h, C.c_void_p(d_ptr)))

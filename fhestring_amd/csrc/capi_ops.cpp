@@ -187,6 +187,37 @@ int fhs_download_string(fhs_ctx *c, const fhs_char_t *chars, size_t n, uint64_t 
     }
     return c->eng.read_many(b.data(), b.size(), blocks);
 }
+int fhs_load_packing_key(fhs_ctx *c, const uint64_t *key) {
+    if (!c) return FHS_ERR_ARG;
+    if (c->eng.planner) return FHS_OK;                       // like fhs_load_multibit_key: a planner holds no key
+    if (int rc = c->eng.flush()) return rc;
+    return c->eng.ctx.load_packing_key(key);
+}
+int fhs_debug_download_string_packed64(fhs_ctx *c, const fhs_char_t *chars, size_t n, void *mask16, void *body16,
+                                       uint64_t *mask64, uint64_t *body64) {
+    if (!c || (n && (!chars || !mask16 || !body16)) || !mask64 != !body64) return bad(c);
+    std::vector<Bid> b(4 * n);
+    for (size_t i = 0; i < n; i++) {
+        if (!c->eng.valid_char(chars[i])) return bad(c);
+        const Bid *cb = c->eng.char_blocks(chars[i]);
+        for (int k = 0; k < 4; k++) b[4 * i + k] = cb[k];
+    }
+    return c->eng.read_packed(b.data(), b.size(), static_cast<uint16_t *>(mask16), static_cast<uint16_t *>(body16), mask64,
+                              body64);
+}
+int fhs_download_string_packed(fhs_ctx *c, const fhs_char_t *chars, size_t n, void *mask16, void *body16) {
+    return fhs_debug_download_string_packed64(c, chars, n, mask16, body16, nullptr, nullptr);
+}
+}  // extern "C"
+int fhs_read_packing_key_file(const char *path, std::vector<uint64_t> &key);   // client.cpp
+extern "C" {
+int fhs_load_packing_key_file(fhs_ctx *c, const char *path) {
+    if (!c || !path) return FHS_ERR_ARG;
+    std::vector<uint64_t> key;
+    if (fhs_read_packing_key_file(path, key) != FHS_OK)
+        return c->eng.ctx.fail(FHS_ERR_STATE, "cannot read packing key file (missing, truncated, not kind 5 or wrong parameters)");
+    return fhs_load_packing_key(c, key.data());
+}
 int fhs_export_device(fhs_ctx *c, fhs_char_t a, uint64_t *d_blocks) {
     if (!ok(c, a) || !d_blocks) return bad(c);
     const Bid *b = c->eng.char_blocks(a);

@@ -183,6 +183,8 @@ struct fhs_client {
     ChaKey cseed{};
     std::vector<uint64_t> cbsk_bodies, cksk_bodies;
     std::mutex csk_mu;
+    std::vector<uint64_t> pack_key;   // automorphism keyswitch keys of the packed result download, generated on first use
+    std::mutex pack_mu;
 };
 
 namespace {
@@ -436,7 +438,7 @@ KeyFileHeader make_header(uint64_t kind) {
 }
 bool header_ok(const KeyFileHeader &h) {
     const KeyFileHeader w = make_header(h.kind);
-    return std::memcmp(&h, &w, sizeof(h)) == 0 && (h.kind == 1 || h.kind == 2 || h.kind == 3 || h.kind == 4);
+    return std::memcmp(&h, &w, sizeof(h)) == 0 && h.kind >= 1 && h.kind <= 5;
 }
 bool write_all(FILE *f, const void *p, size_t n) { return std::fwrite(p, 1, n, f) == n; }
 bool read_all(FILE *f, void *p, size_t n) { return std::fread(p, 1, n, f) == n; }
@@ -706,3 +708,120 @@ int fhs_expand_compressed_server_key(const uint32_t seed[8], const uint64_t *bsk
 }
 
 }  // extern "C"
+
+// ---- packed result download (pack_host.cpp, pack_kernels.hip): key material and decryption ----------------------------
+namespace {
+
+// Automorphism keyswitch keys of the ring packing: for tree level lv = 1..11 (g = 2^lv + 1) and digit level l,
+// K[lv-1][l] = (mask, body) is a GLWE encryption under S of S(X^g) * 2^(64 - PACK_BASE_LOG (l + 1)), with the bootstrapping
+// key's noise and 58-bit grid.  Streams 6000000 + 3 (lv - 1) + l (DOM_MASK / DOM_NOISE), a range of their own.
+constexpr uint64_t PACK_STREAM_BASE = 6000000;
+void keygen_packing(fhs_client *ck) {
+    ck->pack_key.assign(FHS_PACK_KEY_WORDS, 0);
+    const uint64_t qmask = ~((1ull << BSK_QUANT_BITS) - 1), qhalf = 1ull << (BSK_QUANT_BITS - 1);
+    std::vector<std::thread> th;
+    for (int lv = 1; lv <= FHS_PACK_TREE_LEVELS; lv++) {
+        th.emplace_back([=] {
+            const uint32_t g = (1u << lv) + 1;
+            std::vector<uint64_t> sg(POLY_N), prod(POLY_N);
+            for (uint32_t i = 0; i < (uint32_t)POLY_N; i++) {          // S(X^g): coefficient i goes to i g mod 2N
+                const uint32_t r = (i * g) & (2 * POLY_N - 1);
+                sg[r & (POLY_N - 1)] = r >= (uint32_t)POLY_N ? (uint64_t)0 - ck->glwe_sk[i] : ck->glwe_sk[i];
+            }
+            for (int l = 0; l < FHS_PACK_LEVELS; l++) {
+                const uint64_t sid = PACK_STREAM_BASE + (uint64_t)FHS_PACK_LEVELS * (lv - 1) + l;
+                Rng gm(ck->key, sid, DOM_MASK), e(ck->key, sid, DOM_NOISE);
+                uint64_t *mask = ck->pack_key.data() + (((size_t)(lv - 1) * FHS_PACK_LEVELS + l) * 2) * POLY_N;
+                uint64_t *body = mask + POLY_N;
+                for (int n = 0; n < POLY_N; n++) mask[n] = gm.next() & qmask;
+                mul_binary(mask, ck->glwe_sk.data(), prod.data());
+                for (int n = 0; n < POLY_N; n++)
+                    body[n] = (prod[n] + e.noise(GLWE_NOISE) + (sg[n] << (64 - FHS_PACK_BASE_LOG * (l + 1))) + qhalf) & qmask;
+            }
+        });
+    }
+    for (auto &x : th) x.join();
+}
+
+// phases of one packed group: ph[j] = (body16[j] << 48) - ((mask16 << 48) (*) S)[j], j < count
+void packed_phases(const fhs_client *ck, const uint16_t *mask16, const uint16_t *body16, size_t count, uint64_t *ph) {
+    std::vector<uint64_t> a(POLY_N), prod(POLY_N);
+    for (int i = 0; i < POLY_N; i++) a[i] = (uint64_t)mask16[i] << 48;
+    mul_binary(a.data(), ck->glwe_sk.data(), prod.data());
+    for (size_t j = 0; j < count; j++) ph[j] = ((uint64_t)body16[j] << 48) - prod[j];
+}
+
+}  // namespace
+
+extern "C" {
+
+const uint64_t *fhs_client_packing_key(fhs_client *ck) {
+    if (!ck) return nullptr;
+    std::lock_guard<std::mutex> lk(ck->pack_mu);
+    if (ck->pack_key.empty()) keygen_packing(ck);
+    return ck->pack_key.data();
+}
+
+// kind 5: the packing key alone (it accompanies a kind 1 / 2 / 4 file, like kind 3)
+int fhs_client_save_packing_key(fhs_client *ck, const char *path) {
+    if (!ck || !path) return FHS_ERR_ARG;
+    const uint64_t *k = fhs_client_packing_key(ck);
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return FHS_ERR_STATE;
+    KeyFileHeader h = make_header(5);
+    bool ok = write_all(f, &h, sizeof(h)) && write_all(f, k, FHS_PACK_KEY_WORDS * 8);
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? FHS_OK : FHS_ERR_STATE;
+}
+
+int fhs_client_encrypt_blocks(fhs_client *ck, const uint8_t *values, size_t n, uint64_t *blocks) {
+    if (!ck || (n && (!values || !blocks))) return FHS_ERR_ARG;
+    for (size_t i = 0; i < n; i++) encrypt_block(ck, values[i] & 31, blocks + i * BIG_CT);
+    return FHS_OK;
+}
+
+int fhs_client_decrypt_packed_blocks(const fhs_client *ck, const void *mask16_, const void *body16_, size_t n_blocks,
+                                     uint8_t *out) {
+    const uint16_t *mask16 = static_cast<const uint16_t *>(mask16_), *body16 = static_cast<const uint16_t *>(body16_);
+    if (!ck || (n_blocks && (!mask16 || !body16 || !out))) return FHS_ERR_ARG;
+    std::vector<uint64_t> ph(FHS_PACK_GROUP);
+    for (size_t g = 0; g * FHS_PACK_GROUP < n_blocks; g++) {
+        const size_t count = std::min<size_t>(FHS_PACK_GROUP, n_blocks - g * FHS_PACK_GROUP);
+        packed_phases(ck, mask16 + g * POLY_N, body16 + g * FHS_PACK_GROUP, count, ph.data());
+        for (size_t j = 0; j < count; j++)
+            out[g * FHS_PACK_GROUP + j] = (uint8_t)(((ph[j] + (1ull << (DELTA_LOG - 1))) >> DELTA_LOG) & 31);
+    }
+    return FHS_OK;
+}
+
+int fhs_client_decrypt_packed_str(const fhs_client *ck, const void *mask16, const void *body16, size_t n_chars,
+                                  char *out, size_t *out_len) {
+    if (!ck || !out || !out_len || (n_chars && (!mask16 || !body16))) return FHS_ERR_ARG;
+    std::vector<uint8_t> blk(4 * n_chars);
+    if (int rc = fhs_client_decrypt_packed_blocks(ck, mask16, body16, 4 * n_chars, blk.data())) return rc;
+    size_t k = 0;
+    for (size_t i = 0; i < n_chars; i++) {
+        unsigned v = 0;
+        for (int b = 0; b < 4; b++) v += (unsigned)(blk[4 * i + b] & 15) << (2 * b);   // as fhs_client_decrypt_char
+        if ((v & 255) == 0) break;   // truncate at the first NUL
+        out[k++] = (char)(v & 255);
+    }
+    *out_len = k;
+    return FHS_OK;
+}
+
+}  // extern "C"
+
+// reads a kind 5 file (used by fhs_load_packing_key_file in capi_ops.cpp)
+int fhs_read_packing_key_file(const char *path, std::vector<uint64_t> &key) {
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return FHS_ERR_STATE;
+    KeyFileHeader h;
+    bool ok = read_all(f, &h, sizeof(h)) && header_ok(h) && h.kind == 5;
+    if (ok) {
+        key.resize(FHS_PACK_KEY_WORDS);
+        ok = read_all(f, key.data(), key.size() * 8) && std::fgetc(f) == EOF;
+    }
+    std::fclose(f);
+    return ok ? FHS_OK : FHS_ERR_STATE;
+}

@@ -1,4 +1,5 @@
 #include "context.h"
+#include "pack_kernels.h"
 #include "seeded_kernels.h"
 #include "../../include/fhestring_hip.h"
 
@@ -164,6 +165,9 @@ void Context::shutdown() {
     if (d_bsk_mb) (void)hipFree(d_bsk_mb);
     d_bsk_mb = nullptr;
     if (d_bsk_ntt_mb) (void)hipFree(d_bsk_ntt_mb);
+    if (d_pack_key_ntt) (void)hipFree(d_pack_key_ntt);
+    d_pack_key_ntt = nullptr;
+    pack_ws[0].release(); pack_ws[1].release(); pack_tab.release(); pack_out.release();
     d_bsk_ntt_mb = nullptr;
     if (d_fft_tables) (void)hipFree(d_fft_tables);
     d_bsk_fft = nullptr;
@@ -226,6 +230,7 @@ int Context::install_server_key(const uint64_t *bsk, const uint64_t *d_ksk) {
     // a pair key belongs to the server key it was generated with: a new server key invalidates it
     if (d_bsk_mb) { (void)hipFree(d_bsk_mb); d_bsk_mb = nullptr; }
     if (d_bsk_ntt_mb) { (void)hipFree(d_bsk_ntt_mb); d_bsk_ntt_mb = nullptr; }
+    if (d_pack_key_ntt) { (void)hipFree(d_pack_key_ntt); d_pack_key_ntt = nullptr; }   // so does the packing key
     const size_t bsk_ntt_doubles = (size_t)LWE_N * 4 * 2 * POLY_N;
     if (!d_bsk_ntt) HIP_TRY(hipMalloc(&d_bsk_ntt, bsk_ntt_doubles * sizeof(double)), "hipMalloc bsk");
     {   // the KSK is only kept as byte planes in MFMA fragment order (ks_kernels.hip)
@@ -370,6 +375,24 @@ int Context::load_multibit_key(const uint64_t *bsk_mb2) {
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     (void)hipFree(d_std);
     HIP_TRY(e, "pair key -> Fourier domain");
+    return 0;
+}
+
+// Packing key: converted on the host to the layout ntt_transform.h expects (both primes, 58-bit grid, 1/N folded in),
+// exactly like the exact-arithmetic bootstrapping key, whatever arithmetic is selected.  Comes after the server key (whose
+// load uploads the twiddle tables) and belongs to it.
+int Context::load_packing_key(const uint64_t *key) {
+    if (!key) return fail(-1, "null key pointer");
+    if (!key_loaded) return fail(-3, "load the server key before the packing key");
+    HIP_TRY(hipSetDevice(device), "hipSetDevice");
+    if (!ntt_slot_roots_are_bitreversed()) return fail(-3, "internal: NTT slot order is not bit-reversed");
+    const size_t n_d = PACK_KEY_POLYS * 2 * POLY_N;
+    std::vector<double> host(n_d);
+    convert_polys_to_ntt(key, host.data(), 11, PACK_KEY_POLYS, BSK_QUANT_BITS);
+    HIP_TRY(hipStreamSynchronize(stream), "stream sync");     // a queued packing may still read the previous key
+    if (!d_pack_key_ntt) HIP_TRY(hipMalloc(&d_pack_key_ntt, n_d * sizeof(double)), "hipMalloc packing key");
+    HIP_TRY(hipMemcpy(d_pack_key_ntt, host.data(), n_d * sizeof(double), hipMemcpyHostToDevice), "copy packing key");
+    HIP_TRY(prepare_device_for_packing(), "kernel attributes");
     return 0;
 }
 

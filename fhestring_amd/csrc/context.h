@@ -68,6 +68,9 @@ class Context {
     double *d_bsk_mb = nullptr;       // [371][K1,K2,K3][4][1024] complex
     double *d_bsk_ntt_mb = nullptr;   // arith 3 (FHS_ARITH_EXACT_NTT_MB2): [371][K1,K2,K3][4][2 primes][2048] residues
     const double *d_ntt_mono = nullptr;   // [2][4096] inside d_tables
+    // packed result download (pack_kernels.hip): the 11 automorphism keyswitch keys as residues modulo the two NTT primes
+    double *d_pack_key_ntt = nullptr;   // [11][3][2 cols][2 primes][2048]
+    int load_packing_key(const uint64_t *key);   // [FHS_PACK_KEY_WORDS] u64 standard domain (fhs_client_packing_key)
     int load_multibit_key(const uint64_t *bsk_mb2);   // [371][K1,K2,K3][4][2048] u64 standard domain (fhs_client_bsk_mb2)
     int fft4_max_batch = 512;
     size_t launch_chunk[4] = {0, 0, 0, 0};   // per arithmetic: ciphertexts per blind-rotation launch (0 = whole batch)         // batches up to this size use the 4-wavefront kernel (lower latency)
@@ -85,6 +88,7 @@ class Context {
     // scratch
     DevBuf dig_buf;                  // keyswitch digits of the current batch
     DevBuf ks_buf, ms_buf, in_buf, out_buf, lutidx_buf, luts_buf, tab_buf;
+    DevBuf pack_ws[2], pack_tab, pack_out;   // packing: ping-pong tree levels, leaf table, u16 result (allocated on first use, kept)
     KernelTimer timer;
 
     int init(int device_id);

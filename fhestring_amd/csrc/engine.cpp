@@ -1,4 +1,5 @@
 #include "engine.h"
+#include "pack_kernels.h"
 #include "../../include/fhestring_hip.h"
 #include "seeded_kernels.h"
 
@@ -1472,6 +1473,66 @@ int Engine::read_many(const Bid *b, size_t count, uint64_t *host_out) {
             std::memset(row, 0, BIG_CT * 8);
             row[BIG_N] = (uint64_t)nd.triv << DELTA_LOG;
         }
+        done += n;
+    }
+    return 0;
+}
+
+int Engine::read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *body16, uint64_t *mask64, uint64_t *body64) {
+    if (planner) return ctx.fail(-3, "planner context: nothing is computed, there is nothing to download");
+    if (!ctx.d_pack_key_ntt) return ctx.fail(-3, "packing key not loaded (fhs_load_packing_key)");
+    if (count == 0) return 0;
+    (void)hipSetDevice(ctx.device);
+    if (int rc = flush()) return rc;
+    for (size_t i = 0; i < count; i++)                               // as read_many: linear combinations become blocks first
+        if (nodes_[b[i]].kind == BlockNode::LIN)
+            if (int rc = materialize_lin(b[i])) return rc;
+    // level lv of a group writes (2048 >> lv) GLWEs of 32 KB: level 1 is 32 MB, level 2 16 MB, ping-pong between two
+    // buffers; four groups in flight keep the workspace at 192 MB
+    constexpr size_t MAX_GROUPS = 4, GLWE_BYTES = 2 * POLY_N * 8;
+    std::vector<PackLeaf> leaves;
+    std::vector<uint64_t> wide;
+    for (size_t done = 0; done < count;) {
+        const size_t n = std::min(MAX_GROUPS * PACK_GROUP, count - done);
+        const size_t groups = (n + PACK_GROUP - 1) / PACK_GROUP;
+        leaves.resize(n);
+        for (size_t k = 0; k < n; k++) {
+            const BlockNode &nd = nodes_[b[done + k]];
+            if (nd.kind == BlockNode::TRIV) leaves[k] = {nullptr, (uint64_t)nd.triv << DELTA_LOG};
+            else if (nd.kind == BlockNode::MAT) leaves[k] = {nd.dev, 0};
+            else return ctx.fail(-3, "internal: block not materialised");
+        }
+        hipError_t e = ctx.pack_tab.reserve(n * sizeof(PackLeaf));
+        if (e == hipSuccess) e = ctx.pack_ws[0].reserve(groups * (POLY_N / 2) * GLWE_BYTES);
+        if (e == hipSuccess) e = ctx.pack_ws[1].reserve(groups * (POLY_N / 4) * GLWE_BYTES);
+        if (e == hipSuccess) e = ctx.pack_out.reserve(groups * 2 * PACK_GROUP * sizeof(uint16_t));
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(ctx.pack_tab.ptr, leaves.data(), n * sizeof(PackLeaf), hipMemcpyHostToDevice, ctx.stream);
+        for (int lv = 1; lv <= PACK_TREE_LEVELS && e == hipSuccess; lv++) {
+            PackLevelParams p{};
+            p.lv = lv; p.groups = (int)groups; p.total = (uint32_t)n;
+            p.leaves = ctx.pack_tab.as<PackLeaf>();
+            p.src = ctx.pack_ws[lv & 1].as<uint64_t>();
+            p.dst = ctx.pack_ws[(lv - 1) & 1].as<uint64_t>();
+            p.key_ntt = ctx.d_pack_key_ntt; p.tw = ctx.tw;
+            e = launch_pack_level(p, ctx.stream);
+        }
+        uint16_t *d_mask = ctx.pack_out.as<uint16_t>(), *d_body = d_mask + groups * PACK_GROUP;
+        if (e == hipSuccess) e = launch_pack_switch16(ctx.pack_ws[0].as<uint64_t>(), d_mask, d_body, (int)groups, (uint32_t)n, ctx.stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(mask16 + done, d_mask, groups * PACK_GROUP * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(body16 + done, d_body, n * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx.stream);
+        if (e == hipSuccess && mask64 && body64) {
+            wide.resize(groups * 2 * POLY_N);
+            e = hipMemcpyAsync(wide.data(), ctx.pack_ws[0].ptr, groups * GLWE_BYTES, hipMemcpyDeviceToHost, ctx.stream);
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
+        if (e != hipSuccess) return ctx.hip_fail(e, "packed download");
+        if (mask64 && body64)
+            for (size_t g = 0; g < groups; g++) {
+                std::memcpy(mask64 + done + g * POLY_N, wide.data() + g * 2 * POLY_N, POLY_N * 8);
+                std::memcpy(body64 + done + g * POLY_N, wide.data() + (g * 2 + 1) * POLY_N, POLY_N * 8);
+            }
         done += n;
     }
     return 0;

@@ -139,6 +139,9 @@ class Engine {
     // `count` blocks into consecutive 2049-word rows on the host: one gather launch and one copy through the pinned staging
     // buffer per 2048 blocks instead of one synchronous copy per block (the twin of from_host_many)
     int read_many(const Bid *b, size_t count, uint64_t *host_out);
+    // packed download (pack_kernels.hip): ring-packs the blocks in groups of 2048 and stores them at 16 bits; mask16
+    // [groups][2048], body16 [count].  mask64 / body64 (diagnostic, may be null): the 64-bit GLWEs [groups][2048].
+    int read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *body16, uint64_t *mask64, uint64_t *body64);
     // flushes if needed (do_flush = false: the caller has made sure the block's tick is enqueued); wait=false: enqueue only
     int copy_block_to_device(Bid b, uint64_t *d_out, bool wait = true, bool do_flush = true);
     uint64_t blocks_live() const { return live_dev_blocks_; }

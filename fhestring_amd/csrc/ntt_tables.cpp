@@ -120,7 +120,10 @@ bool ntt_slot_roots_are_bitreversed() {
 }
 
 void convert_bsk_to_ntt(const uint64_t *bsk_std, double *out, int nthreads, int n_ggsw, int quant_bits) {
-    const size_t n_polys = (size_t)n_ggsw * 4;
+    convert_polys_to_ntt(bsk_std, out, nthreads, (size_t)n_ggsw * 4, quant_bits);
+}
+
+void convert_polys_to_ntt(const uint64_t *bsk_std, double *out, int nthreads, size_t n_polys, int quant_bits) {
     if (nthreads < 1) nthreads = 1;
     auto work = [&](int tid) {
         std::vector<uint64_t> a(POLY_N);

@@ -462,8 +462,8 @@ int fhs_client_secret_keys(const fhs_client *ck, uint64_t *lwe_sk /*[742]*/, uin
 /* ---- key files (the reference derives serde traits at client_key.rs:9 and
  * server_key/mod.rs:13 but never calls them).  Little-endian: 64-byte header {magic "FHSKEY01", kind,
  * lwe_n, poly_n, ks_levels, ks_base_log, pbs_base_log, bsk_quant_bits}, then raw u64 arrays.
- * kind 1 = client key (secret keys + server key), kind 2 = server key only (bsk, ksk), kind 4 = compressed server key
- * (below). */
+ * kind 1 = client key (secret keys + server key), kind 2 = server key only (bsk, ksk), kind 4 = compressed server key,
+ * kind 5 = packing key (both below). */
 int fhs_client_save(const fhs_client *ck, const char *path, int server_key_only);
 int fhs_client_load(const char *path, fhs_client **out);             /* kind 1 files only */
 int fhs_load_server_key_file(fhs_ctx *ctx, const char *path);        /* kind 1 or 2 */
@@ -490,7 +490,7 @@ int fhs_load_multibit_key_file(fhs_ctx *ctx, const char *path);
  * encryption in the noise bookkeeping.  A seed reveals no secret generator state: it is OS entropy (an insecure seeded
  * client derives it from its 64-bit seed and the call number, never from its secret generator key).
  * Sizes: a character is 4 bodies (32 B) instead of 65 568 B, a string adds its 32-byte seed; the server key (kind 4
- * file) is 24 395 872 B instead of 109 MB.  Results are not compressed. */
+ * file) is 24 395 872 B instead of 109 MB.  Results: see "packed result download" below. */
 #define FHS_DOM_SEEDED_STR 4
 #define FHS_DOM_SEEDED_BSK 5
 #define FHS_DOM_SEEDED_KSK 6
@@ -530,6 +530,58 @@ int fhs_load_compressed_server_key_file(fhs_ctx *ctx, const char *path);   /* ki
  * including the counter's carry into nonce[0] (+0x100 per wrap). */
 int fhs_debug_chacha20_device(fhs_ctx *ctx, const uint32_t key[8], uint32_t counter, const uint32_t nonce[3], uint64_t *out,
                               size_t n);
+
+/* ---- packed result download ---------------------------------------------------------------------------------
+ * Up to 2048 result blocks (512 characters) leave the server as ONE GLWE ciphertext under the client's GLWE key
+ * (N = 2048, k = 1), block j of the group in coefficient j, stored at 16 bits per word: a group is a 2048 x u16 mask and
+ * one u16 body per block present -- 4096 * ceil(4n / 2048) + 8n bytes for n characters (4097 characters: 69 640 B
+ * instead of 268 632 096 B).  The big LWE key of a block IS the flattened GLWE key, so the packing is the ring packing
+ * of Chen, Dai, Kim, Song (PackLWEs: 11 tree levels, one automorphism keyswitch per node) and the only new key material
+ * is 11 automorphism keyswitch keys (FHS_PACK_KEY_WORDS words, ~1 MB):
+ *   key[lv - 1][l] = (mask[2048], body[2048]): GLWE encryption of S(X^(2^lv + 1)) * 2^(64 - FHS_PACK_BASE_LOG (l + 1)),
+ *   lv = 1..11, l < FHS_PACK_LEVELS, on the bootstrapping key's 58-bit grid, body = mask * S + message + noise.
+ * All packing arithmetic is exact in Z_2^64[X]/(X^2048 + 1), whatever fhs_set_arithmetic selects: device and host
+ * reference agree in every word.  mask16 / body16 arguments are arrays of uint16_t (host byte order), passed as void
+ * pointers. */
+#define FHS_PACK_BASE_LOG 16
+#define FHS_PACK_LEVELS 3
+#define FHS_PACK_TREE_LEVELS 11
+#define FHS_PACK_GROUP 2048                                /* blocks per packed GLWE */
+#define FHS_PACK_KEY_WORDS ((size_t)11 * 3 * 2 * 2048)     /* [11][FHS_PACK_LEVELS][mask, body][2048] */
+#define FHS_PACK_KEY_FILE_BYTES ((size_t)64 + 11 * 3 * 2 * 2048 * 8)   /* kind 5 key file */
+/* The packing key of the client (generated on first call and kept; fhs_client_bsk / fhs_client_ksk do not change). */
+const uint64_t *fhs_client_packing_key(fhs_client *ck);
+/* kind 5 key file: header + the packing key.  It travels beside a kind 1 / 2 / 4 file, like kind 3; every other loader
+ * refuses it. */
+int fhs_client_save_packing_key(fhs_client *ck, const char *path);
+int fhs_load_packing_key(fhs_ctx *ctx, const uint64_t *key /*[FHS_PACK_KEY_WORDS]*/);
+int fhs_load_packing_key_file(fhs_ctx *ctx, const char *path);   /* kind 5 only */
+/* Sizes of the packed form of n_chars characters: u16 words of mask (2048 per group) and of body (4 per character). */
+void fhs_packed_bytes(size_t n_chars, size_t *mask_words, size_t *body_words);
+/* fhs_download_string, packed: mask16[ceil(4n / 2048)][2048], body16[4n] (group g's bodies start at 2048 g).  Takes any
+ * handle fhs_download takes and leaves it unchanged.  FHS_ERR_STATE without a packing key or on a planner context. */
+int fhs_download_string_packed(fhs_ctx *ctx, const fhs_char_t *chars, size_t n, void *mask16, void *body16);
+/* Diagnostic: the same, plus the 64-bit packed GLWEs before the storage switch, mask64 / body64 [ceil(4n/2048)][2048]. */
+int fhs_debug_download_string_packed64(fhs_ctx *ctx, const fhs_char_t *chars, size_t n, void *mask16, void *body16,
+                                       uint64_t *mask64, uint64_t *body64);
+/* Host reference (public data only, no GPU): blocks[n][2049] -> the 64-bit packed GLWEs mask64 / body64
+ * [ceil(n / 2048)][2048]; absent blocks of the last group count as zero. */
+int fhs_pack_host(const uint64_t *key, const uint64_t *blocks, size_t n_blocks, uint64_t *mask64, uint64_t *body64);
+/* Storage switch of the host reference: every word -> ((x + 2^47) >> 48) & 0xffff; mask16[groups][2048], body16[n_blocks]. */
+int fhs_pack_switch16(const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, void *mask16, void *body16);
+/* Diagnostic: one tree node of the host reference, level lv = 1..11: out = P + AutoKS_g(M) with T = X^(2048 >> lv) * O,
+ * P = E + T, M = E - T, g = 2^lv + 1; every argument a GLWE as mask[2048] | body[2048]. */
+int fhs_debug_pack_node(const uint64_t *key, int lv, const uint64_t *e /*[2][2048]*/, const uint64_t *o, uint64_t *out);
+/* Diagnostic: n single blocks with the given values mod 32 (message, carry and padding bits as they are) from the
+ * client's sequential streams, like fhs_client_encrypt_char: blocks[n][2049]. */
+int fhs_client_encrypt_blocks(fhs_client *ck, const uint8_t *values, size_t n, uint64_t *blocks);
+/* Client side: semantics of fhs_client_decrypt_str (truncates at the first NUL) on the packed form of n_chars
+ * characters ... */
+int fhs_client_decrypt_packed_str(const fhs_client *ck, const void *mask16, const void *body16, size_t n_chars,
+                                  char *out, size_t *out_len);
+/* ... and every block's value mod 32 (message and carry bits, padding bit included), out[n_blocks]. */
+int fhs_client_decrypt_packed_blocks(const fhs_client *ck, const void *mask16, const void *body16, size_t n_blocks,
+                                     uint8_t *out);
 
 #ifdef __cplusplus
 }
