@@ -342,6 +342,29 @@ def _declare(L):
     L.fhs_load_compressed_server_key_file.restype = i
     L.fhs_debug_chacha20_device.argtypes = [vp, vp, C.c_uint32, vp, vp, sz]
     L.fhs_debug_chacha20_device.restype = i
+    # public-key encryption: compact strings expanded on the GPU
+    L.fhs_client_public_key.argtypes = [vp, vp, vp]
+    L.fhs_client_public_key.restype = i
+    L.fhs_client_save_public_key.argtypes = [vp, C.c_char_p]
+    L.fhs_client_save_public_key.restype = i
+    L.fhs_public_key_create.argtypes = [vp, vp, vp]
+    L.fhs_public_key_create.restype = i
+    L.fhs_public_key_load.argtypes = [C.c_char_p, vp]
+    L.fhs_public_key_load.restype = i
+    L.fhs_public_key_destroy.argtypes = [vp]
+    L.fhs_public_key_destroy.restype = None
+    L.fhs_public_key_get.argtypes = [vp, vp, vp]
+    L.fhs_public_key_get.restype = i
+    L.fhs_public_key_set_insecure_seed.argtypes = [vp, C.c_uint64]
+    L.fhs_public_key_set_insecure_seed.restype = i
+    L.fhs_public_str_words.argtypes = [sz, vp, vp]
+    L.fhs_public_str_words.restype = None
+    L.fhs_public_encrypt_str.argtypes = [vp, C.c_char_p, sz, sz, vp, vp]
+    L.fhs_public_encrypt_str.restype = i
+    L.fhs_expand_public_str.argtypes = [vp, vp, sz, sz, sz, vp]
+    L.fhs_expand_public_str.restype = i
+    L.fhs_upload_string_public.argtypes = [vp, vp, vp, sz, sz, sz, vp]
+    L.fhs_upload_string_public.restype = i
     # packed result download
     L.fhs_client_packing_key.argtypes = [vp]
     L.fhs_client_packing_key.restype = u64p

@@ -181,7 +181,8 @@ class Context:
 # ---------------------------------------------------------------------------------------------
 # Mirror of the reference's types: MyClientKey (src/client_key.rs), FheAsciiChar / FheString
 # (src/ciphertext), MyServerKey (src/server_key/mod.rs).  Same method names and argument meaning;
-# `public_parameters` is accepted and ignored like the reference's dead parameter.
+# `public_parameters` is accepted and ignored by every operation, like the reference's dead parameter;
+# PublicParameters itself is real: it encrypts without the client key (PublicParameters.encrypt).
 # ---------------------------------------------------------------------------------------------
 CHAR_WORDS = 4 * BIG_CT
 MAX_FIND_LENGTH = 255
@@ -351,6 +352,22 @@ class MyClientKey:
         if self._L.fhs_client_decrypt_packed_str(self._h, _ptr(p.mask16), _ptr(p.body16), len(p), buf, C.byref(n)) != 0:
             raise FhsError("fhs_client_decrypt_packed_str failed")
         return buf.raw[:n.value].decode("ascii")
+
+    def public_key(self):
+        """fhs_client_public_key: (seed[8] u32, body[2048] u64) of the client's public key (generated on first use)."""
+        seed = np.zeros(8, np.uint32)
+        body = np.empty(2048, np.uint64)
+        if self._L.fhs_client_public_key(self._h, _ptr(seed), _ptr(body)) != 0:
+            raise FhsError("fhs_client_public_key failed")
+        return seed, body
+
+    def save_public_key(self, path):
+        """fhs_client_save_public_key: kind 6 key file (seed + B, 16 480 B; no secret in it)."""
+        if self._L.fhs_client_save_public_key(self._h, str(path).encode()) != 0:
+            raise FhsError("cannot write public key file %s" % path)
+
+    def get_public_parameters(self):                                                # client_key.rs:41-43
+        return PublicParameters(*self.public_key())
 
     # reference-shaped API (server key needed to place ciphertexts on the device)
     def encrypt(self, string, padding, public_parameters=None, server_key=None):   # :45-65
@@ -527,6 +544,139 @@ class CompressedFheString:
     def decompress(self, server_key, first_char=0, count=None):
         """Expands characters [first_char, first_char + count) on the server key's GPU -> FheString."""
         return server_key.upload_compressed_string(self, first_char, count)
+
+
+class PublicParameters:
+    """The reference's PublicParameters (src/ciphertext/public_parameters.rs): the client's public key and the number of
+    blocks per character.  It holds no secret: anyone can encrypt() with it, and only the client key decrypts
+    (include/fhestring_hip.h, "public-key encryption").  Serialised form: magic FHSPUBK1, seed, body (16 424 B)."""
+
+    MAGIC = b"FHSPUBK1"
+    num_blocks = 4
+
+    def __init__(self, seed, body, _handle=None):
+        self._L = lib()
+        if _handle is None:
+            seed = np.ascontiguousarray(seed, np.uint32).reshape(8)
+            body = np.ascontiguousarray(body, np.uint64).reshape(2048)
+            _handle = C.c_void_p()
+            if self._L.fhs_public_key_create(_ptr(seed), _ptr(body), C.byref(_handle)) != 0:
+                raise FhsError("fhs_public_key_create failed")
+        self._h = _handle
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.fhs_public_key_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @property
+    def public_key(self):
+        """(seed[8] u32, body[2048] u64)"""
+        seed = np.zeros(8, np.uint32)
+        body = np.empty(2048, np.uint64)
+        if self._L.fhs_public_key_get(self._h, _ptr(seed), _ptr(body)) != 0:
+            raise FhsError("fhs_public_key_get failed")
+        return seed, body
+
+    def to_bytes(self):
+        seed, body = self.public_key
+        return self.MAGIC + seed.tobytes() + body.tobytes()
+
+    @classmethod
+    def from_bytes(cls, data):
+        data = bytes(data)
+        if data[:8] != cls.MAGIC or len(data) != 8 + 32 + 2048 * 8:
+            raise ValueError("not a serialised PublicParameters")
+        return cls(np.frombuffer(data, np.uint32, 8, 8), np.frombuffer(data, np.uint64, 2048, 40))
+
+    def save(self, path):
+        """The kind 6 key file of fhs_client_save_public_key."""
+        seed, body = self.public_key
+        hdr = np.array([6, 742, 2048, 5, 3, 23, 6], np.uint64)
+        with open(str(path), "wb") as f:
+            f.write(b"FHSKEY01" + hdr.tobytes() + seed.tobytes() + body.tobytes())
+
+    @classmethod
+    def load(cls, path):
+        h = C.c_void_p()
+        if lib().fhs_public_key_load(str(path).encode(), C.byref(h)) != 0:
+            raise FhsError("cannot read public key file %s (missing, truncated or not kind 6)" % path)
+        return cls(None, None, _handle=h)
+
+    def set_insecure_seed(self, seed):
+        """TESTS ONLY (fhs_public_key_set_insecure_seed): reproducible encryption randomness."""
+        if self._L.fhs_public_key_set_insecure_seed(self._h, int(seed)) != 0:
+            raise FhsError("fhs_public_key_set_insecure_seed failed")
+
+    def encrypt(self, string, padding):
+        """fhs_public_encrypt_str: host only, no secret -> CompactFheString."""
+        data = string.encode("ascii") if isinstance(string, str) else bytes(string)
+        n = len(data) + int(padding)
+        mw, bw = C.c_size_t(), C.c_size_t()
+        self._L.fhs_public_str_words(n, C.byref(mw), C.byref(bw))
+        mask32 = np.empty(max(1, mw.value), np.uint32)[:mw.value]
+        body32 = np.empty(max(1, bw.value), np.uint32)[:bw.value]
+        rc = self._L.fhs_public_encrypt_str(self._h, data, len(data), int(padding), _ptr(mask32), _ptr(body32))
+        if rc != 0:
+            raise AssertionError("The input string must only contain ascii letters and not include null characters")
+        return CompactFheString(n, mask32, body32)
+
+
+class CompactFheString:
+    """A public-key encrypted FheString: one GLWE ciphertext per 2048 blocks (512 characters), every word at 32 bits --
+    mask32[ceil(4n / 2048)][2048] and body32[4n] (include/fhestring_hip.h, "public-key encryption").  Serialised form:
+    magic FHSPSTR1, n (u64), masks, bodies."""
+
+    MAGIC = b"FHSPSTR1"
+
+    def __init__(self, n, mask32, body32):
+        self.n = int(n)
+        self.mask32 = np.ascontiguousarray(mask32, np.uint32).reshape(-1, 2048)
+        self.body32 = np.ascontiguousarray(body32, np.uint32).reshape(-1)
+        assert self.mask32.shape[0] == (4 * self.n + 2047) // 2048 and self.body32.size == 4 * self.n
+
+    def __len__(self):
+        return self.n
+
+    @property
+    def nbytes(self):
+        return 16 + self.mask32.nbytes + self.body32.nbytes
+
+    def to_bytes(self):
+        return self.MAGIC + np.uint64(self.n).tobytes() + self.mask32.tobytes() + self.body32.tobytes()
+
+    @classmethod
+    def from_bytes(cls, data):
+        data = bytes(data)
+        if data[:8] != cls.MAGIC or len(data) < 16:
+            raise ValueError("not a compact FheString")
+        n = int(np.frombuffer(data, np.uint64, 1, 8)[0])
+        groups = (4 * n + 2047) // 2048
+        if len(data) != 16 + 8192 * groups + 16 * n:
+            raise ValueError("compact FheString of %d characters needs %d bytes, got %d"
+                             % (n, 16 + 8192 * groups + 16 * n, len(data)))
+        return cls(n, np.frombuffer(data, np.uint32, 2048 * groups, 16), np.frombuffer(data, np.uint32, 4 * n, 16 + 8192 * groups))
+
+    def _window(self, first_char, count):
+        if count is None:
+            count = len(self) - first_char
+        if not (0 <= first_char and 0 <= count and first_char + count <= len(self)):
+            raise ValueError("window [%d, %d + %d) outside a string of %d characters" % (first_char, first_char, count, len(self)))
+        return first_char, count
+
+    def expand(self, first_char=0, count=None):
+        """fhs_expand_public_str: characters [first_char, first_char + count) as classic [count][4][2049] words."""
+        first_char, count = self._window(first_char, count)
+        out = np.empty((count, 4, BIG_CT), np.uint64)
+        if lib().fhs_expand_public_str(_ptr(self.mask32), _ptr(self.body32), self.n, first_char, count, _ptr(out)) != 0:
+            raise FhsError("fhs_expand_public_str failed")
+        return out
 
 
 class PackedFheString:
@@ -753,6 +903,15 @@ class MyServerKey:
         self.ctx._check(self.ctx._L.fhs_debug_download_string_packed64(self.ctx._h, _harr(chars), len(chars), _ptr(p.mask16),
                                                                        _ptr(p.body16), _ptr(mask64), _ptr(body64)))
         return p, mask64, body64
+
+    def upload_compact_string(self, cstr, first_char=0, count=None):
+        """fhs_upload_string_public: characters [first_char, first_char + count) of a CompactFheString, sample-extracted
+        on the GPU straight into this context's blocks."""
+        first_char, count = cstr._window(first_char, count)
+        hs = (C.c_uint64 * max(1, count))()
+        self.ctx._check(self.ctx._L.fhs_upload_string_public(self.ctx._h, _ptr(cstr.mask32), _ptr(cstr.body32), len(cstr),
+                                                             first_char, count, hs))
+        return FheString([FheAsciiChar(self, hs[i]) for i in range(count)])
 
     def import_device(self, d_ptr):
         return FheAsciiChar(self, self.ctx._L.fhs_import_device(self.ctx._h, C.c_void_p(d_ptr)))

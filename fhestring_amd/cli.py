@@ -3,7 +3,8 @@
 
     python -m fhestring_amd.cli --string "hello" --pattern "ello" --n 1 --from "ello" --to "_llo"
 
-Encrypts the inputs with the client key, runs each MyServerKey method on the MI355X, decrypts,
+Encrypts the inputs with the client key (with `--public-key`: the strings through the client's PublicParameters, the
+way a third party would), runs each MyServerKey method on the MI355X, decrypts,
 compares with the plaintext semantics (python `str` here, Rust `std::str` there) and prints the
 reference's lines: `Test Passed: OK, Result: ..., ` / `Test Failed: Expected: ..., Got: ..., `
 (utils.rs:114-120) followed by `<Method> <duration>` (main.rs:114).  As in the reference the timed
@@ -93,16 +94,22 @@ def _py_split(method, s, p, n):
     raise KeyError(method)
 
 
-def run_fhe_str_method(sk, ck, a, method, out=None):             # utils.rs:122-718
+def run_fhe_str_method(sk, ck, a, method, out=None, pp=None):    # utils.rs:122-718
     out = sys.stdout if out is None else out
     s_plain, p_plain, f_plain, t_plain, n_plain = a.string, a.pattern, a.frm, a.to, a.n
-    s = ck.encrypt(s_plain, STRING_PADDING, None, sk)             # utils.rs:135-145
-    pat = ck.encrypt_no_padding(p_plain, sk)
-    frm = ck.encrypt_no_padding(f_plain, sk)
-    to = ck.encrypt_no_padding(t_plain, sk)
+    if pp is None:
+        enc = lambda text, padding: ck.encrypt(text, padding, None, sk)
+        enc0 = lambda text: ck.encrypt_no_padding(text, sk)
+    else:   # --public-key: every string is encrypted without the client key and expanded on the GPU
+        enc = lambda text, padding: sk.upload_compact_string(pp.encrypt(text, padding))
+        enc0 = lambda text: enc(text, 0).chars
+    s = enc(s_plain, STRING_PADDING)                              # utils.rs:135-145
+    pat = enc0(p_plain)
+    frm = enc0(f_plain)
+    to = enc0(t_plain)
     n = ck.encrypt_char(n_plain & 255, sk)
     dch, dst = ck.decrypt_char, ck.decrypt
-    other = lambda: ck.encrypt(p_plain, STRING_PADDING, None, sk)
+    other = lambda: enc(p_plain, STRING_PADDING)
     clear = lambda text: [sk.trivial(b) for b in text.encode("ascii")]
     pos = lambda v: v if v >= 0 else MAX_FIND_LENGTH
     ok = True
@@ -205,17 +212,21 @@ def main(argv=None):
     ap.add_argument("--methods", default="", help="comma-separated subset (default: all non-split methods)")
     ap.add_argument("--seed", type=int, default=None,
                     help="reproducible (insecure) keys for tests; default: OS entropy, like the reference")
+    ap.add_argument("--public-key", action="store_true",
+                    help="encrypt the input strings with the client's PublicParameters (no secret key on the encrypting "
+                         "side; compact ciphertexts expanded on the GPU) instead of the client key")
     a = ap.parse_args(argv)
     assert a.n <= MAX_REPETITIONS, "n must be <= MAX_REPETITIONS"  # src/main.rs:37-40
     ck = MyClientKey.from_params(seed=a.seed)                     # src/main.rs:43
     sk = ck.get_server_key(0, arith={"exact": 0, "fft": 1, "fft_mb2": 2, "exact_mb2": 3}[a.arith])
     sk.set_mode(1 if a.mode == "fused" else 0)
+    pp = ck.get_public_parameters() if a.public_key else None
     methods = [m for m in a.methods.split(",") if m] or METHODS
     failed = 0
     for m in methods:
         t0 = time.perf_counter()
         try:
-            if not run_fhe_str_method(sk, ck, a, m):
+            if not run_fhe_str_method(sk, ck, a, m, pp=pp):
                 failed += 1
         except OverflowError as e:                                # the reference panics here
             sys.stdout.write("panicked: %s, " % e)

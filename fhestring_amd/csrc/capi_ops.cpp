@@ -88,6 +88,19 @@ int fhs_upload_string_compressed(fhs_ctx *c, const uint32_t seed[8], const uint6
     for (size_t i = 0; i < n; i++) out[i] = c->eng.new_char(&b[4 * i]);
     return FHS_OK;
 }
+int fhs_upload_string_public(fhs_ctx *c, const void *mask32, const void *body32, size_t n_total, size_t first_char,
+                             size_t count, fhs_char_t *out) {
+    if (!c || n_total > ((size_t)1 << 24) || first_char > n_total || count > n_total - first_char ||
+        (count && (!mask32 || !body32 || !out)))
+        return bad(c);
+    if (!c->eng.planner && hipSetDevice(c->eng.ctx.device) != hipSuccess) return c->eng.ctx.fail(FHS_ERR_HIP, "hipSetDevice failed");
+    std::vector<Bid> b(4 * count);
+    if (c->eng.from_public_many(static_cast<const uint32_t *>(mask32), static_cast<const uint32_t *>(body32), 4 * count,
+                                4 * (uint64_t)first_char, b.data()))
+        return c->eng.ctx.fail(FHS_ERR_HIP, "public-key upload failed (device allocation, copy or expansion launch)");
+    for (size_t i = 0; i < count; i++) out[i] = c->eng.new_char(&b[4 * i]);
+    return FHS_OK;
+}
 fhs_char_t fhs_import_device(fhs_ctx *c, const uint64_t *d_blocks) {
     if (!c || !d_blocks) { bad(c); return 0; }
     Bid b[4] = {0, 0, 0, 0};

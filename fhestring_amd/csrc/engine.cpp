@@ -1,6 +1,7 @@
 #include "engine.h"
 #include "pack_kernels.h"
 #include "../../include/fhestring_hip.h"
+#include "pk_kernels.h"
 #include "seeded_kernels.h"
 
 #include <algorithm>
@@ -273,6 +274,59 @@ int Engine::from_compressed_many(const uint32_t seed[8], const uint64_t *bodies,
             return undo(done + n);
         (void)hipEventRecord(upload_done_, ctx.stream);
         if (launch_expand_seeded_blocks(key, first_block + done, upload_dev_, (int)n, ctx.stream) != hipSuccess)
+            return undo(done + n);
+        done += n;
+    }
+    return 0;
+}
+
+int Engine::from_public_many(const uint32_t *mask32, const uint32_t *body32, size_t count, uint64_t first_block, Bid *out) {
+    for (size_t i = 0; i < count; i++) out[i] = 0;
+    auto undo = [&](size_t n) {
+        for (size_t i = 0; i < n; i++) release(out[i]);
+        for (size_t i = 0; i < count; i++) out[i] = 0;
+        return -1;
+    };
+    auto add = [&](size_t i, uint64_t *d) {
+        Bid id = new_node();
+        nodes_[id].kind = BlockNode::MAT;
+        nodes_[id].dev = d;
+        out[i] = id;
+    };
+    if (planner) {
+        for (size_t i = 0; i < count; i++) {
+            uint64_t *d = alloc_block();
+            add(i, d);
+            if (trace_plan) { trace_.push_back(TR_UPLOAD); trace_.push_back((uint64_t)(uintptr_t)d); }
+        }
+        return 0;
+    }
+    (void)hipSetDevice(ctx.device);
+    // staging, in the pinned buffer of from_host_many (at least 533 k words): [n destination pointers][n u32 bodies]
+    // [u32 masks of the groups the pass touches, 2048 each] -- at most three groups for 4096 blocks
+    constexpr size_t MAX_BATCH = 4096;
+    for (size_t done = 0; done < count;) {
+        const size_t n = std::min(MAX_BATCH, count - done);
+        const uint64_t t0 = first_block + done;
+        const size_t g0 = (size_t)(t0 / FHS_PK_GROUP), groups = (size_t)((t0 + n - 1) / FHS_PK_GROUP) - g0 + 1;
+        const size_t body_at = n, mask_at = n + (n + 1) / 2, words = mask_at + groups * (BIG_N / 2);
+        if (!ensure_staging(1)) return undo(done);
+        (void)hipEventSynchronize(upload_done_);     // the previous copy has left the pinned buffer
+        for (size_t k = 0; k < n; k++) {
+            uint64_t *d = alloc_block();
+            if (!d) return undo(done + k);
+            add(done + k, d);
+            upload_pin_[k] = (uint64_t)(uintptr_t)d;
+        }
+        std::memcpy(upload_pin_ + body_at, body32 + t0, n * 4);
+        std::memcpy(upload_pin_ + mask_at, mask32 + g0 * BIG_N, groups * BIG_N * 4);
+        if (hipMemcpyAsync(upload_dev_, upload_pin_, words * 8, hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
+            return undo(done + n);
+        (void)hipEventRecord(upload_done_, ctx.stream);
+        if (launch_expand_public_blocks(reinterpret_cast<const uint32_t *>(upload_dev_ + mask_at),
+                                        reinterpret_cast<const uint32_t *>(upload_dev_ + body_at),
+                                        reinterpret_cast<uint64_t *const *>(upload_dev_), (uint32_t)(t0 % FHS_PK_GROUP), (int)n,
+                                        ctx.stream) != hipSuccess)
             return undo(done + n);
         done += n;
     }

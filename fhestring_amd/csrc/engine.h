@@ -77,6 +77,11 @@ class Engine {
     // first_block .. first_block + count - 1, bodies[count].  Only body and destination pointer cross the bus; the
     // masks are regenerated from the seed straight into the pool blocks (seeded_kernels.hip).
     int from_compressed_many(const uint32_t seed[8], const uint64_t *bodies, size_t count, uint64_t first_block, Bid *out);
+    // The public-key twin (fhs_upload_string_public): `count` blocks of a compact string, global block indices
+    // first_block .. first_block + count - 1; mask32 / body32 are the WHOLE string's.  The u32 masks of the groups a
+    // pass touches, its u32 bodies and the destination pointers cross the bus; every block is a sample extraction
+    // written straight into its pool block (pk_kernels.hip).
+    int from_public_many(const uint32_t *mask32, const uint32_t *body32, size_t count, uint64_t first_block, Bid *out);
     Bid from_device(const uint64_t *d_ct);      // D2D copy
     Bid lin(const Term *terms, size_t n, int konst);
     Bid pbs(Bid x, int lut);

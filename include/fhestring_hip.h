@@ -463,7 +463,7 @@ int fhs_client_secret_keys(const fhs_client *ck, uint64_t *lwe_sk /*[742]*/, uin
  * server_key/mod.rs:13 but never calls them).  Little-endian: 64-byte header {magic "FHSKEY01", kind,
  * lwe_n, poly_n, ks_levels, ks_base_log, pbs_base_log, bsk_quant_bits}, then raw u64 arrays.
  * kind 1 = client key (secret keys + server key), kind 2 = server key only (bsk, ksk), kind 4 = compressed server key,
- * kind 5 = packing key (both below). */
+ * kind 5 = packing key, kind 6 = public key (all three below). */
 int fhs_client_save(const fhs_client *ck, const char *path, int server_key_only);
 int fhs_client_load(const char *path, fhs_client **out);             /* kind 1 files only */
 int fhs_load_server_key_file(fhs_ctx *ctx, const char *path);        /* kind 1 or 2 */
@@ -582,6 +582,56 @@ int fhs_client_decrypt_packed_str(const fhs_client *ck, const void *mask16, cons
 /* ... and every block's value mod 32 (message and carry bits, padding bit included), out[n_blocks]. */
 int fhs_client_decrypt_packed_blocks(const fhs_client *ck, const void *mask16, const void *body16, size_t n_blocks,
                                      uint8_t *out);
+
+/* ---- public-key encryption: compact strings expanded on the GPU --------------------------------------------
+ * Anyone who holds the client's PUBLIC key can encrypt a string this library computes on (the reference hands one out:
+ * PublicKey::new / PublicParameters, client_key.rs:30-43).  The big LWE key of a block is the flattened GLWE key S, so
+ * the public key is one RLWE sample in R = Z_2^64[X]/(X^2048 + 1),
+ *   A = 2048 draws of the ChaCha20 stream of a PUBLIC 256-bit seed (the seeded-stream convention above), domain 7,
+ *       stream 0;   B = A S + E   (E: the GLWE noise, from a secret stream of the client),
+ * 32 B + 16 384 B in all, and one GLWE ciphertext under it carries 2048 blocks = 512 characters.  Block t = 4 x
+ * character + digit of a string sits in group g = t / 2048 at coefficient j = t % 2048.  Per group the encryptor draws
+ * U (uniform binary) and E1, E2 (GLWE noise) and sends
+ *   mask = A U + E1,   body = B U + E2 + sum_j m_j 2^59 X^j      (wrapping 64-bit arithmetic)
+ * with every word stored at 32 bits, (x + 2^31) >> 32: mask32[ceil(4n / 2048)][2048] and body32[4n] (group g's bodies
+ * start at 2048 g), 8192 ceil(4n / 2048) + 16 n bytes for n characters (4097 characters: 139 280 B).  The server turns
+ * block (g, j) into a classic 2049-word block by sample extraction, words widened by << 32:
+ *   a_i = A_g[j - i] for i <= j,   a_i = -A_g[2048 + j - i] for i > j,   b = B_g[j]      (A_g, B_g: the group's mask, body)
+ * Noise of an expanded block: E U - E1 S + E2 and the storage rounding, sigma ~ 2^35.2 against a bootstrap output's
+ * 2^48.9, so a public-key upload counts as one fresh encryption (sum c^2 = 1) like every other upload (DESIGN.md
+ * section 12).  Not wire compatible with tfhe-rs's CompactPublicKey / CompactCiphertextList, whose roles these play. */
+#define FHS_DOM_PUBLIC_KEY 7
+#define FHS_PK_BODY_WORDS 2048                             /* u64 words of B */
+#define FHS_PK_GROUP 2048                                  /* blocks per public-key GLWE */
+#define FHS_PK_FILE_BYTES ((size_t)64 + 32 + 2048 * 8)     /* kind 6 key file */
+/* The client's public key (generated on first call and kept, like the packing key). */
+int fhs_client_public_key(fhs_client *ck, uint32_t seed_out[8], uint64_t *body_out /*[2048]*/);
+/* kind 6 key file: header, seed (32 B), B.  Every other loader refuses it. */
+int fhs_client_save_public_key(fhs_client *ck, const char *path);
+/* A public-key handle holds NO secret; it is an opaque pointer and nothing below takes an fhs_client.
+ * fhs_public_key_load reads kind 6 files only. */
+int fhs_public_key_create(const uint32_t seed[8], const uint64_t *body /*[2048]*/, void **pk_out);
+int fhs_public_key_load(const char *path, void **pk_out);
+void fhs_public_key_destroy(void *pk);
+/* The handle's key back: seed_out[8], body_out[2048]. */
+int fhs_public_key_get(const void *pk, uint32_t seed_out[8], uint64_t *body_out);
+/* TEST ONLY: the encryptor's randomness (U, E1, E2) comes from this 64-bit seed and the number of calls since, instead
+ * of a ChaCha key drawn from getrandom(2) per call. */
+int fhs_public_key_set_insecure_seed(void *pk, uint64_t seed);
+/* u32 words of mask (2048 per group) and of body (4 per character) of n_chars characters. */
+void fhs_public_str_words(size_t n_chars, size_t *mask_words, size_t *body_words);
+/* Host, no secret, no GPU.  The input rules of fhs_client_encrypt_str (ASCII, no NUL, `padding` NULs appended);
+ * mask32 / body32 are arrays of uint32_t sized by fhs_public_str_words(len + padding). */
+int fhs_public_encrypt_str(void *pk, const char *s, size_t len, size_t padding, void *mask32, void *body32);
+/* Host reference expansion (public data only): characters first_char .. first_char + count - 1 of a string of n_total
+ * characters, mask32 / body32 = the WHOLE string's -> out[count][4][2049]. */
+int fhs_expand_public_str(const void *mask32, const void *body32, size_t n_total, size_t first_char, size_t count,
+                          uint64_t *out);
+/* Device expansion straight into the context's ciphertext blocks, same arguments: only the masks of the groups the
+ * window touches, its bodies and the destinations cross the bus.  A planner context records the uploads and computes
+ * nothing. */
+int fhs_upload_string_public(fhs_ctx *ctx, const void *mask32, const void *body32, size_t n_total, size_t first_char,
+                             size_t count, fhs_char_t *out);
 
 #ifdef __cplusplus
 }

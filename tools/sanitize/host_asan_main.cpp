@@ -1,5 +1,5 @@
 // ASan/UBSan driver of the product's HOST-ONLY code (no device is touched): client keygen / encrypt / decrypt /
-// key files (client.cpp), the twiddle and key transforms (ntt_tables.cpp, fft_tables.cpp), and the whole DAG layer --
+// key files (client.cpp), public-key encryption and its expansion (pk_host.cpp), the twiddle and key transforms (ntt_tables.cpp, fft_tables.cpp), and the whole DAG layer --
 // engine.cpp graph logic, radix.cpp, strings.cpp, capi_*.cpp -- through a planner context (fhs_ctx_create_planner),
 // which records and levelises every string op of the C ABI without executing anything.
 // Built by `make -C fhestring_amd/csrc asan`; run by tests/test_sanitizers.py.  CPU only.
@@ -41,6 +41,34 @@ int main() {
     fhs_client *os = nullptr;
     CHECK(fhs_client_create(&os) == FHS_OK);           // OS-entropy path
     fhs_client_destroy(os);
+    {   // public-key encryption and its host expansion (pk_host.cpp): a string that crosses a group boundary
+        uint32_t seed[8];
+        std::vector<uint64_t> body(FHS_PK_BODY_WORDS);
+        CHECK(fhs_client_public_key(ck, seed, body.data()) == FHS_OK);
+        const std::string pub = "/tmp/fhs_asan_public.bin";
+        CHECK(fhs_client_save_public_key(ck, pub.c_str()) == FHS_OK);
+        void *pk = nullptr, *pk2 = nullptr, *none = nullptr;
+        fhs_client *no_client = nullptr;
+        CHECK(fhs_public_key_load(pub.c_str(), &pk) == FHS_OK && fhs_public_key_create(seed, body.data(), &pk2) == FHS_OK);
+        CHECK(fhs_client_load(pub.c_str(), &no_client) != FHS_OK && fhs_public_key_load(path.c_str(), &none) != FHS_OK);   // kinds 6 / 1
+        std::remove(pub.c_str());
+        CHECK(fhs_public_key_set_insecure_seed(pk, 5) == FHS_OK);
+        const std::string text(515, 's');
+        size_t mw = 0, bw = 0;
+        fhs_public_str_words(text.size() + 2, &mw, &bw);
+        CHECK(mw == 2 * 2048 && bw == 4 * 517);
+        std::vector<uint32_t> m32(mw), b32(bw);
+        CHECK(fhs_public_encrypt_str(pk, text.data(), text.size(), 2, m32.data(), b32.data()) == FHS_OK);
+        CHECK(fhs_public_encrypt_str(pk, "bad\0x", 5, 0, m32.data(), b32.data()) == FHS_ERR_ARG);
+        std::vector<uint64_t> win((size_t)10 * FHS_CHAR_WORDS);
+        CHECK(fhs_expand_public_str(m32.data(), b32.data(), 517, 507, 10, win.data()) == FHS_OK);   // blocks 2028 .. 2067
+        CHECK(fhs_expand_public_str(m32.data(), b32.data(), 517, 510, 10, win.data()) == FHS_ERR_ARG);
+        char pbuf[16];
+        size_t pn = 0;
+        CHECK(fhs_client_decrypt_str(ck, win.data(), 10, pbuf, &pn) == FHS_OK && pn == 8 && !std::memcmp(pbuf, "ssssssss", 8));
+        fhs_public_key_destroy(pk);
+        fhs_public_key_destroy(pk2);
+    }
     std::remove(path.c_str());
 
     // ---- host transforms of the key ---------------------------------------------------------------------------
@@ -160,6 +188,15 @@ int main() {
         CHECK(fhs_str_compare(c, s.data(), s.size(), s.data(), s.size() - 3, 1, &r) == FHS_OK);   // le: the longer buffer has a non-NUL tail
         CHECK(fhs_trivial_value(c, r, &triv, &val) == FHS_OK && triv == 1 && val == 0);
         CHECK(fhs_flush(c) == FHS_OK);
+    }
+    {   // a public-key upload on the planner: handles only, nothing is read
+        std::vector<uint32_t> m32(2 * 2048, 0), b32(4 * 600, 0);
+        std::vector<fhs_char_t> hs(600);
+        CHECK(fhs_upload_string_public(c, m32.data(), b32.data(), 600, 0, 600, hs.data()) == FHS_OK);
+        CHECK(fhs_upload_string_public(c, m32.data(), b32.data(), 600, 590, 11, hs.data()) == FHS_ERR_ARG);
+        uint64_t c2 = 0;
+        CHECK(fhs_char_sum_c2(c, hs[599], &c2) == FHS_OK && c2 == 1);
+        for (fhs_char_t h : hs) CHECK(fhs_release(c, h) == FHS_OK);
     }
     fhs_stats st;
     // (mostly plaintext strings: counts over repeated flags may pass the budget slightly, tests/test_planner.py)
