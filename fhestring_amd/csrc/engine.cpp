@@ -171,16 +171,59 @@ bool Engine::ensure_staging(size_t n_blocks) {
     return upload_pin_ && (upload_done_ || hipEventCreateWithFlags(&upload_done_, hipEventDisableTiming) == hipSuccess);
 }
 
+// ---- whole-string uploads: what the three variants share -----------------------------------------------------------
+int Engine::undo_upload(Bid *out, size_t count) {
+    for (size_t i = 0; i < count; i++) {
+        if (out[i]) release(out[i]);
+        out[i] = 0;
+    }
+    return -1;
+}
+
+// `n` fresh pool blocks as MAT nodes in out[0..n); their device pointers go to ptrs[0..n) (the pass's pointer table in
+// the pinned buffer).  false: the pool is exhausted (the caller undoes the whole upload).
+bool Engine::new_mat_blocks(size_t n, Bid *out, uint64_t *ptrs) {
+    for (size_t k = 0; k < n; k++) {
+        uint64_t *d = alloc_block();
+        if (!d) return false;
+        out[k] = new_node();
+        nodes_[out[k]].kind = BlockNode::MAT;
+        nodes_[out[k]].dev = d;
+        ptrs[k] = (uint64_t)(uintptr_t)d;
+    }
+    return true;
+}
+
+// the planner's upload: blocks and nodes only, one TR_UPLOAD per block in block order
+int Engine::plan_upload(size_t count, Bid *out) {
+    for (size_t i = 0; i < count; i++) {
+        uint64_t tok = 0;
+        (void)new_mat_blocks(1, out + i, &tok);
+        if (trace_plan) { trace_.push_back(TR_UPLOAD); trace_.push_back(tok); }
+    }
+    return 0;
+}
+
+// One pass through the pinned buffer.  begin: the buffer holds `rows` full rows (0: its minimum size, 533 k words) and
+// the previous copy has left it.  send: the pass's `n` blocks are allocated, their pointers written at word `ptr_at`,
+// `words` words copied to the device mirror and the event behind the copy recorded.
+bool Engine::begin_pass(size_t rows) {
+    if (!ensure_staging(std::max<size_t>(rows, 1))) return false;
+    (void)hipEventSynchronize(upload_done_);         // (no-op before the first copy)
+    return true;
+}
+bool Engine::send_pass(size_t n, Bid *out, size_t ptr_at, size_t words) {
+    if (!new_mat_blocks(n, out, upload_pin_ + ptr_at)) return false;
+    if (hipMemcpyAsync(upload_dev_, upload_pin_, words * 8, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) return false;
+    (void)hipEventRecord(upload_done_, ctx.stream);
+    return true;
+}
+
 int Engine::from_host_many(const uint64_t *cts, size_t count, Bid *out) {
     for (size_t i = 0; i < count; i++) out[i] = 0;
-    auto undo = [&](size_t n) {
-        for (size_t i = 0; i < n; i++) release(out[i]);
-        for (size_t i = 0; i < count; i++) out[i] = 0;
-        return -1;
-    };
     auto one_by_one = [&](size_t from) {
         for (size_t i = from; i < count; i++)
-            if (!(out[i] = from_host(cts + i * BIG_CT))) return undo(i);
+            if (!(out[i] = from_host(cts + i * BIG_CT))) return undo_upload(out, count);
         return 0;
     };
     if (planner || count < 4) return one_by_one(0);
@@ -188,11 +231,9 @@ int Engine::from_host_many(const uint64_t *cts, size_t count, Bid *out) {
     // staging: [count x 2049 words][count destination pointers], pinned on the host and mirrored on the device: one copy,
     // one scatter launch (pool blocks are not neighbours once the free list has been through a few operations)
     constexpr size_t MAX_BATCH = 2048;               // 33.6 MB per pass
-    for (size_t done = 0; done < count;) {
-        const size_t n = std::min(MAX_BATCH, count - done);
-        const size_t words = n * BIG_CT + n;
-        if (!ensure_staging(n)) return one_by_one(done);             // no staging memory: block by block
-        (void)hipEventSynchronize(upload_done_);     // the previous copy has left the pinned buffer (no-op before the first)
+    for (size_t done = 0, n; done < count; done += n) {
+        n = std::min(MAX_BATCH, count - done);
+        if (!begin_pass(n)) return one_by_one(done);                 // no staging memory: block by block
         {
             // pageable -> pinned: one thread copies ~10 GB/s, which for the 537 MB of two 4097-character strings is as long
             // as their (threaded) client encryption; large passes are split over a few host threads
@@ -213,20 +254,9 @@ int Engine::from_host_many(const uint64_t *cts, size_t count, Bid *out) {
                 for (auto &x : th) x.join();
             }
         }
-        for (size_t k = 0; k < n; k++) {
-            uint64_t *d = alloc_block();
-            if (!d) return undo(done + k);
-            Bid id = new_node();
-            nodes_[id].kind = BlockNode::MAT;
-            nodes_[id].dev = d;
-            out[done + k] = id;
-            upload_pin_[n * BIG_CT + k] = (uint64_t)(uintptr_t)d;
-        }
-        if (hipMemcpyAsync(upload_dev_, upload_pin_, words * 8, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) return undo(done + n);
-        (void)hipEventRecord(upload_done_, ctx.stream);
-        if (launch_scatter_blocks(upload_dev_, reinterpret_cast<uint64_t *const *>(upload_dev_ + n * BIG_CT), (int)n, ctx.stream) != hipSuccess)
-            return undo(done + n);
-        done += n;
+        if (!send_pass(n, out + done, n * BIG_CT, n * BIG_CT + n) ||
+            launch_scatter_blocks(upload_dev_, reinterpret_cast<uint64_t *const *>(upload_dev_ + n * BIG_CT), (int)n, ctx.stream) != hipSuccess)
+            return undo_upload(out, count);
     }
     return 0;
 }
@@ -234,101 +264,45 @@ int Engine::from_host_many(const uint64_t *cts, size_t count, Bid *out) {
 int Engine::from_compressed_many(const uint32_t seed[8], const uint64_t *bodies, size_t count, uint64_t first_block,
                                  Bid *out) {
     for (size_t i = 0; i < count; i++) out[i] = 0;
-    auto undo = [&](size_t n) {
-        for (size_t i = 0; i < n; i++) release(out[i]);
-        for (size_t i = 0; i < count; i++) out[i] = 0;
-        return -1;
-    };
-    auto add = [&](size_t i, uint64_t *d) {
-        Bid id = new_node();
-        nodes_[id].kind = BlockNode::MAT;
-        nodes_[id].dev = d;
-        out[i] = id;
-    };
-    if (planner) {
-        for (size_t i = 0; i < count; i++) {
-            uint64_t *d = alloc_block();
-            add(i, d);
-            if (trace_plan) { trace_.push_back(TR_UPLOAD); trace_.push_back((uint64_t)(uintptr_t)d); }
-        }
-        return 0;
-    }
+    if (planner) return plan_upload(count, out);
     (void)hipSetDevice(ctx.device);
     SeedKey key;
     for (int i = 0; i < 8; i++) key.w[i] = seed[i];
-    // staging: [n bodies][n destination pointers] (16 B per block) in the pinned buffer of from_host_many, which holds at
-    // least 260 full rows (533 k words): 4096 blocks per pass
+    // staging: [n bodies][n destination pointers] (16 B per block) in the pinned buffer of from_host_many: 4096 blocks
+    // per pass
     constexpr size_t MAX_BATCH = 4096;
-    for (size_t done = 0; done < count;) {
-        const size_t n = std::min(MAX_BATCH, count - done);
-        if (!ensure_staging(1)) return undo(done);
-        (void)hipEventSynchronize(upload_done_);     // the previous copy has left the pinned buffer
+    for (size_t done = 0, n; done < count; done += n) {
+        n = std::min(MAX_BATCH, count - done);
+        if (!begin_pass(0)) return undo_upload(out, count);
         std::memcpy(upload_pin_, bodies + done, n * 8);
-        for (size_t k = 0; k < n; k++) {
-            uint64_t *d = alloc_block();
-            if (!d) return undo(done + k);
-            add(done + k, d);
-            upload_pin_[n + k] = (uint64_t)(uintptr_t)d;
-        }
-        if (hipMemcpyAsync(upload_dev_, upload_pin_, 2 * n * 8, hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
-            return undo(done + n);
-        (void)hipEventRecord(upload_done_, ctx.stream);
-        if (launch_expand_seeded_blocks(key, first_block + done, upload_dev_, (int)n, ctx.stream) != hipSuccess)
-            return undo(done + n);
-        done += n;
+        if (!send_pass(n, out + done, n, 2 * n) ||
+            launch_expand_seeded_blocks(key, first_block + done, upload_dev_, (int)n, ctx.stream) != hipSuccess)
+            return undo_upload(out, count);
     }
     return 0;
 }
 
 int Engine::from_public_many(const uint32_t *mask32, const uint32_t *body32, size_t count, uint64_t first_block, Bid *out) {
     for (size_t i = 0; i < count; i++) out[i] = 0;
-    auto undo = [&](size_t n) {
-        for (size_t i = 0; i < n; i++) release(out[i]);
-        for (size_t i = 0; i < count; i++) out[i] = 0;
-        return -1;
-    };
-    auto add = [&](size_t i, uint64_t *d) {
-        Bid id = new_node();
-        nodes_[id].kind = BlockNode::MAT;
-        nodes_[id].dev = d;
-        out[i] = id;
-    };
-    if (planner) {
-        for (size_t i = 0; i < count; i++) {
-            uint64_t *d = alloc_block();
-            add(i, d);
-            if (trace_plan) { trace_.push_back(TR_UPLOAD); trace_.push_back((uint64_t)(uintptr_t)d); }
-        }
-        return 0;
-    }
+    if (planner) return plan_upload(count, out);
     (void)hipSetDevice(ctx.device);
-    // staging, in the pinned buffer of from_host_many (at least 533 k words): [n destination pointers][n u32 bodies]
-    // [u32 masks of the groups the pass touches, 2048 each] -- at most three groups for 4096 blocks
+    // staging, in the pinned buffer of from_host_many: [n destination pointers][n u32 bodies][u32 masks of the groups
+    // the pass touches, 2048 each] -- at most three groups for 4096 blocks
     constexpr size_t MAX_BATCH = 4096;
-    for (size_t done = 0; done < count;) {
-        const size_t n = std::min(MAX_BATCH, count - done);
+    for (size_t done = 0, n; done < count; done += n) {
+        n = std::min(MAX_BATCH, count - done);
         const uint64_t t0 = first_block + done;
         const size_t g0 = (size_t)(t0 / FHS_PK_GROUP), groups = (size_t)((t0 + n - 1) / FHS_PK_GROUP) - g0 + 1;
         const size_t body_at = n, mask_at = n + (n + 1) / 2, words = mask_at + groups * (BIG_N / 2);
-        if (!ensure_staging(1)) return undo(done);
-        (void)hipEventSynchronize(upload_done_);     // the previous copy has left the pinned buffer
-        for (size_t k = 0; k < n; k++) {
-            uint64_t *d = alloc_block();
-            if (!d) return undo(done + k);
-            add(done + k, d);
-            upload_pin_[k] = (uint64_t)(uintptr_t)d;
-        }
+        if (!begin_pass(0)) return undo_upload(out, count);
         std::memcpy(upload_pin_ + body_at, body32 + t0, n * 4);
         std::memcpy(upload_pin_ + mask_at, mask32 + g0 * BIG_N, groups * BIG_N * 4);
-        if (hipMemcpyAsync(upload_dev_, upload_pin_, words * 8, hipMemcpyHostToDevice, ctx.stream) != hipSuccess)
-            return undo(done + n);
-        (void)hipEventRecord(upload_done_, ctx.stream);
-        if (launch_expand_public_blocks(reinterpret_cast<const uint32_t *>(upload_dev_ + mask_at),
+        if (!send_pass(n, out + done, 0, words) ||
+            launch_expand_public_blocks(reinterpret_cast<const uint32_t *>(upload_dev_ + mask_at),
                                         reinterpret_cast<const uint32_t *>(upload_dev_ + body_at),
                                         reinterpret_cast<uint64_t *const *>(upload_dev_), (uint32_t)(t0 % FHS_PK_GROUP), (int)n,
                                         ctx.stream) != hipSuccess)
-            return undo(done + n);
-        done += n;
+            return undo_upload(out, count);
     }
     return 0;
 }
@@ -540,7 +514,7 @@ Bid Engine::pbs(Bid x, int lut) {
 }
 
 // ------------------------------------------------------------------------------------------
-// flush: plan every level on the host, upload the plan once, enqueue all launches
+// flush: plan the pending levels one by one and enqueue each as soon as it is planned
 // ------------------------------------------------------------------------------------------
 int Engine::flush() {
     if (auto_flush_rc_) {                                     // an automatic partial flush failed while the DAG was recorded
@@ -550,10 +524,7 @@ int Engine::flush() {
     }
     while (!sched_.empty())                                   // drain the scheduled ticks of submitted jobs first
         if (int rc = pump(1)) return rc;
-    if (level_parallel && ctx.dist.active()) {                // world 1 too: same stream-ordered path
-        if (!ctx.dist.active()) return ctx.fail(-3, "level-parallel flush without a transport (fhs_dist_init)");
-        return plan_job(true);
-    }
+    if (level_parallel && ctx.dist.active()) return plan_job(true);   // world 1 too: same stream-ordered path
     if (dist_world > 1 && !pending_.empty())
         return ctx.fail(-3, "distributed context: pending PBS must be run with fhs_flush_plan/level_exec/level_commit");
     manual_jobs_ = false;                                     // every scheduled tick is in the stream: automatic partial flushes may resume
@@ -567,12 +538,283 @@ int Engine::flush() {
         return 0;
     }
     if (!plan_capture) return plan_job(true);                 // level by level: planning overlaps execution
-    int rc = plan_flush();                                    // capture mode: the all-at-once plan keeps the records
+    int rc = plan_flush();                                    // capture mode: unshared, whole levels, in level order
     if (rc) return rc;
-    for (size_t k = 0; k < plan_.levels.size(); k++)
-        if ((rc = exec_level(k, 0, plan_.levels[k].count, nullptr))) return rc;
-    plan_.levels.clear();
+    for (size_t k = 0; k < planned_.size(); k++)
+        if ((rc = exec_level(k, 0, planned_[k].descs.size(), nullptr))) return rc;
+    planned_.clear();
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// the level builder: pending bootstraps -> levels -> rows (plan_job and plan_flush)
+// ------------------------------------------------------------------------------------------
+void Engine::reset_depth1() {
+    n_depth1_ = 0;
+    n_depth1_solo_ = 0;
+    depth1_keys_.clear();
+}
+
+// pending_ -> the live pending bootstraps by level; first_level_only: depth 1 only (at most peel_limit_ rotations), the
+// other pending nodes stay pending, one level shallower than before
+Engine::LevelMap Engine::collect_levels(bool first_level_only) {
+    LevelMap by_level;
+    reset_depth1();
+    if (!first_level_only) {
+        for (const Pend &p : pending_)
+            if (nodes_[p.id].kind == BlockNode::PBS && nodes_[p.id].gen == p.gen) by_level[nodes_[p.id].level].push_back(p.id);
+        pending_.clear();
+        return by_level;
+    }
+    std::vector<Pend> rest;
+    const size_t limit = peel_limit_ ? peel_limit_ : ~(size_t)0;     // in ROTATIONS: rows sharing a taken row's key ride along
+    size_t left_ready = 0, taken_rot = 0;
+    std::unordered_map<uint64_t, char> taken_keys;
+    for (const Pend &p : pending_) {
+        BlockNode &n = nodes_[p.id];
+        if (n.kind != BlockNode::PBS || n.gen != p.gen) continue;
+        bool take = false;
+        if (n.level <= 1) {
+            if (n.nk && taken_keys.count(n.nk)) take = true;
+            else if (taken_rot < limit) {
+                take = true;
+                taken_rot++;
+                if (n.nk) taken_keys[n.nk] = 1;
+            }
+        }
+        if (take) by_level[1].push_back(p.id);
+        else {
+            if (n.level <= 1) { left_ready++; depth1_add(n); }
+            rest.push_back(p);
+        }
+    }
+    // every ready row taken: the rest moves one level up.  A partial peel (whole rounds only) leaves the levels alone:
+    // a stale level is only ever too HIGH, which keeps the order valid
+    if (left_ready == 0) {
+        for (const Pend &p : rest)
+            if (--nodes_[p.id].level == 1) { n_depth1_++; depth1_add(nodes_[p.id]); }
+    } else {
+        n_depth1_ = left_ready;
+    }
+    peel_limit_ = 0;
+    pending_.swap(rest);
+    return by_level;
+}
+
+// ---- rotation sharing ----------------------------------------------------------------------------------------------
+// Rows of this level with the same look-up table on the same linear combination up to its trivial CONSTANT
+// (e.g. the nibble of a character tested against the different nibbles of a clear pattern: is0(x - c)) share ONE
+// keyswitch + blind rotation: adding c * Delta to a ciphertext rotates the accumulator by X^(128 c) exactly, so the
+// other rows are further sample extractions of the leader's accumulator (extract_shift_kernel) -- the same
+// ciphertext a bootstrap of their own would give, up to decomposition ties (the CPU oracle restates it:
+// orc_pbs_shifted).  The level is reordered: rotation rows first (their number is returned), followers behind.
+size_t Engine::share_level(LevelMap &by_level, LevelMap::iterator lvit, bool first_level_only, std::vector<ShareRow> &followers) {
+    std::vector<Bid> &lv = lvit->second;
+    followers.clear();
+    if (!(share_rotations && mode == 1 && lv.size() > 1 && !(level_parallel && ctx.dist.active()))) return lv.size();
+    std::unordered_map<uint64_t, std::vector<uint32_t>> seen;     // hash of (lut, terms) -> leader positions
+    std::vector<Bid> rot, fol;
+    std::vector<ShareRow> fmeta;
+    std::vector<uint32_t> used;                                    // per rotation row: bit t = an extraction at shift t exists
+    auto key_terms = [&](const BlockNode &src, Bid self, std::vector<std::pair<Bid, int64_t>> &tt, int &konst) {
+        tt.clear();
+        if (src.kind == BlockNode::LIN) {
+            for (const Term &t : src.terms) tt.emplace_back(t.blk, t.coef);
+            std::sort(tt.begin(), tt.end());
+            konst = src.konst;
+        } else {
+            tt.emplace_back(self, 1);
+            konst = 0;
+        }
+    };
+    std::vector<std::pair<Bid, int64_t>> ta, tb;
+    for (Bid b : lv) {
+        const BlockNode &n = nodes_[b];
+        int ka = 0;
+        key_terms(nodes_[n.src], n.src, ta, ka);
+        uint64_t h = 0x9E3779B97F4A7C15ull * (uint64_t)(n.lut + 1);
+        for (auto &t : ta) {
+            h ^= ((uint64_t)t.first << 20) + (uint64_t)t.second * 0xBF58476D1CE4E5B9ull;
+            h = (h ^ (h >> 29)) * 0x94D049BB133111EBull;
+        }
+        std::vector<uint32_t> &cand = seen[h];
+        bool shared = false;
+        for (uint32_t pos : cand) {
+            const BlockNode &ln = nodes_[rot[pos]];
+            int kb = 0;
+            key_terms(nodes_[ln.src], ln.src, tb, kb);
+            if (ln.lut != n.lut || ta != tb) continue;
+            // a constant difference of 16 is the SAME coefficient of the accumulator, negated (X^2048 = -1): its
+            // error is exactly minus the other's (rho = -1; the full-correlation charge of lin_c2 covers it, but a
+            // sum a - b of the two would DOUBLE the error for no information) -- no two members of a group may be
+            // 16 apart (such a row joins another group of the same key, or starts one)
+            const uint32_t t = (uint32_t)(((ka - kb) % 32 + 32) % 32);
+            if (used[pos] & (1u << ((t + 16) & 31))) continue;
+            used[pos] |= 1u << t;
+            fol.push_back(b);
+            fmeta.push_back({pos, 128 * t, nullptr});
+            shared = true;
+            break;
+        }
+        if (!shared) {
+            cand.push_back((uint32_t)rot.size());
+            rot.push_back(b);
+            used.push_back(1u);                                    // the leader itself: shift 0
+        }
+    }
+    if (!fol.empty()) unshare_over_budget(by_level, lvit, first_level_only, rot, fol, fmeta);
+    if (fol.empty()) return lv.size();
+    const size_t R = rot.size();
+    lv.swap(rot);
+    lv.insert(lv.end(), fol.begin(), fol.end());
+    followers.swap(fmeta);
+    return R;
+}
+
+// Sharing must not push a CONSUMER over the noise budget: extractions of one rotation are correlated (lin_c2 charges
+// them as fully correlated), so a later bootstrap whose input sums several members of one group with the same sign is
+// charged cross terms the string layer did not see when it built that sum.  Every pending consumer is known here
+// (deeper levels of this plan; in a partial peel the nodes still pending) -- consumers recorded later see the groups
+// through sum_c2().  A follower whose group would take a consumer from within the budget to beyond it gets a rotation
+// of its own (appended to `rot`: positions stay valid).
+void Engine::unshare_over_budget(const LevelMap &by_level, LevelMap::const_iterator lvit, bool first_level_only,
+                                 std::vector<Bid> &rot, std::vector<Bid> &fol, std::vector<ShareRow> &fmeta) {
+    std::unordered_map<Bid, uint32_t> member;              // node -> leader position (leaders with followers too)
+    for (size_t i = 0; i < fol.size(); i++) {
+        member[fol[i]] = fmeta[i].lead_row;
+        member[rot[fmeta[i].lead_row]] = fmeta[i].lead_row;
+    }
+    std::vector<char> unshare(fol.size(), 0);
+    bool any_unshare = false;
+    auto check = [&](Bid consumer) {
+        const BlockNode &cn = nodes_[consumer];
+        if (cn.kind != BlockNode::PBS) return;
+        const BlockNode &src = nodes_[cn.src];
+        if (src.kind != BlockNode::LIN || src.terms.size() < 2) return;
+        struct G { uint32_t lead; int64_t sum_abs, sum_c2; };
+        G g[8];
+        int ng = 0;
+        bool multi = false;
+        for (const Term &t : src.terms) {
+            auto it = member.find(t.blk);
+            if (it == member.end()) continue;
+            int k = 0;
+            while (k < ng && g[k].lead != it->second) k++;
+            if (k == ng) { if (ng == 8) continue; g[ng++] = G{it->second, 0, 0}; }
+            else multi = true;
+            g[k].sum_abs += t.coef < 0 ? -t.coef : t.coef;
+            g[k].sum_c2 += t.coef * t.coef;
+        }
+        if (!multi) return;
+        int64_t plain = lin_c2(src.terms), extra = 0;      // (members are still pending: counted as independent)
+        for (int k = 0; k < ng; k++) extra += g[k].sum_abs * g[k].sum_abs - g[k].sum_c2;   // as lin_c2 will
+        if (plain + extra <= FHS_NOISE_BUDGET_SUM_C2 || extra == 0) return;
+        for (const Term &t : src.terms)                    // the followers among this sum's terms leave their groups
+            for (size_t i = 0; i < fol.size(); i++)
+                if (fol[i] == t.blk && !unshare[i]) { unshare[i] = 1; any_unshare = true; }
+    };
+    for (auto nx = std::next(lvit); nx != by_level.end(); ++nx)
+        for (Bid c : nx->second) check(c);
+    if (first_level_only)
+        for (const Pend &pd : pending_)
+            if (nodes_[pd.id].gen == pd.gen) check(pd.id);
+    if (!any_unshare) return;
+    std::vector<Bid> fol2;
+    std::vector<ShareRow> fmeta2;
+    for (size_t i = 0; i < fol.size(); i++) {
+        if (unshare[i]) rot.push_back(fol[i]);             // a rotation row of its own
+        else { fol2.push_back(fol[i]); fmeta2.push_back(fmeta[i]); }
+    }
+    fol.swap(fol2);
+    fmeta.swap(fmeta2);
+}
+
+// The rows of one level: lv[0..R) are the rotation rows, tl.ext (from share_level) the extractions behind them.  Per row the
+// lincomb descriptor, its terms, the look-up table, the latest tick that produces one of its inputs (row_need) and the
+// noise bookkeeping; then the blocks: row outputs in row order, then per follower its output and its leader's body
+// block if new.  keep_recs: a CaptureRec per row (while capturing), numbered rec_level.
+int Engine::build_rows(const std::vector<Bid> &lv, size_t R, TickLevel &tl, std::vector<uint64_t> &row_need, bool keep_recs,
+                       uint32_t rec_level) {
+    if (!tl.ext.empty()) tl.body.assign(R, nullptr);
+    row_need.assign(R, 0);
+    for (size_t li = 0; li < R; li++) {
+        const Bid b = lv[li];
+        const BlockNode &n = nodes_[b];
+        const BlockNode &s = nodes_[n.src];
+        LinDesc d{};
+        d.first_term = (uint32_t)tl.terms.size();
+        // noise bookkeeping: the variance of the combination entering this bootstrap in units of one bootstrap output's
+        // (uploads counted like outputs; extractions of one shared rotation as fully correlated: lin_c2)
+        int64_t c2 = 0;
+        uint64_t &need = row_need[li];
+        if (s.kind == BlockNode::MAT) {
+            tl.terms.push_back({s.dev, 1});
+            d.n_terms = 1;
+            need = std::max(need, s.ready_tick);
+            c2 = s.var;
+        } else if (s.kind == BlockNode::LIN) {
+            for (const Term &t : s.terms) {
+                const BlockNode &tb = nodes_[t.blk];
+                if (tb.kind != BlockNode::MAT || !tb.dev)
+                    return ctx.fail(-3, "internal: lincomb term not materialised at its level");
+                tl.terms.push_back({tb.dev, t.coef});
+                need = std::max(need, tb.ready_tick);
+            }
+            c2 = lin_c2(s.terms);
+            d.n_terms = (uint32_t)s.terms.size();
+            d.konst_body = (uint64_t)(s.konst & 31) << DELTA_LOG;
+        } else {
+            return ctx.fail(-3, "internal: PBS source is neither MAT nor LIN (node " + std::to_string(b) + " level " +
+                                    std::to_string(n.level) + " lut " + std::to_string(n.lut) + ", source " +
+                                    std::to_string(n.src) + " kind " + std::to_string((int)s.kind) + " level " +
+                                    std::to_string(s.level) + " refs " + std::to_string(s.refs) + ")");
+        }
+        stats.max_input_sum_c2 = std::max<uint64_t>(stats.max_input_sum_c2, (uint64_t)c2);
+        if (c2 > FHS_NOISE_BUDGET_SUM_C2 && std::getenv("FHS_DEBUG_C2")) {
+            std::fprintf(stderr, "c2=%lld lut=%d terms:", (long long)c2, (int)n.lut);
+            for (const Term &t : s.terms) std::fprintf(stderr, " %lld*b%u", (long long)t.coef, t.blk);
+            std::fprintf(stderr, "\n");
+        }
+        tl.descs.push_back(d);
+        tl.lut.push_back(n.lut);
+        if (capture_max_rows && keep_recs)
+            tl.recs.push_back(CaptureRec{rec_level, (uint32_t)li, n.lut, d.n_terms, c2, s.kind == BlockNode::LIN ? s.konst : 0,
+                                         (uint32_t)R});
+        uint64_t *o = alloc_block();
+        if (!o) return ctx.fail(-2, "device block pool exhausted (hipMalloc failed)");
+        tl.out.push_back(o);
+    }
+    for (ShareRow &f : tl.ext) {                         // a follower's own block; its leader also stores the body polynomial
+        f.out = alloc_block();
+        if (!f.out) return ctx.fail(-2, "device block pool exhausted (hipMalloc failed)");
+        if (!tl.body[f.lead_row]) {
+            tl.body[f.lead_row] = alloc_block();
+            if (!tl.body[f.lead_row]) return ctx.fail(-2, "device block pool exhausted (hipMalloc failed)");
+        }
+    }
+    return 0;
+}
+
+// The level's nodes become materialised (rotation rows lv[0..R) -> tl.out, followers -> tl.ext), the members of a shared
+// rotation get its group number, and the inputs are released: later levels may recycle their blocks.  row_tick (the
+// scheduled path): the tick that writes each rotation row; a follower is ready with its leader.
+void Engine::commit_rows(const std::vector<Bid> &lv, const TickLevel &tl, const std::vector<uint64_t> *row_tick) {
+    const size_t R = tl.out.size();
+    std::vector<uint32_t> rot_of(tl.ext.empty() ? 0 : R, 0);
+    for (const ShareRow &f : tl.ext)
+        if (!rot_of[f.lead_row]) rot_of[f.lead_row] = ++rot_counter_ ? rot_counter_ : ++rot_counter_;
+    for (size_t k = 0; k < lv.size(); k++) {
+        BlockNode &n = nodes_[lv[k]];
+        const size_t lead = k < R ? k : tl.ext[k - R].lead_row;
+        const Bid src = n.src;
+        n.kind = BlockNode::MAT;
+        n.dev = k < R ? tl.out[k] : tl.ext[k - R].out;
+        if (!tl.ext.empty()) n.rot = rot_of[lead];
+        n.src = 0;
+        n.level = 0;
+        if (row_tick) n.ready_tick = (*row_tick)[lead];
+        release(src);
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -583,363 +825,118 @@ int Engine::plan_job(bool run_now, bool first_level_only, bool stream_pump) {
     if (!run_now && level_parallel && ctx.dist.active())
         return ctx.fail(-3, "fhs_submit is not available in level-parallel mode");
     if (!planner && !ctx.key_loaded) return ctx.fail(-3, "server key not loaded");
-    std::map<uint32_t, std::vector<Bid>> by_level;
-    if (first_level_only) {
-        // peel depth 1 only: the other pending nodes stay pending, one level shallower than before
-        std::vector<Pend> rest;
-        n_depth1_ = 0;
-        n_depth1_solo_ = 0;
-        depth1_keys_.clear();
-        const size_t limit = peel_limit_ ? peel_limit_ : ~(size_t)0;     // in ROTATIONS: rows sharing a taken row's key ride along
-        size_t left_ready = 0, taken_rot = 0;
-        std::unordered_map<uint64_t, char> taken_keys;
-        for (const Pend &p : pending_) {
-            BlockNode &n = nodes_[p.id];
-            if (n.kind != BlockNode::PBS || n.gen != p.gen) continue;
-            bool take = false;
-            if (n.level <= 1) {
-                if (n.nk && taken_keys.count(n.nk)) take = true;
-                else if (taken_rot < limit) {
-                    take = true;
-                    taken_rot++;
-                    if (n.nk) taken_keys[n.nk] = 1;
-                }
-            }
-            if (take) by_level[1].push_back(p.id);
-            else {
-                if (n.level <= 1) { left_ready++; depth1_add(n); }
-                rest.push_back(p);
-            }
-        }
-        // every ready row taken: the rest moves one level up.  A partial peel (whole rounds only) leaves the levels alone:
-        // a stale level is only ever too HIGH, which keeps the order valid
-        if (left_ready == 0) {
-            for (const Pend &p : rest)
-                if (--nodes_[p.id].level == 1) { n_depth1_++; depth1_add(nodes_[p.id]); }
-        } else {
-            n_depth1_ = left_ready;
-        }
-        peel_limit_ = 0;
-        pending_.swap(rest);
-    } else {
-        for (const Pend &p : pending_)
-            if (nodes_[p.id].kind == BlockNode::PBS && nodes_[p.id].gen == p.gen) by_level[nodes_[p.id].level].push_back(p.id);
-        pending_.clear();
-        n_depth1_ = 0;
-        n_depth1_solo_ = 0;
-        depth1_keys_.clear();
-    }
+    LevelMap by_level = collect_levels(first_level_only);
     uint64_t tick = next_tick_ - 1;                           // the job's first level goes to next_tick_ at the earliest
     const uint64_t job = ++job_counter_;
     std::vector<uint64_t> row_need;                           // per row: latest tick that produces one of its inputs
     for (auto lvit = by_level.begin(); lvit != by_level.end(); ++lvit) {
-        std::vector<Bid> &lv = lvit->second;
-        TickLevel tl;
-        tl.job = job;
-        // ---- rotation sharing ------------------------------------------------------------------------------------
-        // Rows of this level with the same look-up table on the same linear combination up to its trivial CONSTANT
-        // (e.g. the nibble of a character tested against the different nibbles of a clear pattern: is0(x - c)) share ONE
-        // keyswitch + blind rotation: adding c * Delta to a ciphertext rotates the accumulator by X^(128 c) exactly, so the
-        // other rows are further sample extractions of the leader's accumulator (extract_shift_kernel) -- the same
-        // ciphertext a bootstrap of their own would give, up to decomposition ties (the CPU oracle restates it:
-        // orc_pbs_shifted).  The level is reordered: rotation rows first (R of them), followers behind.
-        std::vector<ShareRow> followers;
-        size_t R = lv.size();
-        if (share_rotations && mode == 1 && lv.size() > 1 && !(level_parallel && ctx.dist.active())) {
-            std::unordered_map<uint64_t, std::vector<uint32_t>> seen;     // hash of (lut, terms) -> leader positions
-            std::vector<Bid> rot, fol;
-            std::vector<ShareRow> fmeta;
-            std::vector<uint32_t> used;                                    // per rotation row: bit t = an extraction at shift t exists
-            auto key_terms = [&](const BlockNode &src, Bid self, std::vector<std::pair<Bid, int64_t>> &tt, int &konst) {
-                tt.clear();
-                if (src.kind == BlockNode::LIN) {
-                    for (const Term &t : src.terms) tt.emplace_back(t.blk, t.coef);
-                    std::sort(tt.begin(), tt.end());
-                    konst = src.konst;
-                } else {
-                    tt.emplace_back(self, 1);
-                    konst = 0;
-                }
-            };
-            std::vector<std::pair<Bid, int64_t>> ta, tb;
-            for (Bid b : lv) {
-                const BlockNode &n = nodes_[b];
-                int ka = 0;
-                key_terms(nodes_[n.src], n.src, ta, ka);
-                uint64_t h = 0x9E3779B97F4A7C15ull * (uint64_t)(n.lut + 1);
-                for (auto &t : ta) {
-                    h ^= ((uint64_t)t.first << 20) + (uint64_t)t.second * 0xBF58476D1CE4E5B9ull;
-                    h = (h ^ (h >> 29)) * 0x94D049BB133111EBull;
-                }
-                std::vector<uint32_t> &cand = seen[h];
-                bool shared = false;
-                for (uint32_t pos : cand) {
-                    const BlockNode &ln = nodes_[rot[pos]];
-                    int kb = 0;
-                    key_terms(nodes_[ln.src], ln.src, tb, kb);
-                    if (ln.lut != n.lut || ta != tb) continue;
-                    // a constant difference of 16 is the SAME coefficient of the accumulator, negated (X^2048 = -1): its
-                    // error is exactly minus the other's (rho = -1; the full-correlation charge of lin_c2 covers it, but a
-                    // sum a - b of the two would DOUBLE the error for no information) -- no two members of a group may be
-                    // 16 apart (such a row joins another group of the same key, or starts one)
-                    const uint32_t t = (uint32_t)(((ka - kb) % 32 + 32) % 32);
-                    if (used[pos] & (1u << ((t + 16) & 31))) continue;
-                    used[pos] |= 1u << t;
-                    fol.push_back(b);
-                    fmeta.push_back({pos, 128 * t, nullptr});
-                    shared = true;
-                    break;
-                }
-                if (!shared) {
-                    cand.push_back((uint32_t)rot.size());
-                    rot.push_back(b);
-                    used.push_back(1u);                                    // the leader itself: shift 0
-                }
-            }
-            if (!fol.empty()) {
-                // Sharing must not push a CONSUMER over the noise budget: extractions of one rotation are
-                // correlated (lin_c2 charges them as fully correlated), so a later bootstrap whose input sums several members of one group with the same
-                // sign is charged cross terms the string layer did not see when it built that sum.  Every pending consumer
-                // is known here (deeper levels of this plan; in a partial peel the nodes still pending) -- consumers recorded
-                // later see the groups through sum_c2().  A follower whose group would take a consumer from within the
-                // budget to beyond it gets a rotation of its own.
-                std::unordered_map<Bid, uint32_t> member;              // node -> leader position (leaders with followers too)
-                for (size_t i = 0; i < fol.size(); i++) {
-                    member[fol[i]] = fmeta[i].lead_row;
-                    member[rot[fmeta[i].lead_row]] = fmeta[i].lead_row;
-                }
-                std::vector<char> unshare(fol.size(), 0);
-                bool any_unshare = false;
-                auto check = [&](Bid consumer) {
-                    const BlockNode &cn = nodes_[consumer];
-                    if (cn.kind != BlockNode::PBS) return;
-                    const BlockNode &src = nodes_[cn.src];
-                    if (src.kind != BlockNode::LIN || src.terms.size() < 2) return;
-                    struct G { uint32_t lead; int64_t sum_abs, sum_c2; };
-                    G g[8];
-                    int ng = 0;
-                    bool multi = false;
-                    for (const Term &t : src.terms) {
-                        auto it = member.find(t.blk);
-                        if (it == member.end()) continue;
-                        int k = 0;
-                        while (k < ng && g[k].lead != it->second) k++;
-                        if (k == ng) { if (ng == 8) continue; g[ng++] = G{it->second, 0, 0}; }
-                        else multi = true;
-                        g[k].sum_abs += t.coef < 0 ? -t.coef : t.coef;
-                        g[k].sum_c2 += t.coef * t.coef;
-                    }
-                    if (!multi) return;
-                    int64_t plain = lin_c2(src.terms), extra = 0;      // (members are still pending: counted as independent)
-                    for (int k = 0; k < ng; k++) extra += g[k].sum_abs * g[k].sum_abs - g[k].sum_c2;   // as lin_c2 will
-                    if (plain + extra <= FHS_NOISE_BUDGET_SUM_C2 || extra == 0) return;
-                    for (const Term &t : src.terms)                    // the followers among this sum's terms leave their groups
-                        for (size_t i = 0; i < fol.size(); i++)
-                            if (fol[i] == t.blk && !unshare[i]) { unshare[i] = 1; any_unshare = true; }
-                };
-                for (auto nx = std::next(lvit); nx != by_level.end(); ++nx)
-                    for (Bid c : nx->second) check(c);
-                if (first_level_only)
-                    for (const Pend &pd : pending_)
-                        if (nodes_[pd.id].gen == pd.gen) check(pd.id);
-                if (any_unshare) {
-                    std::vector<Bid> fol2;
-                    std::vector<ShareRow> fmeta2;
-                    for (size_t i = 0; i < fol.size(); i++) {
-                        if (unshare[i]) { rot.push_back(fol[i]); used.push_back(1u); }   // a rotation row of its own (appended: positions stay valid)
-                        else { fol2.push_back(fol[i]); fmeta2.push_back(fmeta[i]); }
-                    }
-                    fol.swap(fol2);
-                    fmeta.swap(fmeta2);
-                }
-            }
-            if (!fol.empty()) {
-                R = rot.size();
-                lv.swap(rot);
-                lv.insert(lv.end(), fol.begin(), fol.end());
-                followers.swap(fmeta);
-                tl.body.assign(R, nullptr);
-            }
-        }
-        row_need.assign(R, 0);
-        size_t row_i = 0;
-        for (size_t li = 0; li < R; li++) {
-            const Bid b = lv[li];
-            BlockNode &n = nodes_[b];
-            const BlockNode &s = nodes_[n.src];
-            LinDesc d{};
-            d.first_term = (uint32_t)tl.terms.size();
-            int64_t c2 = 0;
-            uint64_t &need = row_need[row_i++];
-            if (s.kind == BlockNode::MAT) {
-                tl.terms.push_back({s.dev, 1});
-                d.n_terms = 1;
-                need = std::max(need, s.ready_tick);
-                c2 = s.var;
-            } else if (s.kind == BlockNode::LIN) {
-                for (const Term &t : s.terms) {
-                    const BlockNode &tb = nodes_[t.blk];
-                    if (tb.kind != BlockNode::MAT || !tb.dev)
-                        return ctx.fail(-3, "internal: lincomb term not materialised at its level");
-                    tl.terms.push_back({tb.dev, t.coef});
-                    need = std::max(need, tb.ready_tick);
-                }
-                c2 = lin_c2(s.terms);                        // extractions of one shared rotation count as fully correlated
-                d.n_terms = (uint32_t)s.terms.size();
-                d.konst_body = (uint64_t)(s.konst & 31) << DELTA_LOG;
-            } else {
-                return ctx.fail(-3, "internal: PBS source is neither MAT nor LIN (node " + std::to_string(b) + " level " +
-                                        std::to_string(n.level) + " lut " + std::to_string(n.lut) + ", source " +
-                                        std::to_string(n.src) + " kind " + std::to_string((int)s.kind) + " level " +
-                                        std::to_string(s.level) + " refs " + std::to_string(s.refs) + ")");
-            }
-            stats.max_input_sum_c2 = std::max<uint64_t>(stats.max_input_sum_c2, (uint64_t)c2);
-            if (c2 > 64 && std::getenv("FHS_DEBUG_C2")) {
-                std::fprintf(stderr, "c2=%lld lut=%d terms:", (long long)c2, (int)n.lut);
-                for (const Term &t : s.terms) std::fprintf(stderr, " %lld*b%u", (long long)t.coef, t.blk);
-                std::fprintf(stderr, "\n");
-            }
-            tl.descs.push_back(d);
-            tl.lut.push_back(n.lut);
-            if (capture_max_rows && capture_live)             // level: filled in when the row runs (run_tick)
-                tl.recs.push_back(CaptureRec{0, (uint32_t)li, n.lut, d.n_terms, c2, s.kind == BlockNode::LIN ? s.konst : 0,
-                                             (uint32_t)R});
-            uint64_t *o = alloc_block();
-            if (!o) return ctx.fail(-2, "device block pool exhausted (hipMalloc failed)");
-            tl.out.push_back(o);
-        }
-        for (ShareRow &f : followers) {                      // a follower's own block; its leader also stores the body polynomial
-            f.out = alloc_block();
-            if (!f.out) return ctx.fail(-2, "device block pool exhausted (hipMalloc failed)");
-            if (!tl.body[f.lead_row]) {
-                tl.body[f.lead_row] = alloc_block();
-                if (!tl.body[f.lead_row]) return ctx.fail(-2, "device block pool exhausted (hipMalloc failed)");
-            }
-        }
-        tl.ext = followers;
+        std::vector<TickLevel> one(1);
+        one[0].job = job;
+        const size_t R = share_level(by_level, lvit, first_level_only, one[0].ext);
+        if (int rc = build_rows(lvit->second, R, one[0], row_need, capture_live, 0)) return rc;   // (level: run_tick)
         if (run_now) {
             // nothing is scheduled (flush drained it): enqueue this level right away, then plan the next one meanwhile
-            std::vector<TickLevel> one;
-            one.push_back(std::move(tl));
             if (int rc = run_tick(one, level_parallel && ctx.dist.active())) return rc;
-            std::vector<uint32_t> rot_of(followers.empty() ? 0 : R, 0);
-            for (const ShareRow &f : followers)
-                if (!rot_of[f.lead_row]) rot_of[f.lead_row] = ++rot_counter_ ? rot_counter_ : ++rot_counter_;
-            for (size_t k = 0; k < lv.size(); k++) {
-                BlockNode &n = nodes_[lv[k]];
-                const Bid src = n.src;
-                n.kind = BlockNode::MAT;
-                n.dev = k < R ? one[0].out[k] : followers[k - R].out;
-                if (!followers.empty()) n.rot = rot_of[k < R ? k : followers[k - R].lead_row];
-                n.src = 0;
-                n.level = 0;
-                release(src);                                // immediate recycling is safe: stream order
-            }
+            commit_rows(lvit->second, one[0], nullptr);       // immediate recycling is safe: stream order
             continue;
         }
-        // ---- list scheduling at ROW granularity ------------------------------------------------------------------
-        // A row runs at the first tick after the one that produces its last input (and not before the tick after the
-        // previous level's).  Rows of one level may therefore sit on different ticks: the rows that consume a result
-        // which was itself sent one tick later (round alignment below, or a dependent job) follow it, the others stay.
-        const uint64_t t0 = tick + 1;
-        uint64_t base = ~0ull, last = 0;
-        for (size_t k = 0; k < R; k++) {
-            row_need[k] = std::max(t0, row_need[k] + 1);      // now: the row's own tick
-            base = std::min(base, row_need[k]);
-            last = std::max(last, row_need[k]);
-        }
-        tick = base;
-        // round alignment: with `cur` rows already scheduled for the base tick, keep only as many of this level's on-time
-        // rows as fill whole rounds of the persistent kernel; the excess (less than one round) runs one tick later with
-        // whatever is scheduled there -- only ITS consumers follow it, the rest of the next level does not wait
-        size_t n_base = 0;
-        for (size_t k = 0; k < R; k++) n_base += row_need[k] == base;
-        if (balance_slots) {
-            size_t cur = 0;
-            auto it = sched_.find(base);
-            if (it != sched_.end())
-                for (const TickLevel &l : it->second) cur += l.descs.size();
-            const size_t total = cur + n_base, rem = total % balance_slots;
-            const size_t rounds = (total + balance_slots - 1) / balance_slots;
-            size_t defer = 0;
-            // only when the last round would be less than ~2/3 full overall: a group that already fills 95 % of its rounds
-            // is left alone (the split costs its consumers one tick)
-            // (jobs scheduled by hand share their ticks with jobs still to come: there only a level that is at least one
-            // round wide by itself is split; a streaming flush knows the whole population of the tick)
-            if ((stream_pump ? total : n_base) >= balance_slots && rem && rem < n_base &&
-                total * 100 < rounds * balance_slots * 95)
-                defer = rem;
-            // a sliver in front of a wide level (what an automatic partial flush leaves of a level: 16 388 = 2 x 8192 + 4)
-            // would pay one whole bootstrap alone: it joins the next tick, where the rows of the next level that do not
-            // consume it run anyway
-            auto nx = std::next(lvit);
-            if (stream_pump && !defer && total * 8 < balance_slots && nx != by_level.end() &&
-                nx->second.size() >= 2 * balance_slots)
-                defer = n_base;
-            for (size_t k = R; k-- > 0 && defer;)
-                if (row_need[k] == base) { row_need[k] = base + 1; defer--; }
-            for (size_t k = 0; k < R; k++) last = std::max(last, row_need[k]);
-        }
-        last_sched_tick_ = std::max(last_sched_tick_, last);  // before the releases below
-        std::vector<uint32_t> rot_of(tl.ext.empty() ? 0 : R, 0);
-        for (const ShareRow &f : tl.ext)
-            if (!rot_of[f.lead_row]) rot_of[f.lead_row] = ++rot_counter_ ? rot_counter_ : ++rot_counter_;
-        for (size_t k = 0; k < lv.size(); k++) {
-            BlockNode &n = nodes_[lv[k]];
-            const Bid src = n.src;
-            n.kind = BlockNode::MAT;
-            n.dev = k < R ? tl.out[k] : tl.ext[k - R].out;
-            if (!tl.ext.empty()) n.rot = rot_of[k < R ? k : tl.ext[k - R].lead_row];
-            n.src = 0;
-            n.level = 0;
-            n.ready_tick = k < R ? row_need[k] : row_need[tl.ext[k - R].lead_row];   // a follower is ready with its leader
-            release(src);
-        }
-        // hand the rows to their ticks (ascending): one TickLevel per job and tick, rows of several levels merged
-        std::vector<uint64_t> ticks(row_need.begin(), row_need.begin() + R);
-        std::sort(ticks.begin(), ticks.end());
-        ticks.erase(std::unique(ticks.begin(), ticks.end()), ticks.end());
-        for (uint64_t tk : ticks) {
-            std::vector<TickLevel> &slot = sched_[tk];
-            TickLevel *dst = nullptr;
-            for (TickLevel &l : slot)
-                if (l.job == job) dst = &l;
-            if (!dst) {
-                slot.emplace_back();
-                dst = &slot.back();
-                dst->job = job;
-            }
-            if (ticks.size() == 1 && dst->descs.empty()) {    // the common case: the whole level on one tick
-                tl.job = job;
-                *dst = std::move(tl);
-                break;
-            }
-            std::vector<uint32_t> moved(tl.ext.empty() ? 0 : R, 0);   // leader row -> its position in dst
-            for (size_t k = 0; k < R; k++) {
-                if (row_need[k] != tk) continue;
-                LinDesc d = tl.descs[k];
-                const uint32_t f = d.first_term;
-                d.first_term = (uint32_t)dst->terms.size();
-                dst->terms.insert(dst->terms.end(), tl.terms.begin() + f, tl.terms.begin() + f + d.n_terms);
-                if (!tl.ext.empty()) {
-                    moved[k] = (uint32_t)dst->descs.size();
-                    dst->body.resize(dst->descs.size(), nullptr);
-                    dst->body.push_back(tl.body[k]);
-                }
-                dst->descs.push_back(d);
-                dst->lut.push_back(tl.lut[k]);
-                dst->out.push_back(tl.out[k]);
-                if (tl.recs.size() == tl.descs.size()) dst->recs.push_back(tl.recs[k]);
-            }
-            for (const ShareRow &f : tl.ext)                       // followers travel with their leader's tick
-                if (row_need[f.lead_row] == tk) dst->ext.push_back({moved[f.lead_row], f.K, f.out});
-        }
-        // streaming flush: every tick up to `base` is complete now (later levels cannot reach back) -- enqueue them while
-        // the host plans the next level
-        if (stream_pump)
-            while (!sched_.empty() && sched_.begin()->first <= base)
-                if (int rc = pump(1)) return rc;
+        auto nx = std::next(lvit);
+        const size_t next_width = nx == by_level.end() ? 0 : nx->second.size();
+        if (int rc = schedule_level(one[0], lvit->second, row_need, tick, stream_pump, next_width)) return rc;
     }
+    return 0;
+}
+
+// ---- list scheduling at ROW granularity ----------------------------------------------------------------------------
+// A row runs at the first tick after the one that produces its last input (and not before the tick after the
+// previous level's, `tick`).  Rows of one level may therefore sit on different ticks: the rows that consume a result
+// which was itself sent one tick later (round alignment below, or a dependent job) follow it, the others stay.
+// row_need: in, per row the latest tick that produces one of its inputs; out, the row's own tick.
+int Engine::schedule_level(TickLevel &tl, const std::vector<Bid> &lv, std::vector<uint64_t> &row_need, uint64_t &tick,
+                           bool stream_pump, size_t next_width) {
+    const size_t R = tl.descs.size();
+    const uint64_t job = tl.job;
+    const uint64_t t0 = tick + 1;
+    uint64_t base = ~0ull, last = 0;
+    for (size_t k = 0; k < R; k++) {
+        row_need[k] = std::max(t0, row_need[k] + 1);      // now: the row's own tick
+        base = std::min(base, row_need[k]);
+        last = std::max(last, row_need[k]);
+    }
+    tick = base;
+    // round alignment: with `cur` rows already scheduled for the base tick, keep only as many of this level's on-time
+    // rows as fill whole rounds of the persistent kernel; the excess (less than one round) runs one tick later with
+    // whatever is scheduled there -- only ITS consumers follow it, the rest of the next level does not wait
+    size_t n_base = 0;
+    for (size_t k = 0; k < R; k++) n_base += row_need[k] == base;
+    if (balance_slots) {
+        size_t cur = 0;
+        auto it = sched_.find(base);
+        if (it != sched_.end())
+            for (const TickLevel &l : it->second) cur += l.descs.size();
+        const size_t total = cur + n_base, rem = total % balance_slots;
+        const size_t rounds = (total + balance_slots - 1) / balance_slots;
+        size_t defer = 0;
+        // only when the last round would be less than ~2/3 full overall: a group that already fills 95 % of its rounds
+        // is left alone (the split costs its consumers one tick)
+        // (jobs scheduled by hand share their ticks with jobs still to come: there only a level that is at least one
+        // round wide by itself is split; a streaming flush knows the whole population of the tick)
+        if ((stream_pump ? total : n_base) >= balance_slots && rem && rem < n_base &&
+            total * 100 < rounds * balance_slots * 95)
+            defer = rem;
+        // a sliver in front of a wide level (what an automatic partial flush leaves of a level: 16 388 = 2 x 8192 + 4)
+        // would pay one whole bootstrap alone: it joins the next tick, where the rows of the next level that do not
+        // consume it run anyway
+        if (stream_pump && !defer && total * 8 < balance_slots && next_width >= 2 * balance_slots) defer = n_base;
+        for (size_t k = R; k-- > 0 && defer;)
+            if (row_need[k] == base) { row_need[k] = base + 1; defer--; }
+        for (size_t k = 0; k < R; k++) last = std::max(last, row_need[k]);
+    }
+    last_sched_tick_ = std::max(last_sched_tick_, last);  // before the releases of commit_rows
+    commit_rows(lv, tl, &row_need);
+    // hand the rows to their ticks (ascending): one TickLevel per job and tick, rows of several levels merged
+    std::vector<uint64_t> ticks(row_need.begin(), row_need.begin() + R);
+    std::sort(ticks.begin(), ticks.end());
+    ticks.erase(std::unique(ticks.begin(), ticks.end()), ticks.end());
+    for (uint64_t tk : ticks) {
+        std::vector<TickLevel> &slot = sched_[tk];
+        TickLevel *dst = nullptr;
+        for (TickLevel &l : slot)
+            if (l.job == job) dst = &l;
+        if (!dst) {
+            slot.emplace_back();
+            dst = &slot.back();
+            dst->job = job;
+        }
+        if (ticks.size() == 1 && dst->descs.empty()) {    // the common case: the whole level on one tick
+            *dst = std::move(tl);
+            break;
+        }
+        std::vector<uint32_t> moved(tl.ext.empty() ? 0 : R, 0);   // leader row -> its position in dst
+        for (size_t k = 0; k < R; k++) {
+            if (row_need[k] != tk) continue;
+            LinDesc d = tl.descs[k];
+            const uint32_t f = d.first_term;
+            d.first_term = (uint32_t)dst->terms.size();
+            dst->terms.insert(dst->terms.end(), tl.terms.begin() + f, tl.terms.begin() + f + d.n_terms);
+            if (!tl.ext.empty()) {
+                moved[k] = (uint32_t)dst->descs.size();
+                dst->body.resize(dst->descs.size(), nullptr);
+                dst->body.push_back(tl.body[k]);
+            }
+            dst->descs.push_back(d);
+            dst->lut.push_back(tl.lut[k]);
+            dst->out.push_back(tl.out[k]);
+            if (tl.recs.size() == tl.descs.size()) dst->recs.push_back(tl.recs[k]);
+        }
+        for (const ShareRow &f : tl.ext)                       // followers travel with their leader's tick
+            if (row_need[f.lead_row] == tk) dst->ext.push_back({moved[f.lead_row], f.K, f.out});
+    }
+    // streaming flush: every tick up to `base` is complete now (later levels cannot reach back) -- enqueue them while
+    // the host plans the next level
+    if (stream_pump)
+        while (!sched_.empty() && sched_.begin()->first <= base)
+            if (int rc = pump(1)) return rc;
     return 0;
 }
 
@@ -988,167 +985,206 @@ int Engine::upload_plan(void *d_dst, const void *src, size_t bytes) {
     return 0;
 }
 
-// one launch group over the union of the job levels scheduled for a tick
-int Engine::run_tick(std::vector<TickLevel> &levels, bool sharded) {
-    size_t width = 0, n_terms = 0;
-    for (auto &l : levels) { width += l.descs.size(); n_terms += l.terms.size(); }
-    if (width == 0) return 0;
-    for (auto &l : levels) {
-        stats.levels += 1;
-        if (stats.level_widths.size() < (1u << 20)) stats.level_widths.push_back((uint32_t)l.descs.size());
-        stats.max_level_width = std::max<uint64_t>(stats.max_level_width, l.descs.size());
+// ------------------------------------------------------------------------------------------
+// launch groups: lincomb -> keyswitch -> blind rotation over the rows of one or more job levels
+// ------------------------------------------------------------------------------------------
+void Engine::note_level(size_t width) {
+    stats.levels += 1;
+    if (stats.level_widths.size() < (1u << 20)) stats.level_widths.push_back((uint32_t)width);
+    stats.max_level_width = std::max<uint64_t>(stats.max_level_width, width);
+}
+
+// The device layout of a launch group, defined here only: [descs | terms | lut | out pointers (16-byte aligned)], and
+// with rotation sharing behind them [body pointer per row | one ExtractDesc per follower].  first_term becomes relative
+// to the group's terms.
+Engine::GroupView Engine::pack_group(const TickLevel *levels, size_t n_levels, std::vector<uint8_t> &host) const {
+    GroupView v;
+    size_t n_terms = 0;
+    for (size_t j = 0; j < n_levels; j++) {
+        v.width += levels[j].descs.size();
+        n_terms += levels[j].terms.size();
+        v.n_ext += levels[j].ext.size();
     }
-    const size_t world = sharded ? (size_t)ctx.dist.world : 1, rank = sharded ? (size_t)ctx.dist.rank : 0;
-    const size_t cap = (width + world - 1) / world;
-    const size_t lo = std::min(width, rank * cap), hi = std::min(width, lo + cap), cnt = hi - lo;
-    stats.pbs_executed += cnt;
-    size_t n_ext = 0;
-    for (auto &l : levels) n_ext += l.ext.size();
-    if (n_ext && sharded) return ctx.fail(-3, "internal: rotation sharing in a level-parallel launch group");
-    stats.pbs_extracted += n_ext;
-    if (stats.group_rows.size() < (1u << 20)) stats.group_rows.push_back((uint32_t)cnt);
-    if (planner && trace_plan) {
-        for (auto &l : levels) {
-            for (size_t k = 0; k < l.descs.size(); k++) {
-                const LinDesc &d = l.descs[k];
-                trace_.push_back(TR_ROW);
-                trace_.push_back((uint64_t)(uintptr_t)l.out[k]);
-                trace_.push_back(l.lut[k]);
-                trace_.push_back(d.konst_body >> DELTA_LOG);
-                trace_.push_back(d.n_terms);
-                for (uint32_t t = 0; t < d.n_terms; t++) {
-                    trace_.push_back((uint64_t)(uintptr_t)l.terms[d.first_term + t].src);
-                    trace_.push_back((uint64_t)l.terms[d.first_term + t].coef);
-                }
-            }
-            for (const ShareRow &f : l.ext) {
-                trace_.push_back(TR_EXT);
-                trace_.push_back((uint64_t)(uintptr_t)l.out[f.lead_row]);
-                trace_.push_back((uint64_t)(uintptr_t)f.out);
-                trace_.push_back(f.K);
-            }
-        }
-        trace_.push_back(TR_GROUP_END);
-        trace_.push_back(width);
-    }
-    if (planner) {
-        // nothing runs, but the exchange of a level-parallel launch group is accounted for like Dist::all_gather does
-        if (sharded) { ctx.dist.n_gathers++; ctx.dist.bytes_sent += cap * BIG_CT * 8; }
-        for (auto &l : levels)
-            for (uint64_t *b : l.body)
-                if (b) free_block(b);
-        return 0;
-    }
-    if (hipSetDevice(ctx.device) != hipSuccess) return ctx.fail(-2, "hipSetDevice failed");
-    const size_t off_desc = 0;
-    const size_t off_terms = off_desc + width * sizeof(LinDesc);
-    const size_t off_lut = off_terms + n_terms * sizeof(LinTerm);
-    const size_t off_out = (off_lut + width * 4 + 15) & ~(size_t)15;
-    // rotation sharing: [body pointer per row | one ExtractDesc per follower] behind the output pointers
-    const size_t off_body = off_out + width * sizeof(uint64_t *);
-    const size_t off_ext = off_body + (n_ext ? width * sizeof(uint64_t *) : 0);
-    const size_t total = off_ext + n_ext * sizeof(ExtractDesc);
-    std::vector<uint8_t> host(total);
-    LinDesc *hd = reinterpret_cast<LinDesc *>(host.data() + off_desc);
-    LinTerm *ht = reinterpret_cast<LinTerm *>(host.data() + off_terms);
-    uint32_t *hl = reinterpret_cast<uint32_t *>(host.data() + off_lut);
-    uint64_t **ho = reinterpret_cast<uint64_t **>(host.data() + off_out);
-    uint64_t **hb = reinterpret_cast<uint64_t **>(host.data() + off_body);
-    ExtractDesc *hx = reinterpret_cast<ExtractDesc *>(host.data() + off_ext);
+    v.off_terms = v.width * sizeof(LinDesc);
+    v.off_lut = v.off_terms + n_terms * sizeof(LinTerm);
+    v.off_out = (v.off_lut + v.width * 4 + 15) & ~(size_t)15;
+    v.off_body = v.off_out + v.width * sizeof(uint64_t *);
+    v.off_ext = v.off_body + (v.n_ext ? v.width * sizeof(uint64_t *) : 0);
+    v.total = v.off_ext + v.n_ext * sizeof(ExtractDesc);
+    host.assign(v.total, 0);
+    LinDesc *hd = reinterpret_cast<LinDesc *>(host.data());
+    LinTerm *ht = reinterpret_cast<LinTerm *>(host.data() + v.off_terms);
+    uint32_t *hl = reinterpret_cast<uint32_t *>(host.data() + v.off_lut);
+    uint64_t **ho = reinterpret_cast<uint64_t **>(host.data() + v.off_out);
+    uint64_t **hb = reinterpret_cast<uint64_t **>(host.data() + v.off_body);
+    ExtractDesc *hx = reinterpret_cast<ExtractDesc *>(host.data() + v.off_ext);
     size_t di = 0, ti = 0, xi = 0;
-    for (auto &l : levels) {
+    for (size_t j = 0; j < n_levels; j++) {
+        const TickLevel &l = levels[j];
         for (size_t k = 0; k < l.descs.size(); k++) {
             LinDesc d = l.descs[k];
             d.first_term += (uint32_t)ti;
             hd[di + k] = d;
             hl[di + k] = l.lut[k];
             ho[di + k] = l.out[k];
-            if (n_ext) hb[di + k] = k < l.body.size() ? l.body[k] : nullptr;
+            if (v.n_ext) hb[di + k] = k < l.body.size() ? l.body[k] : nullptr;
         }
         for (const ShareRow &f : l.ext) hx[xi++] = ExtractDesc{l.out[f.lead_row], l.body[f.lead_row], f.out, f.K, 0};
-        std::memcpy(ht + ti, l.terms.data(), l.terms.size() * sizeof(LinTerm));
+        if (!l.terms.empty()) std::memcpy(ht + ti, l.terms.data(), l.terms.size() * sizeof(LinTerm));
         di += l.descs.size();
         ti += l.terms.size();
     }
-    hipError_t e = tick_buf_.cap >= total ? hipSuccess : hipStreamSynchronize(ctx.stream);
-    if (e == hipSuccess) e = tick_buf_.reserve(total);
-    if (e == hipSuccess && batch_in_.cap < width * BIG_CT * 8) {
-        e = hipStreamSynchronize(ctx.stream);
-        if (e == hipSuccess) e = batch_in_.reserve(width * BIG_CT * 8);
+    return v;
+}
+
+// room for a group of `width` rows whose packed form takes `bytes`; a buffer that grows waits for the stream (queued
+// launches read the old one)
+int Engine::ensure_group_buffers(size_t width, size_t bytes) {
+    auto grow = [&](DevBuf &b, size_t want) {
+        if (b.cap >= want) return hipSuccess;
+        hipError_t e = hipStreamSynchronize(ctx.stream);
+        return e == hipSuccess ? b.reserve(want) : e;
+    };
+    hipError_t e = grow(tick_buf_, bytes);
+    if (e == hipSuccess) e = grow(batch_in_, width * BIG_CT * 8);
+    if (e == hipSuccess) e = grow(ctx.ks_buf, width * SMALL_CT * 8);
+    return e == hipSuccess ? 0 : ctx.hip_fail(e, "tick buffers");
+}
+
+// packs the group, makes room and uploads it: stream-ordered after the previous group's kernels, which read the old
+// contents; pinned staging, so the host goes on
+int Engine::upload_group(const TickLevel *levels, size_t n_levels, GroupView &v) {
+    std::vector<uint8_t> host;
+    v = pack_group(levels, n_levels, host);
+    if (int rc = ensure_group_buffers(v.width, v.total)) return rc;
+    return upload_plan(tick_buf_.ptr, host.data(), v.total);
+}
+
+// debug only: a strided sample of rows [first, first + cnt) of level `l`, which lie in batch_in_ from row `batch_row`
+// on, goes to the host (synchronous copies).  `level`: live captures number the levels as the statistics do, captures
+// through an all-at-once plan by their position in that flush.
+int Engine::sample_capture(const TickLevel &l, size_t first, size_t cnt, size_t batch_row, uint32_t level) {
+    const size_t stride = (cnt + capture_max_rows - 1) / capture_max_rows;
+    for (size_t i = 0; i < cnt; i += stride) {
+        const size_t at = capture_rows.size();
+        capture_rows.resize(at + BIG_CT);
+        hipError_t e = hipMemcpyAsync(capture_rows.data() + at, batch_in_.as<uint64_t>() + (batch_row + i) * BIG_CT, BIG_CT * 8,
+                                      hipMemcpyDeviceToHost, ctx.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
+        if (e != hipSuccess) return ctx.hip_fail(e, "capture download");
+        CaptureRec r = l.recs[first + i];
+        r.level = level;
+        capture_recs.push_back(r);
     }
-    if (e == hipSuccess && ctx.ks_buf.cap < width * SMALL_CT * 8) {
-        e = hipStreamSynchronize(ctx.stream);
-        if (e == hipSuccess) e = ctx.ks_buf.reserve(width * SMALL_CT * 8);
-    }
-    if (e != hipSuccess) return ctx.hip_fail(e, "tick buffers");
-    // stream-ordered after the previous tick's kernels, which read the old contents; pinned staging: the host goes on
-    if (int rc = upload_plan(tick_buf_.ptr, host.data(), total)) return rc;
+    return 0;
+}
+
+// Rows [lo, lo + cnt) of the uploaded group `v`: lincomb -> (capture sample) -> keyswitch -> blind rotation.
+// dense_out: the results go to its rows 0..cnt (a slice for an exchange); null: to the rows' own blocks (and the
+// accumulator bodies of rotation leaders to theirs).  levels / first_level: the group's levels for the capture
+// sampler (n_levels 0: none).
+int Engine::launch_rows(const GroupView &v, size_t lo, size_t cnt, uint64_t *dense_out, const TickLevel *levels,
+                        size_t n_levels, size_t first_level) {
     const uint8_t *dp = tick_buf_.as<uint8_t>();
-    const LinDesc *d_desc = reinterpret_cast<const LinDesc *>(dp + off_desc);
-    const LinTerm *d_terms = reinterpret_cast<const LinTerm *>(dp + off_terms);
-    const uint32_t *d_lut = reinterpret_cast<const uint32_t *>(dp + off_lut);
-    uint64_t *const *d_out = reinterpret_cast<uint64_t *const *>(dp + off_out);
-    if (!sharded) {
-        e = launch_lincomb(d_desc, d_terms, batch_in_.as<uint64_t>(), (int)width, ctx.stream);
-        if (e != hipSuccess) return ctx.hip_fail(e, "lincomb launch");
-        if (capture_max_rows && capture_live) {
-            // debug only: a strided sample of every job level's PBS inputs in this launch group goes to the host
-            // (synchronous copies); the rows are the ones the production path bootstraps, shared rotations included
-            size_t row0 = 0, lvl = stats.levels - levels.size();
-            for (auto &l : levels) {
-                const size_t cnt_l = l.descs.size();
-                if (l.recs.size() == cnt_l) {
-                    const size_t stride = (cnt_l + capture_max_rows - 1) / capture_max_rows;
-                    for (size_t i = 0; i < cnt_l; i += stride) {
-                        const size_t at = capture_rows.size();
-                        capture_rows.resize(at + BIG_CT);
-                        e = hipMemcpyAsync(capture_rows.data() + at, batch_in_.as<uint64_t>() + (row0 + i) * BIG_CT, BIG_CT * 8,
-                                           hipMemcpyDeviceToHost, ctx.stream);
-                        if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
-                        if (e != hipSuccess) return ctx.hip_fail(e, "capture download");
-                        CaptureRec r = l.recs[i];
-                        r.level = (uint32_t)lvl;
-                        capture_recs.push_back(r);
-                    }
-                }
-                row0 += cnt_l;
-                lvl++;
+    const LinDesc *d_desc = reinterpret_cast<const LinDesc *>(dp);
+    const LinTerm *d_terms = reinterpret_cast<const LinTerm *>(dp + v.off_terms);
+    const uint32_t *d_lut = reinterpret_cast<const uint32_t *>(dp + v.off_lut);
+    uint64_t *const *d_out = reinterpret_cast<uint64_t *const *>(dp + v.off_out);
+    uint64_t *const *d_body = reinterpret_cast<uint64_t *const *>(dp + v.off_body);
+    hipError_t e = launch_lincomb(d_desc + lo, d_terms, batch_in_.as<uint64_t>(), (int)cnt, ctx.stream);
+    if (e != hipSuccess) return ctx.hip_fail(e, "lincomb launch");
+    size_t row0 = 0;
+    for (size_t j = 0; j < n_levels && capture_max_rows; j++) {
+        const TickLevel &l = levels[j];
+        const size_t w = l.descs.size(), a = std::max(lo, row0), b = std::min(lo + cnt, row0 + w);
+        if (l.recs.size() == w && a < b)
+            if (int rc = sample_capture(l, a - row0, b - a, a - lo, (uint32_t)(first_level + j))) return rc;
+        row0 += w;
+    }
+    if (int rc = ctx.keyswitch(batch_in_.as<uint64_t>(), cnt, ctx.stream)) return rc;
+    return ctx.blind_rotate(ctx.ks_buf.as<uint64_t>(), d_lut + lo, d_luts_, dense_out, dense_out ? nullptr : d_out + lo, cnt,
+                            ctx.stream, v.n_ext && !dense_out ? d_body + lo : nullptr);
+}
+
+// rows 0..width of d_all (a gathered level, row order) -> the rows' own blocks; d_out: their pointer table on the device
+int Engine::scatter_rows(const uint64_t *d_all, uint64_t *const *d_out, size_t width) {
+    hipError_t e = launch_scatter_blocks(d_all, d_out, (int)width, ctx.stream);
+    return e == hipSuccess ? 0 : ctx.hip_fail(e, "scatter launch");
+}
+
+// what a planner context WOULD run in this launch group (engine.h "plan trace")
+void Engine::trace_group(const std::vector<TickLevel> &levels, size_t width) {
+    for (auto &l : levels) {
+        for (size_t k = 0; k < l.descs.size(); k++) {
+            const LinDesc &d = l.descs[k];
+            trace_.insert(trace_.end(), {TR_ROW, (uint64_t)(uintptr_t)l.out[k], l.lut[k], d.konst_body >> DELTA_LOG, d.n_terms});
+            for (uint32_t t = 0; t < d.n_terms; t++) {
+                trace_.push_back((uint64_t)(uintptr_t)l.terms[d.first_term + t].src);
+                trace_.push_back((uint64_t)l.terms[d.first_term + t].coef);
             }
         }
-        if (int rc = ctx.keyswitch(batch_in_.as<uint64_t>(), width, ctx.stream)) return rc;
-        uint64_t *const *d_body = n_ext ? reinterpret_cast<uint64_t *const *>(dp + off_body) : nullptr;
-        if (int rc = ctx.blind_rotate(ctx.ks_buf.as<uint64_t>(), d_lut, d_luts_, nullptr, d_out, width, ctx.stream, d_body)) return rc;
-        if (n_ext) {
-            // the followers: further sample extractions of their leaders' accumulators, then the body polynomials' blocks
-            // go back to the pool (stream order: whoever gets them next runs behind this kernel)
-            e = launch_extract_shift(reinterpret_cast<const ExtractDesc *>(dp + off_ext), (int)n_ext, ctx.stream);
-            if (e != hipSuccess) return ctx.hip_fail(e, "extract launch");
-            for (auto &l : levels)
-                for (uint64_t *b : l.body)
-                    if (b) free_block(b);
-        }
-        if (!last_group_done_) (void)hipEventCreateWithFlags(&last_group_done_, hipEventDisableTiming);
-        if (last_group_done_) (void)hipEventRecord(last_group_done_, ctx.stream);
+        for (const ShareRow &f : l.ext)
+            trace_.insert(trace_.end(), {TR_EXT, (uint64_t)(uintptr_t)l.out[f.lead_row], (uint64_t)(uintptr_t)f.out, f.K});
+    }
+    trace_.push_back(TR_GROUP_END);
+    trace_.push_back(width);
+}
+
+// One launch group over the union of the job levels scheduled for a tick.  sharded: level-parallel mode -- this rank
+// runs slice [rank*cap, (rank+1)*cap) of the group into the exchange buffer, the slices are all-gathered on the stream
+// and scattered into the nodes' blocks (all enqueued, no host wait with RCCL).
+int Engine::run_tick(std::vector<TickLevel> &levels, bool sharded) {
+    size_t width = 0, n_ext = 0;
+    for (auto &l : levels) { width += l.descs.size(); n_ext += l.ext.size(); }
+    if (width == 0) return 0;
+    for (auto &l : levels) note_level(l.descs.size());        // the full width, whatever this rank's slice
+    const size_t world = sharded ? (size_t)ctx.dist.world : 1, rank = sharded ? (size_t)ctx.dist.rank : 0;
+    const size_t cap = (width + world - 1) / world;
+    const size_t lo = std::min(width, rank * cap), hi = std::min(width, lo + cap), cnt = hi - lo;
+    stats.pbs_executed += cnt;
+    if (n_ext && sharded) return ctx.fail(-3, "internal: rotation sharing in a level-parallel launch group");
+    stats.pbs_extracted += n_ext;
+    if (stats.group_rows.size() < (1u << 20)) stats.group_rows.push_back((uint32_t)cnt);
+    auto free_bodies = [&] {                                  // the accumulator bodies' blocks go back to the pool
+        for (auto &l : levels)
+            for (uint64_t *b : l.body)
+                if (b) free_block(b);
+    };
+    if (planner) {
+        if (trace_plan) trace_group(levels, width);
+        // nothing runs, but the exchange of a level-parallel launch group is accounted for like Dist::all_gather does
+        if (sharded) { ctx.dist.n_gathers++; ctx.dist.bytes_sent += cap * BIG_CT * 8; }
+        free_bodies();
         return 0;
     }
-    // level-parallel: own slice -> dense exchange buffer -> all-gather -> scatter (all enqueued, no host wait with RCCL)
-    if (ctx.xchg_send.cap < cap * BIG_CT * 8 || ctx.xchg_recv.cap < world * cap * BIG_CT * 8) {
-        e = hipStreamSynchronize(ctx.stream);
-        if (e == hipSuccess) e = ctx.xchg_send.reserve(cap * BIG_CT * 8);
-        if (e == hipSuccess) e = ctx.xchg_recv.reserve(world * cap * BIG_CT * 8);
-        if (e != hipSuccess) return ctx.hip_fail(e, "level exchange buffers");
-    }
-    if (cnt) {
-        e = launch_lincomb(d_desc + lo, d_terms, batch_in_.as<uint64_t>(), (int)cnt, ctx.stream);
-        if (e != hipSuccess) return ctx.hip_fail(e, "lincomb launch");
-        if (int rc = ctx.keyswitch(batch_in_.as<uint64_t>(), cnt, ctx.stream)) return rc;
-        if (int rc = ctx.blind_rotate(ctx.ks_buf.as<uint64_t>(), d_lut + lo, d_luts_, ctx.xchg_send.as<uint64_t>(), nullptr, cnt,
-                                      ctx.stream))
+    if (hipSetDevice(ctx.device) != hipSuccess) return ctx.fail(-2, "hipSetDevice failed");
+    GroupView v;
+    if (int rc = upload_group(levels.data(), levels.size(), v)) return rc;
+    if (!sharded) {
+        // while capturing live: the rows are the ones the production path bootstraps, shared rotations included
+        if (int rc = launch_rows(v, 0, width, nullptr, levels.data(), levels.size(), stats.levels - levels.size())) return rc;
+        if (n_ext) {
+            // the followers: further sample extractions of their leaders' accumulators (stream order: whoever gets the
+            // bodies' blocks next runs behind this kernel)
+            hipError_t e = launch_extract_shift(reinterpret_cast<const ExtractDesc *>(tick_buf_.as<uint8_t>() + v.off_ext),
+                                                (int)n_ext, ctx.stream);
+            if (e != hipSuccess) return ctx.hip_fail(e, "extract launch");
+            free_bodies();
+        }
+    } else {
+        if (ctx.xchg_send.cap < cap * BIG_CT * 8 || ctx.xchg_recv.cap < world * cap * BIG_CT * 8) {
+            hipError_t e = hipStreamSynchronize(ctx.stream);
+            if (e == hipSuccess) e = ctx.xchg_send.reserve(cap * BIG_CT * 8);
+            if (e == hipSuccess) e = ctx.xchg_recv.reserve(world * cap * BIG_CT * 8);
+            if (e != hipSuccess) return ctx.hip_fail(e, "level exchange buffers");
+        }
+        if (cnt)
+            if (int rc = launch_rows(v, lo, cnt, ctx.xchg_send.as<uint64_t>(), nullptr, 0, 0)) return rc;
+        if (int rc = ctx.dist.all_gather(ctx.xchg_send.ptr, ctx.xchg_recv.ptr, cap * BIG_CT * 8, ctx.stream, ctx.err)) return rc;
+        if (int rc = scatter_rows(ctx.xchg_recv.as<uint64_t>(),
+                                  reinterpret_cast<uint64_t *const *>(tick_buf_.as<uint8_t>() + v.off_out), width))
             return rc;
     }
-    if (int rc = ctx.dist.all_gather(ctx.xchg_send.ptr, ctx.xchg_recv.ptr, cap * BIG_CT * 8, ctx.stream, ctx.err)) return rc;
-    e = launch_scatter_blocks(ctx.xchg_recv.as<uint64_t>(), d_out, (int)width, ctx.stream);
-    if (e != hipSuccess) return ctx.hip_fail(e, "scatter launch");
     if (!last_group_done_) (void)hipEventCreateWithFlags(&last_group_done_, hipEventDisableTiming);
     if (last_group_done_) (void)hipEventRecord(last_group_done_, ctx.stream);
     return 0;
@@ -1230,196 +1266,64 @@ int Engine::gather_blocks(const Bid *local, size_t n, std::vector<Bid> &out) {
     return 0;
 }
 
-// Builds the plan for every pending level and uploads it; nodes get their output blocks here.
+// ------------------------------------------------------------------------------------------
+// the all-at-once plan (fhs_flush_plan / fhs_flush_level_exec / fhs_flush_level_commit, and captures that are not live)
+// ------------------------------------------------------------------------------------------
+// Plans every pending level with the builder of plan_job, but as whole DAG levels in level order: no rotation sharing,
+// no tick scheduling, no round alignment.  The nodes get their output blocks here; the levels wait in planned_ for
+// exec_level, which counts them in the statistics when they run.
 int Engine::plan_flush() {
-    plan_.levels.clear();
-    plan_.recs.clear();
+    planned_.clear();
+    planned_max_width_ = 0;
     if (pending_.empty()) return 0;
     if (!planner) {
         if (!ctx.key_loaded) return ctx.fail(-3, "server key not loaded");
         if (hipSetDevice(ctx.device) != hipSuccess) return ctx.fail(-2, "hipSetDevice failed");
     }
-
-    std::map<uint32_t, std::vector<Bid>> by_level;
-    for (const Pend &p : pending_)
-        if (nodes_[p.id].kind == BlockNode::PBS && nodes_[p.id].gen == p.gen) by_level[nodes_[p.id].level].push_back(p.id);
-    pending_.clear();
-    n_depth1_ = 0;
-    n_depth1_solo_ = 0;
-    depth1_keys_.clear();
-    if (by_level.empty()) return 0;
-
-    std::vector<LevelPlan> &levels = plan_.levels;
-    std::vector<LinDesc> descs;
-    std::vector<LinTerm> terms;
-    std::vector<uint32_t> lut_idx;
-    std::vector<uint64_t *> out_ptrs;
-    size_t max_width = 0;
-
+    LevelMap by_level = collect_levels(false);
+    std::vector<uint64_t> row_need;
     for (auto &kv : by_level) {
-        std::vector<Bid> &lv = kv.second;
-        const size_t first = descs.size();
-        for (Bid b : lv) {
-            BlockNode &n = nodes_[b];
-            const BlockNode &s = nodes_[n.src];
-            LinDesc d{};
-            d.first_term = (uint32_t)terms.size();
-            if (s.kind == BlockNode::MAT) {
-                terms.push_back({s.dev, 1});
-                d.n_terms = 1;
-                d.konst_body = 0;
-            } else if (s.kind == BlockNode::LIN) {
-                for (const Term &t : s.terms) {
-                    const BlockNode &tb = nodes_[t.blk];
-                    if (tb.kind != BlockNode::MAT || !tb.dev)
-                        return ctx.fail(-3, "internal: lincomb term not materialised at its level");
-                    terms.push_back({tb.dev, t.coef});
-                }
-                d.n_terms = (uint32_t)s.terms.size();
-                d.konst_body = (uint64_t)(s.konst & 31) << DELTA_LOG;
-            } else {
-                return ctx.fail(-3, "internal: PBS source is neither MAT nor LIN");
-            }
-            descs.push_back(d);
-            lut_idx.push_back(n.lut);
-            {   // noise bookkeeping: sum of squared coefficients of the (flattened) linear combination entering this
-                // bootstrap, i.e. its noise variance in units of one bootstrap output's (uploads counted like outputs)
-                int64_t c2 = 0;
-                if (s.kind == BlockNode::LIN) c2 = lin_c2(s.terms);
-                else c2 = s.var;
-                stats.max_input_sum_c2 = std::max<uint64_t>(stats.max_input_sum_c2, (uint64_t)c2);
-                if (c2 > 64 && std::getenv("FHS_DEBUG_C2")) {
-                    std::fprintf(stderr, "c2=%lld lut=%d terms:", (long long)c2, (int)n.lut);
-                    for (const Term &t : s.terms) std::fprintf(stderr, " %lld*b%u", (long long)t.coef, t.blk);
-                    std::fprintf(stderr, "\n");
-                }
-                if (capture_max_rows)
-                    plan_.recs.push_back(CaptureRec{(uint32_t)levels.size(), (uint32_t)(descs.size() - 1 - first), n.lut,
-                                                    d.n_terms, c2, s.kind == BlockNode::LIN ? s.konst : 0,
-                                                    (uint32_t)lv.size()});
-            }
-            uint64_t *o = alloc_block();
-            if (!o) return ctx.fail(-2, "device block pool exhausted (hipMalloc failed)");
-            out_ptrs.push_back(o);
-        }
-        // commit the level: nodes become materialised, their inputs can be recycled by later levels
-        for (size_t k = 0; k < lv.size(); k++) {
-            BlockNode &n = nodes_[lv[k]];
-            const Bid src = n.src;
-            n.kind = BlockNode::MAT;
-            n.dev = out_ptrs[first + k];
-            n.src = 0;
-            n.level = 0;
-            release(src);
-        }
-        levels.push_back({first, lv.size()});
-        max_width = std::max(max_width, lv.size());
+        planned_.emplace_back();
+        if (int rc = build_rows(kv.second, kv.second.size(), planned_.back(), row_need, true, (uint32_t)planned_.size() - 1)) return rc;
+        commit_rows(kv.second, planned_.back(), nullptr);
+        planned_max_width_ = std::max(planned_max_width_, kv.second.size());
     }
-
-    plan_.max_width = max_width;
-    if (planner) return 0;                           // nothing to upload: the plan only feeds the statistics
-    // one upload: [descs | terms | lut_idx | out_ptrs]
-    const size_t off_desc = 0;
-    const size_t off_terms = off_desc + descs.size() * sizeof(LinDesc);
-    const size_t off_lut = off_terms + terms.size() * sizeof(LinTerm);
-    const size_t off_out = (off_lut + lut_idx.size() * 4 + 15) & ~(size_t)15;
-    const size_t total = off_out + out_ptrs.size() * sizeof(uint64_t *);
-    std::vector<uint8_t> host(total);
-    std::memcpy(host.data() + off_desc, descs.data(), descs.size() * sizeof(LinDesc));
-    std::memcpy(host.data() + off_terms, terms.data(), terms.size() * sizeof(LinTerm));
-    std::memcpy(host.data() + off_lut, lut_idx.data(), lut_idx.size() * 4);
-    std::memcpy(host.data() + off_out, out_ptrs.data(), out_ptrs.size() * sizeof(uint64_t *));
-    // the previous flush may still be reading the old plan buffer: order through the stream
-    hipError_t e = plan_buf_.cap >= total ? hipSuccess : hipStreamSynchronize(ctx.stream);
-    if (e == hipSuccess) e = plan_buf_.reserve(total);
-    if (e != hipSuccess) return ctx.hip_fail(e, "plan buffer");
-    if (int rc = upload_plan(plan_buf_.ptr, host.data(), total)) return rc;
-    if (batch_in_.cap < max_width * BIG_CT * 8) {
-        e = hipStreamSynchronize(ctx.stream);
-        if (e == hipSuccess) e = batch_in_.reserve(max_width * BIG_CT * 8);
-        if (e != hipSuccess) return ctx.hip_fail(e, "batch buffer");
-    }
-    if (ctx.ks_buf.cap < max_width * SMALL_CT * 8) {
-        e = hipStreamSynchronize(ctx.stream);
-        if (e == hipSuccess) e = ctx.ks_buf.reserve(max_width * SMALL_CT * 8);
-        if (e != hipSuccess) return ctx.hip_fail(e, "ks buffer");
-    }
-    // pageable host memory: hipMemcpyAsync has consumed `host` when it returns
-
-    plan_.off_desc = off_desc;
-    plan_.off_terms = off_terms;
-    plan_.off_lut = off_lut;
-    plan_.off_out = off_out;
-    plan_.max_width = max_width;
     return 0;
 }
 
-// Runs items [lo, hi) of level k.  dense_out == nullptr: results go straight to the nodes' blocks;
+// Runs rows [lo, hi) of planned level k.  dense_out == nullptr: results go straight to the nodes' blocks;
 // otherwise they are written as rows 0..hi-lo of dense_out (distributed mode, before the all-gather).
 int Engine::exec_level(size_t k, size_t lo, size_t hi, uint64_t *dense_out) {
-    if (k >= plan_.levels.size()) return ctx.fail(-1, "level index out of range");
-    const LevelPlan &lp = plan_.levels[k];
-    if (lo > hi || hi > lp.count) return ctx.fail(-1, "slice out of range");
+    if (k >= planned_.size()) return ctx.fail(-1, "level index out of range");
+    const TickLevel &l = planned_[k];
+    if (lo > hi || hi > l.descs.size()) return ctx.fail(-1, "slice out of range");
     const size_t cnt = hi - lo;
     if (cnt == 0) return 0;
+    if (!planner) {
+        if (hipSetDevice(ctx.device) != hipSuccess) return ctx.fail(-2, "hipSetDevice failed");
+        GroupView v;
+        if (int rc = upload_group(&l, 1, v)) return rc;
+        if (int rc = launch_rows(v, lo, cnt, dense_out, &l, 1, k)) return rc;
+    }
     if (stats.group_rows.size() < (1u << 20)) stats.group_rows.push_back((uint32_t)cnt);
-    if (planner) {
-        stats.pbs_executed += cnt;
-        if (lo == 0 || dense_out) {
-            stats.levels += 1;
-            if (stats.level_widths.size() < (1u << 20)) stats.level_widths.push_back((uint32_t)lp.count);
-            stats.max_level_width = std::max<uint64_t>(stats.max_level_width, lp.count);
-        }
-        return 0;
-    }
-    if (hipSetDevice(ctx.device) != hipSuccess) return ctx.fail(-2, "hipSetDevice failed");
-    const uint8_t *dp = plan_buf_.as<uint8_t>();
-    const LinDesc *d_desc = reinterpret_cast<const LinDesc *>(dp + plan_.off_desc) + lp.first + lo;
-    const LinTerm *d_terms = reinterpret_cast<const LinTerm *>(dp + plan_.off_terms);
-    const uint32_t *d_lut = reinterpret_cast<const uint32_t *>(dp + plan_.off_lut) + lp.first + lo;
-    uint64_t *const *d_out = reinterpret_cast<uint64_t *const *>(dp + plan_.off_out) + lp.first + lo;
-    hipError_t e = launch_lincomb(d_desc, d_terms, batch_in_.as<uint64_t>(), (int)cnt, ctx.stream);
-    if (e != hipSuccess) return ctx.hip_fail(e, "lincomb launch");
-    if (capture_max_rows && plan_.recs.size() >= lp.first + hi) {
-        // debug only: a strided sample of this level's PBS inputs goes to the host (synchronous copies)
-        const size_t stride = (cnt + capture_max_rows - 1) / capture_max_rows;
-        for (size_t i = 0; i < cnt; i += stride) {
-            const size_t at = capture_rows.size();
-            capture_rows.resize(at + BIG_CT);
-            e = hipMemcpyAsync(capture_rows.data() + at, batch_in_.as<uint64_t>() + i * BIG_CT, BIG_CT * 8,
-                               hipMemcpyDeviceToHost, ctx.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
-            if (e != hipSuccess) return ctx.hip_fail(e, "capture download");
-            capture_recs.push_back(plan_.recs[lp.first + lo + i]);
-        }
-    }
-    if (int rc = ctx.keyswitch(batch_in_.as<uint64_t>(), cnt, ctx.stream)) return rc;
-    if (int rc = ctx.blind_rotate(ctx.ks_buf.as<uint64_t>(), d_lut, d_luts_, dense_out, dense_out ? nullptr : d_out, cnt,
-                                  ctx.stream))
-        return rc;
     stats.pbs_executed += cnt;
-    if (lo == 0 || dense_out) {
-        stats.levels += 1;
-        if (stats.level_widths.size() < (1u << 20)) stats.level_widths.push_back((uint32_t)lp.count);
-        stats.max_level_width = std::max<uint64_t>(stats.max_level_width, lp.count);
-    }
+    if (lo == 0 || dense_out) note_level(l.descs.size());
     return 0;
 }
 
-// Distributed mode: rows 0..count of d_all (the gathered level, item order) -> the nodes' blocks.
+// Distributed mode: rows 0..width of d_all (the gathered level, row order) -> the nodes' blocks.  Other work may have
+// used the stream since exec_level: the level's pointer table is uploaded again.
 int Engine::commit_level(size_t k, const uint64_t *d_all) {
-    if (k >= plan_.levels.size()) return ctx.fail(-1, "level index out of range");
-    const LevelPlan &lp = plan_.levels[k];
-    if (planner) {
-        if (k + 1 == plan_.levels.size()) plan_.levels.clear();
-        return 0;
+    if (k >= planned_.size()) return ctx.fail(-1, "level index out of range");
+    const TickLevel &l = planned_[k];
+    if (!planner) {
+        if (hipSetDevice(ctx.device) != hipSuccess) return ctx.fail(-2, "hipSetDevice failed");
+        const size_t bytes = l.out.size() * sizeof(uint64_t *);
+        if (int rc = ensure_group_buffers(0, bytes)) return rc;
+        if (int rc = upload_plan(tick_buf_.ptr, l.out.data(), bytes)) return rc;
+        if (int rc = scatter_rows(d_all, tick_buf_.as<uint64_t *>(), l.out.size())) return rc;
     }
-    if (hipSetDevice(ctx.device) != hipSuccess) return ctx.fail(-2, "hipSetDevice failed");
-    uint64_t *const *d_out =
-        reinterpret_cast<uint64_t *const *>(plan_buf_.as<uint8_t>() + plan_.off_out) + lp.first;
-    hipError_t e = launch_scatter_blocks(d_all, d_out, (int)lp.count, ctx.stream);
-    if (e != hipSuccess) return ctx.hip_fail(e, "scatter launch");
-    if (k + 1 == plan_.levels.size()) plan_.levels.clear();
+    if (k + 1 == planned_.size()) planned_.clear();
     return 0;
 }
 

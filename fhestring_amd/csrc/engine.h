@@ -2,9 +2,14 @@
 // programmable bootstraps and launches each dependency level as one wide batch.
 //
 // The reference evaluates every FheAsciiChar op eagerly and blocking; behind that
-// API a GPU would only ever see 4-8 PBS at a time.  Here an op only creates nodes; flush() plans
-// all levels on the host, uploads the plan once and enqueues lincomb -> keyswitch -> blind-rotate
-// per level on one stream with no host round trip in between.
+// API a GPU would only ever see 4-8 PBS at a time.  Here an op only creates nodes.  The pending
+// bootstraps are planned LEVEL BY LEVEL (plan_job): rows that differ only in a trivial constant
+// share one blind rotation, the level's rows are uploaded and enqueued as one launch group
+// (lincomb -> keyswitch -> blind rotation, run_tick) while the host plans the next level -- or, for
+// submitted jobs and round alignment, scheduled on ticks whose launch groups merge the levels of
+// several jobs.  A level that is already wide is peeled and run while the DAG is still being
+// recorded.  One level builder and one launch-group path serve all of it, the all-at-once plan of
+// fhs_flush_plan / fhs_flush_level_exec / fhs_flush_level_commit included.
 #pragma once
 #include <cstdint>
 #include <map>
@@ -131,13 +136,14 @@ class Engine {
     // Flushes the local DAG first; everything is enqueued on the context's stream.
     int gather_blocks(const Bid *local, size_t n, std::vector<Bid> &out);
     // distributed execution (one process per GPU, identical DAGs on every rank): plan once, then per
-    // level every rank runs its slice into a dense buffer, the caller all-gathers, commit scatters
+    // level every rank runs its slice into a dense buffer, the caller all-gathers, commit scatters.
+    // plan_flush is plan_job's level builder without rotation sharing and without scheduling: whole DAG levels in
+    // level order, kept until exec_level runs them through the launch-group path of run_tick.
     int dist_rank = 0, dist_world = 1;
-    struct LevelPlan { size_t first, count; };
     int plan_flush();
-    size_t planned_levels() const { return plan_.levels.size(); }
-    size_t level_width(size_t k) const { return plan_.levels[k].count; }
-    size_t planned_max_width() const { return plan_.max_width; }
+    size_t planned_levels() const { return planned_.size(); }
+    size_t level_width(size_t k) const { return planned_[k].descs.size(); }
+    size_t planned_max_width() const { return planned_max_width_; }
     int exec_level(size_t k, size_t lo, size_t hi, uint64_t *dense_out);
     int commit_level(size_t k, const uint64_t *d_all);
     int read_block(Bid b, uint64_t *host_out);        // flushes if needed
@@ -157,7 +163,8 @@ class Engine {
     struct CaptureRec { uint32_t level, index, lut, n_terms; int64_t sum_c2; int32_t konst; uint32_t width; };
     size_t capture_max_rows = 0;
     // capture_live: sample inside the ordinary execution path (plan_job / run_tick: rotation sharing, round alignment and
-    // tick scheduling as in production) instead of the all-at-once plan of plan_flush (which never shares rotations)
+    // tick scheduling as in production; records numbered like stats.levels, width = the level's rotation rows) instead of
+    // the all-at-once plan of plan_flush (unshared, whole levels; records numbered by their level within the flush)
     bool capture_live = false;
     std::vector<uint64_t> capture_rows;      // [n][2049]
     std::vector<CaptureRec> capture_recs;
@@ -197,18 +204,18 @@ class Engine {
     uint64_t live_dev_blocks_ = 0;
     uint64_t planner_tokens_ = 0;
     bool ensure_staging(size_t n_blocks);
+    // whole-string uploads (from_host_many / from_compressed_many / from_public_many)
+    int undo_upload(Bid *out, size_t count);                   // releases what was made, zeroes out[], returns -1
+    bool new_mat_blocks(size_t n, Bid *out, uint64_t *ptrs);
+    int plan_upload(size_t count, Bid *out);
+    bool begin_pass(size_t rows);
+    bool send_pass(size_t n, Bid *out, size_t ptr_at, size_t words);
     uint64_t *alloc_block();
     void free_block(uint64_t *p);
 
     // LUT table on device (catalogue)
     uint64_t *d_luts_ = nullptr;
     DevBuf plan_buf_, batch_in_;
-
-    struct FlushPlan {
-        std::vector<LevelPlan> levels;
-        std::vector<CaptureRec> recs;        // per planned PBS (only filled while capturing)
-        size_t off_desc = 0, off_terms = 0, off_lut = 0, off_out = 0, max_width = 0;
-    } plan_;
 
     // rotation sharing (plan_job): a follower row is a further sample extraction of its leader's blind rotation
     struct ShareRow {
@@ -223,9 +230,11 @@ class Engine {
         std::vector<uint64_t *> out;
         std::vector<uint64_t *> body;     // empty, or per rotation row: where the accumulator's body polynomial goes (leaders)
         std::vector<ShareRow> ext;        // followers of this level's leaders
-        std::vector<CaptureRec> recs;     // per row, only while capturing live (capture_live)
+        std::vector<CaptureRec> recs;     // per row, only while capturing
         uint64_t job = 0;                 // rows of one job that land on the same tick share one TickLevel
     };
+    std::vector<TickLevel> planned_;      // plan_flush: whole levels waiting for exec_level / commit_level
+    size_t planned_max_width_ = 0;
     std::map<uint64_t, std::vector<TickLevel>> sched_;            // tick -> job levels to run in that launch group
     std::map<uint64_t, std::vector<uint64_t *>> free_after_;      // blocks reusable once that tick has been enqueued
     uint64_t next_tick_ = 1, last_sched_tick_ = 0;
@@ -234,9 +243,32 @@ class Engine {
     int auto_flush_rc_ = 0;              // first error of an automatic partial flush, reported by the next flush()
     std::string auto_flush_err_;
     DevBuf tick_buf_;
+    // ---- one launch group (engine.cpp): byte offsets of its packed form in tick_buf_ ----
+    struct GroupView { size_t width = 0, n_ext = 0, off_terms = 0, off_lut = 0, off_out = 0, off_body = 0, off_ext = 0, total = 0; };
+    GroupView pack_group(const TickLevel *levels, size_t n_levels, std::vector<uint8_t> &host) const;
+    int ensure_group_buffers(size_t width, size_t bytes);
+    int upload_group(const TickLevel *levels, size_t n_levels, GroupView &v);
+    int launch_rows(const GroupView &v, size_t lo, size_t cnt, uint64_t *dense_out, const TickLevel *levels, size_t n_levels,
+                    size_t first_level);
+    int sample_capture(const TickLevel &l, size_t first, size_t cnt, size_t batch_row, uint32_t level);
+    int scatter_rows(const uint64_t *d_all, uint64_t *const *d_out, size_t width);
+    void note_level(size_t width);
+    void trace_group(const std::vector<TickLevel> &levels, size_t width);
     // sharded: level-parallel mode -- this rank runs slice [rank*cap, (rank+1)*cap) of the group into the exchange buffer,
     // the slices are all-gathered on the stream and scattered into the nodes' blocks
     int run_tick(std::vector<TickLevel> &levels, bool sharded = false);
+    // ---- the level builder (plan_job and plan_flush) ----
+    using LevelMap = std::map<uint32_t, std::vector<Bid>>;
+    void reset_depth1();
+    LevelMap collect_levels(bool first_level_only);
+    size_t share_level(LevelMap &by_level, LevelMap::iterator lvit, bool first_level_only, std::vector<ShareRow> &followers);
+    void unshare_over_budget(const LevelMap &by_level, LevelMap::const_iterator lvit, bool first_level_only,
+                             std::vector<Bid> &rot, std::vector<Bid> &fol, std::vector<ShareRow> &fmeta);
+    int build_rows(const std::vector<Bid> &lv, size_t R, TickLevel &tl, std::vector<uint64_t> &row_need, bool keep_recs,
+                   uint32_t rec_level);
+    void commit_rows(const std::vector<Bid> &lv, const TickLevel &tl, const std::vector<uint64_t> *row_tick);
+    int schedule_level(TickLevel &tl, const std::vector<Bid> &lv, std::vector<uint64_t> &row_need, uint64_t &tick,
+                       bool stream_pump, size_t next_width);
     // plans the pending PBS level by level; run_now: every level is enqueued as soon as it is planned (the host plans level
     // k + 1 while the GPU runs level k), otherwise the levels are scheduled on ticks (submit)
     // stream_pump (scheduled path only): enqueue every tick as soon as no later level can add rows to it

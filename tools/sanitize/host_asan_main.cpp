@@ -3,6 +3,7 @@
 // engine.cpp graph logic, radix.cpp, strings.cpp, capi_*.cpp -- through a planner context (fhs_ctx_create_planner),
 // which records and levelises every string op of the C ABI without executing anything.
 // Built by `make -C fhestring_amd/csrc asan`; run by tests/test_sanitizers.py.  CPU only.
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -197,6 +198,35 @@ int main() {
         uint64_t c2 = 0;
         CHECK(fhs_char_sum_c2(c, hs[599], &c2) == FHS_OK && c2 == 1);
         for (fhs_char_t h : hs) CHECK(fhs_release(c, h) == FHS_OK);
+    }
+    for (int r = 0; r < 2; r++) {
+        // a compressed upload on the planner (handles only), then the all-at-once plan walked as rank r of 2 would:
+        // fhs_flush_plan builds whole levels with the level builder of every flush, level_exec counts this rank's slice
+        CHECK(fhs_set_mode(c, 1) == FHS_OK && fhs_dist_config(c, r, 2) == FHS_OK);
+        const uint32_t seed[8] = {1, 2, 3, 4, 5, 6, 7, 8};
+        std::vector<uint64_t> bodies(4 * 40, 0);
+        std::vector<fhs_char_t> s(40);
+        CHECK(fhs_upload_string_compressed(c, seed, bodies.data(), 40, 3, s.data()) == FHS_OK);
+        auto p = dummy(c, 3), to = dummy(c, 2);
+        size_t len = 0;
+        std::vector<fhs_char_t> rep(fhs_str_replace_len(s.size(), p.size(), to.size()) + 8);
+        CHECK(fhs_str_replace(c, s.data(), s.size(), p.data(), p.size(), to.data(), to.size(), rep.data(), rep.size(), &len) == FHS_OK);
+        CHECK(fhs_flush(c) == FHS_ERR_STATE);                    // a distributed context is run level by level
+        uint64_t n_levels = 0, max_w = 0, slice[1] = {0}, covered = 0;
+        CHECK(fhs_flush_plan(c, &n_levels, &max_w) == FHS_OK && n_levels > 5 && max_w > 0);
+        fhs_stats before, after;
+        CHECK(fhs_get_stats(c, &before) == FHS_OK);
+        for (uint64_t k = 0; k < n_levels; k++) {
+            uint64_t width = 0, cap = 0;
+            CHECK(fhs_flush_level_exec(c, k, slice, &width, &cap) == FHS_OK && width <= max_w && cap == (width + 1) / 2);
+            covered += width > (uint64_t)r * cap ? std::min(cap, width - (uint64_t)r * cap) : 0;
+            CHECK(fhs_flush_level_commit(c, k, slice) == FHS_OK);
+        }
+        CHECK(fhs_get_stats(c, &after) == FHS_OK && after.pbs_executed - before.pbs_executed == covered &&
+              after.levels - before.levels == n_levels);
+        CHECK(fhs_flush_level_exec(c, 0, slice, &max_w, &max_w) == FHS_ERR_ARG);   // the plan is used up
+        CHECK(fhs_dist_config(c, 0, 1) == FHS_OK && fhs_flush(c) == FHS_OK);
+        for (fhs_char_t h : s) CHECK(fhs_release(c, h) == FHS_OK);
     }
     fhs_stats st;
     // (mostly plaintext strings: counts over repeated flags may pass the budget slightly, tests/test_planner.py)
