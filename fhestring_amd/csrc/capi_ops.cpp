@@ -165,8 +165,7 @@ int fhs_resident_slots(const fhs_ctx *c) {
     if (!c) return FHS_ERR_ARG;
     // ciphertexts the selected blind-rotation kernel works on at a time: 4 workgroups of 2 wavefronts per CU for the
     // f64-FFT kernels (persistent), 2 workgroups of 4 wavefronts per CU for the exact ones
-    const int a = c->eng.ctx.arith;
-    return (a == 1 || a == 2) ? c->eng.ctx.wg_slots : c->eng.ctx.wg_slots / 2;
+    return fhs::is_f64_fft(c->eng.ctx.arith) ? c->eng.ctx.wg_slots : c->eng.ctx.wg_slots / 2;
 }
 
 int fhs_submit(fhs_ctx *c) {

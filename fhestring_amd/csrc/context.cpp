@@ -22,12 +22,14 @@ constexpr size_t BSK_BYTES = (size_t)LWE_N * 4 * POLY_N * sizeof(uint64_t);
 
 hipError_t DevBuf::reserve(size_t bytes) {
     if (bytes <= cap) return hipSuccess;
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-    size_t want = std::max(bytes, (size_t)1 << 20);
-    hipError_t e = hipMalloc(&ptr, want);
-    if (e == hipSuccess) cap = want;
+    return reserve_exact(std::max(bytes, (size_t)1 << 20));
+}
+hipError_t DevBuf::reserve_exact(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    release();
+    hipError_t e = hipMalloc(&ptr, bytes);
+    if (e == hipSuccess) cap = bytes;
+    else ptr = nullptr;
     return e;
 }
 void DevBuf::release() {
@@ -129,52 +131,26 @@ int Context::init(int device_id) {
     // two-bit f64 kernel: one round of resident workgroups per launch (its 73 MB key only stays inside the L2 window
     // while the workgroups walk it together; consecutive launches overlap at the seams): 202 k instead of 183 k PBS/s at
     // 4096 rows, 214 k instead of 152 k at 14 336.  The classic f64 kernel (48 MB key) does not care below 4096 rows.
-    launch_chunk[2] = (size_t)wg_slots;
+    launch_chunk[FHS_ARITH_F64_FFT_MB2] = (size_t)wg_slots;
     // classic f64 kernel (round 5): one round per launch as well.  Time-neutral (default bench 134.5 k PBS/s plain, 135.5 k
     // chunked; 3968-wide launches 30.12 ms plain, 30.33 ms chunked: profiles/r05_chunk_ab.txt) but every launch restarts
     // the key walk of all workgroups together: L2 hit rate 95 -> 98.5 %, fabric-side traffic 6.3 -> 2.4 GB per launch
     // group -- traffic that eight processes on one node would otherwise multiply by eight.  A remainder below a quarter of
     // a round rides in the last launch instead of becoming one of its own (blind_rotate()).
-    launch_chunk[1] = (size_t)wg_slots;
-    HIP_TRY(hipMalloc(&d_work_counter, 64), "hipMalloc counter");
+    launch_chunk[FHS_ARITH_F64_FFT] = (size_t)wg_slots;
+    HIP_TRY(d_work_counter.reserve_exact(64), "hipMalloc counter");
     return 0;
 }
 
 void Context::shutdown() {
     if (stream) (void)hipStreamSynchronize(stream);
     dist.shutdown();
-    xchg_send.release();
-    xchg_recv.release();
     timer.destroy();
-    ms_buf.release();
-    ks_buf.release();
-    in_buf.release();
-    out_buf.release();
-    lutidx_buf.release();
-    tab_buf.release();
-    luts_buf.release();
-    if (d_ksk_planes) (void)hipFree(d_ksk_planes);
-    d_ksk_planes = nullptr;
-    dig_buf.release();
-    if (d_bsk_ntt) (void)hipFree(d_bsk_ntt);
-    if (d_tables) (void)hipFree(d_tables);
-    if (d_work_counter) (void)hipFree(d_work_counter);
-    d_work_counter = nullptr;
-    if (d_bsk_fft) (void)hipFree(d_bsk_fft);
-    if (d_bsk_std) (void)hipFree(d_bsk_std);
-    if (d_bsk_mb) (void)hipFree(d_bsk_mb);
-    d_bsk_mb = nullptr;
-    if (d_bsk_ntt_mb) (void)hipFree(d_bsk_ntt_mb);
-    if (d_pack_key_ntt) (void)hipFree(d_pack_key_ntt);
-    d_pack_key_ntt = nullptr;
-    pack_ws[0].release(); pack_ws[1].release(); pack_tab.release(); pack_out.release();
-    d_bsk_ntt_mb = nullptr;
-    if (d_fft_tables) (void)hipFree(d_fft_tables);
-    d_bsk_fft = nullptr;
-    d_bsk_std = nullptr;
-    d_fft_tables = nullptr;
-    d_bsk_ntt = nullptr;
-    d_tables = nullptr;
+    for (DevBuf *b : {&xchg_send, &xchg_recv, &dig_buf, &ks_buf, &ms_buf, &in_buf, &out_buf, &lutidx_buf, &luts_buf, &tab_buf,
+                      &pack_ws[0], &pack_ws[1], &pack_tab, &pack_out,
+                      &d_ksk_planes, &d_bsk_ntt, &d_tables, &d_bsk_fft, &d_bsk_std, &d_fft_tables, &d_work_counter,
+                      &d_bsk_mb, &d_bsk_ntt_mb, &d_pack_key_ntt})
+        b->release();
     if (stream) (void)hipStreamDestroy(stream);
     stream = nullptr;
 }
@@ -182,18 +158,13 @@ void Context::shutdown() {
 int Context::load_server_key(const uint64_t *bsk, const uint64_t *ksk) {
     if (!bsk || !ksk) return fail(-1, "null key pointer");
     HIP_TRY(hipSetDevice(device), "hipSetDevice");
-    uint64_t *d_ksk = nullptr;
-    HIP_TRY(hipMalloc(&d_ksk, KSK_BYTES), "hipMalloc ksk staging");
-    hipError_t e = hipMemcpy(d_ksk, ksk, KSK_BYTES, hipMemcpyHostToDevice);
-    if (e == hipSuccess && !d_bsk_std) e = hipMalloc(&d_bsk_std, BSK_BYTES);
-    if (e == hipSuccess) e = hipMemcpy(d_bsk_std, bsk, BSK_BYTES, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(d_ksk);
-        return hip_fail(e, "copy server key");
-    }
-    const int rc = install_server_key(bsk, d_ksk);
-    (void)hipFree(d_ksk);
-    return rc;
+    DevBuf d_ksk;
+    HIP_TRY(d_ksk.reserve_exact(KSK_BYTES), "hipMalloc ksk staging");
+    hipError_t e = hipMemcpy(d_ksk.ptr, ksk, KSK_BYTES, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = d_bsk_std.reserve_exact(BSK_BYTES);
+    if (e == hipSuccess) e = hipMemcpy(d_bsk_std.ptr, bsk, BSK_BYTES, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(e, "copy server key");
+    return install_server_key(bsk, d_ksk.as<uint64_t>());
 }
 
 // Compressed server key: the masks are regenerated on the device from the public seed (seeded_kernels.hip) into the
@@ -204,39 +175,36 @@ int Context::load_compressed_server_key(const uint32_t seed[8], const uint64_t *
     SeedKey key;
     for (int i = 0; i < 8; i++) key.w[i] = seed[i];
     const size_t bb = FHS_CBSK_BODY_WORDS * 8, kb = FHS_CKSK_BODY_WORDS * 8;
-    uint64_t *d_ksk = nullptr, *d_bodies = nullptr;
+    DevBuf d_ksk;
     std::vector<uint64_t> bsk((size_t)LWE_N * 4 * POLY_N);
-    hipError_t e = hipMalloc(&d_ksk, KSK_BYTES);
-    if (e == hipSuccess) e = hipMalloc(&d_bodies, bb + kb);
-    if (e == hipSuccess && !d_bsk_std) e = hipMalloc(&d_bsk_std, BSK_BYTES);
-    if (e == hipSuccess) e = hipMemcpy(d_bodies, bsk_bodies, bb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_bodies + FHS_CBSK_BODY_WORDS, ksk_bodies, kb, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_expand_seeded_bsk(key, d_bodies, d_bsk_std, stream);
-    if (e == hipSuccess) e = launch_expand_seeded_ksk(key, d_bodies + FHS_CBSK_BODY_WORDS, d_ksk, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = hipMemcpy(bsk.data(), d_bsk_std, BSK_BYTES, hipMemcpyDeviceToHost);
-    if (d_bodies) (void)hipFree(d_bodies);
-    if (e != hipSuccess) {
-        if (d_ksk) (void)hipFree(d_ksk);
-        return hip_fail(e, "compressed server key expansion");
+    {
+        DevBuf d_bodies;
+        hipError_t e = d_ksk.reserve_exact(KSK_BYTES);
+        if (e == hipSuccess) e = d_bodies.reserve_exact(bb + kb);
+        if (e == hipSuccess) e = d_bsk_std.reserve_exact(BSK_BYTES);
+        uint64_t *const bodies = d_bodies.as<uint64_t>();
+        if (e == hipSuccess) e = hipMemcpy(bodies, bsk_bodies, bb, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(bodies + FHS_CBSK_BODY_WORDS, ksk_bodies, kb, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = launch_expand_seeded_bsk(key, bodies, d_bsk_std.as<uint64_t>(), stream);
+        if (e == hipSuccess) e = launch_expand_seeded_ksk(key, bodies + FHS_CBSK_BODY_WORDS, d_ksk.as<uint64_t>(), stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(stream);
+        if (e == hipSuccess) e = hipMemcpy(bsk.data(), d_bsk_std.ptr, BSK_BYTES, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) return hip_fail(e, "compressed server key expansion");
     }
-    const int rc = install_server_key(bsk.data(), d_ksk);
-    (void)hipFree(d_ksk);
-    return rc;
+    return install_server_key(bsk.data(), d_ksk.as<uint64_t>());
 }
 
 // The shared tail of both key loads: d_bsk_std holds the standard-domain BSK (`bsk`: a host copy of it), d_ksk the KSK.
 int Context::install_server_key(const uint64_t *bsk, const uint64_t *d_ksk) {
-    // a pair key belongs to the server key it was generated with: a new server key invalidates it
-    if (d_bsk_mb) { (void)hipFree(d_bsk_mb); d_bsk_mb = nullptr; }
-    if (d_bsk_ntt_mb) { (void)hipFree(d_bsk_ntt_mb); d_bsk_ntt_mb = nullptr; }
-    if (d_pack_key_ntt) { (void)hipFree(d_pack_key_ntt); d_pack_key_ntt = nullptr; }   // so does the packing key
+    // what was derived from the previous server key, or generated with it, goes with it: the Fourier-domain key (rebuilt
+    // below from the new standard-domain key if an f64-FFT arithmetic is selected, otherwise the first time one is), both
+    // pair keys and the packing key
+    for (DevBuf *b : {&d_bsk_fft, &d_bsk_mb, &d_bsk_ntt_mb, &d_pack_key_ntt}) b->release();
     const size_t bsk_ntt_doubles = (size_t)LWE_N * 4 * 2 * POLY_N;
-    if (!d_bsk_ntt) HIP_TRY(hipMalloc(&d_bsk_ntt, bsk_ntt_doubles * sizeof(double)), "hipMalloc bsk");
+    HIP_TRY(d_bsk_ntt.reserve_exact(bsk_ntt_doubles * sizeof(double)), "hipMalloc bsk");
     {   // the KSK is only kept as byte planes in MFMA fragment order (ks_kernels.hip)
-        hipError_t e = hipSuccess;
-        if (!d_ksk_planes) e = hipMalloc(&d_ksk_planes, ks_planes_bytes());
-        if (e == hipSuccess) e = launch_ksk_to_planes(d_ksk, d_ksk_planes, stream);
+        hipError_t e = d_ksk_planes.reserve_exact(ks_planes_bytes());
+        if (e == hipSuccess) e = launch_ksk_to_planes(d_ksk, d_ksk_planes.as<int8_t>(), stream);
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
         HIP_TRY(e, "ksk -> byte planes");
     }
@@ -244,14 +212,14 @@ int Context::install_server_key(const uint64_t *bsk, const uint64_t *d_ksk) {
         std::vector<double> host(bsk_ntt_doubles);
         unsigned hc = std::thread::hardware_concurrency();
         convert_bsk_to_ntt(bsk, host.data(), (int)std::min(32u, std::max(1u, hc)));
-        HIP_TRY(hipMemcpy(d_bsk_ntt, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice),
+        HIP_TRY(hipMemcpy(d_bsk_ntt.ptr, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice),
                 "copy bsk");
     }
     HostNttTables ht;
     build_ntt_tables(ht);
     const size_t n_tab = ht.fwd_uni.size() + ht.fwd_lane.size() + ht.inv_uni.size() + ht.inv_lane.size() + ht.mono.size();
-    if (!d_tables) HIP_TRY(hipMalloc(&d_tables, n_tab * sizeof(double)), "hipMalloc tables");
-    double *pd = d_tables;
+    HIP_TRY(d_tables.reserve_exact(n_tab * sizeof(double)), "hipMalloc tables");
+    double *pd = d_tables.as<double>();
     auto up = [&](const std::vector<double> &v, const double *&slot) -> hipError_t {
         slot = pd;
         hipError_t e = hipMemcpy(pd, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice);
@@ -273,11 +241,7 @@ int Context::install_server_key(const uint64_t *bsk, const uint64_t *d_ksk) {
     }
     // the standard-domain key stays on the device (48.6 MB of 288 GB): the Fourier-domain key is built from it with the
     // device's own forward transform -- now if the f64 arithmetic is selected, otherwise the first time it is
-    if (d_bsk_fft) {          // a new key invalidates the Fourier-domain form of the old one
-        (void)hipFree(d_bsk_fft);
-        d_bsk_fft = nullptr;
-    }
-    if (arith == 1 || arith == 2)
+    if (is_f64_fft(arith))
         if (int rc = build_fft_key()) return rc;
     key_loaded = true;
     return 0;
@@ -288,30 +252,32 @@ int Context::install_server_key(const uint64_t *bsk, const uint64_t *d_ksk) {
 int Context::build_fft_key() {
     if (!d_bsk_std) return fail(-3, "server key not loaded");
     HIP_TRY(hipSetDevice(device), "hipSetDevice");
-    HostFftTables ft;
-    build_fft_tables(ft);
+    HostFftTables ht;
+    build_fft_tables(ht);
     {   // the kernel's literal twiddles must equal the libm-derived ones
         double wr[16], wi[16], ur[3], ui[3];
         fft_uniform_consts(wr, wi, ur, ui);
         bool ok = true;
-        for (int k = 1; k < 16; k++) ok = ok && wr[k] == ft.w_re[k] && wi[k] == ft.w_im[k];
-        for (int k = 0; k < 3; k++) ok = ok && ur[k] == ft.u_re[k] && ui[k] == ft.u_im[k];
+        for (int k = 1; k < 16; k++) ok = ok && wr[k] == ht.w_re[k] && wi[k] == ht.w_im[k];
+        for (int k = 0; k < 3; k++) ok = ok && ur[k] == ht.u_re[k] && ui[k] == ht.u_im[k];
         if (!ok) return fail(-3, "fft_consts.inc does not match the libm-derived twiddles (regenerate it)");
     }
-    std::vector<double> flat(ft.lanetab);
-    flat.insert(flat.end(), ft.weff.begin(), ft.weff.end());
-    flat.insert(flat.end(), ft.mono.begin(), ft.mono.end());
-    flat.insert(flat.end(), ft.r16.begin(), ft.r16.end());
-    if (!d_fft_tables) HIP_TRY(hipMalloc(&d_fft_tables, flat.size() * sizeof(double)), "hipMalloc fft tables");
-    HIP_TRY(hipMemcpy(d_fft_tables, flat.data(), flat.size() * sizeof(double), hipMemcpyHostToDevice), "copy fft tables");
+    std::vector<double> flat;                      // one upload; every table keeps the pointer to where it landed
+    auto put = [&](const std::vector<double> &v) {
+        const size_t at = flat.size();
+        flat.insert(flat.end(), v.begin(), v.end());
+        return at;
+    };
+    const size_t at_lanetab = put(ht.lanetab), at_weff = put(ht.weff), at_mono = put(ht.mono), at_r16 = put(ht.r16);
+    HIP_TRY(d_fft_tables.reserve_exact(flat.size() * sizeof(double)), "hipMalloc fft tables");
+    HIP_TRY(hipMemcpy(d_fft_tables.ptr, flat.data(), flat.size() * sizeof(double), hipMemcpyHostToDevice), "copy fft tables");
+    const double *const tab = d_fft_tables.as<double>();
+    ft.lanetab = tab + at_lanetab; ft.weff = tab + at_weff; ft.mono = tab + at_mono; ft.r16 = tab + at_r16;
     const size_t n = (size_t)LWE_N * 4 * POLY_N;   // 1024 complex (2048 doubles) per polynomial
-    if (!d_bsk_fft) HIP_TRY(hipMalloc(&d_bsk_fft, n * sizeof(double)), "hipMalloc bsk fft");
-    hipError_t e = launch_bsk_to_fft(d_bsk_std, d_bsk_fft, d_fft_tables, stream);
+    HIP_TRY(d_bsk_fft.reserve_exact(n * sizeof(double)), "hipMalloc bsk fft");
+    hipError_t e = launch_bsk_to_fft(d_bsk_std.as<uint64_t>(), d_bsk_fft.as<double>(), ft.lanetab, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) {
-        (void)hipFree(d_bsk_fft);
-        d_bsk_fft = nullptr;
-    }
+    if (e != hipSuccess) d_bsk_fft.release();      // not loaded
     HIP_TRY(e, "bsk -> Fourier domain");
     return 0;
 }
@@ -322,7 +288,7 @@ int Context::keyswitch(const uint64_t *d_in, size_t B, hipStream_t s) {
         HIP_TRY(dig_buf.reserve(ks_digits_bytes((int)B)), "hipMalloc digits");
     }
     timer.begin(1, B, s);
-    hipError_t e = launch_keyswitch_mfma(d_in, d_ksk_planes, dig_buf.as<int8_t>(), ks_buf.as<uint64_t>(), (int)B, s,
+    hipError_t e = launch_keyswitch_mfma(d_in, d_ksk_planes.as<int8_t>(), dig_buf.as<int8_t>(), ks_buf.as<uint64_t>(), (int)B, s,
                                          wg_slots / 4);
     timer.end(s);
     if (e != hipSuccess) return hip_fail(e, "keyswitch launch");
@@ -330,13 +296,13 @@ int Context::keyswitch(const uint64_t *d_in, size_t B, hipStream_t s) {
 }
 
 int Context::set_arithmetic(int mode) {
-    if (mode < 0 || mode > 3) return fail(-1, "unknown arithmetic mode");
-    if ((mode == 1 || mode == 2) && key_loaded && !d_bsk_fft)      // the key was loaded under the exact arithmetic: build
+    if (mode < 0 || mode >= N_ARITH) return fail(-1, "unknown arithmetic mode");
+    if (is_f64_fft(mode) && key_loaded && !d_bsk_fft)              // the key was loaded under the exact arithmetic: build
         if (int rc = build_fft_key()) return rc;                   // its Fourier-domain form now (either order works)
-    if (mode == 2 && key_loaded && !d_bsk_mb)
+    if (mode == FHS_ARITH_F64_FFT_MB2 && key_loaded && !d_bsk_mb)
         return fail(-3, "the two-bits-per-product arithmetic needs the pair key in the Fourier domain: call "
                         "fhs_load_multibit_key while arithmetic 1 (f64 FFT) is selected, then fhs_set_arithmetic 2");
-    if (mode == 3 && key_loaded && !d_bsk_ntt_mb)
+    if (mode == FHS_ARITH_EXACT_NTT_MB2 && key_loaded && !d_bsk_ntt_mb)
         return fail(-3, "the exact two-bits-per-product arithmetic needs the pair key converted to residues: call "
                         "fhs_load_multibit_key while the EXACT arithmetic (fhs_set_arithmetic 0) is selected, then "
                         "fhs_set_arithmetic 3");
@@ -350,15 +316,15 @@ int Context::load_multibit_key(const uint64_t *bsk_mb2) {
     if (!bsk_mb2) return fail(-1, "null key pointer");
     if (!key_loaded) return fail(-3, "load the server key before the pair key");
     HIP_TRY(hipSetDevice(device), "hipSetDevice");
-    if (arith == 0 || arith == 3) {
+    if (!is_f64_fft(arith)) {
         // exact arithmetic: residues of the pair key modulo the two NTT primes, on the 57-bit torus grid (nttmb_kernels.hip)
         if (!ntt_slot_roots_are_bitreversed()) return fail(-3, "internal: NTT slot order is not bit-reversed");
         const size_t n_d = (size_t)(LWE_N / 2) * 3 * 4 * 2 * POLY_N;
         std::vector<double> host(n_d);
         unsigned hc = std::thread::hardware_concurrency();
         convert_bsk_to_ntt(bsk_mb2, host.data(), (int)std::min(32u, std::max(1u, hc)), (LWE_N / 2) * 3, 7);
-        if (!d_bsk_ntt_mb) HIP_TRY(hipMalloc(&d_bsk_ntt_mb, n_d * sizeof(double)), "hipMalloc pair key (NTT)");
-        HIP_TRY(hipMemcpy(d_bsk_ntt_mb, host.data(), n_d * sizeof(double), hipMemcpyHostToDevice), "copy pair key");
+        HIP_TRY(d_bsk_ntt_mb.reserve_exact(n_d * sizeof(double)), "hipMalloc pair key (NTT)");
+        HIP_TRY(hipMemcpy(d_bsk_ntt_mb.ptr, host.data(), n_d * sizeof(double), hipMemcpyHostToDevice), "copy pair key");
         HIP_TRY(prepare_device_for_ntt_mb2(), "kernel attributes");
         return 0;
     }
@@ -366,14 +332,12 @@ int Context::load_multibit_key(const uint64_t *bsk_mb2) {
         return fail(-3, "load the server key in an f64-FFT arithmetic (fhs_set_arithmetic 1 or 2) before the pair key");
     const int n_polys = (LWE_N / 2) * 3 * 4;
     const size_t n = (size_t)n_polys * POLY_N;            // u64 in, doubles out (1024 complex per polynomial)
-    uint64_t *d_std = nullptr;
-    HIP_TRY(hipMalloc(&d_std, n * sizeof(uint64_t)), "hipMalloc pair key staging");
-    hipError_t e = hipSuccess;
-    if (!d_bsk_mb) e = hipMalloc(&d_bsk_mb, n * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpy(d_std, bsk_mb2, n * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_bsk_to_fft(d_std, d_bsk_mb, d_fft_tables, stream, n_polys);
+    DevBuf d_std;
+    HIP_TRY(d_std.reserve_exact(n * sizeof(uint64_t)), "hipMalloc pair key staging");
+    hipError_t e = d_bsk_mb.reserve_exact(n * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(d_std.ptr, bsk_mb2, n * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_bsk_to_fft(d_std.as<uint64_t>(), d_bsk_mb.as<double>(), ft.lanetab, stream, n_polys);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    (void)hipFree(d_std);
     HIP_TRY(e, "pair key -> Fourier domain");
     return 0;
 }
@@ -390,8 +354,8 @@ int Context::load_packing_key(const uint64_t *key) {
     std::vector<double> host(n_d);
     convert_polys_to_ntt(key, host.data(), 11, PACK_KEY_POLYS, BSK_QUANT_BITS);
     HIP_TRY(hipStreamSynchronize(stream), "stream sync");     // a queued packing may still read the previous key
-    if (!d_pack_key_ntt) HIP_TRY(hipMalloc(&d_pack_key_ntt, n_d * sizeof(double)), "hipMalloc packing key");
-    HIP_TRY(hipMemcpy(d_pack_key_ntt, host.data(), n_d * sizeof(double), hipMemcpyHostToDevice), "copy packing key");
+    HIP_TRY(d_pack_key_ntt.reserve_exact(n_d * sizeof(double)), "hipMalloc packing key");
+    HIP_TRY(hipMemcpy(d_pack_key_ntt.ptr, host.data(), n_d * sizeof(double), hipMemcpyHostToDevice), "copy packing key");
     HIP_TRY(prepare_device_for_packing(), "kernel attributes");
     return 0;
 }
@@ -399,10 +363,11 @@ int Context::load_packing_key(const uint64_t *key) {
 int Context::blind_rotate(const uint64_t *d_ks, const uint32_t *d_lut_idx, const uint64_t *d_luts, uint64_t *d_out,
                           uint64_t *const *d_out_ptrs, size_t B, hipStream_t s, uint64_t *const *d_body_ptrs) {
     hipError_t e = hipSuccess;
-    const bool four = arith == 1 && B <= (size_t)fft4_max_batch;
-    if (arith == 2 && !d_bsk_mb) return fail(-3, "pair key not loaded (fhs_load_multibit_key)");
-    if (arith == 3 && !d_bsk_ntt_mb) return fail(-3, "pair key not loaded in the exact arithmetic (fhs_load_multibit_key)");
-    if (arith == 1 && !d_bsk_fft) return fail(-3, "Fourier-domain key not loaded");
+    const bool four = arith == FHS_ARITH_F64_FFT && B <= (size_t)fft4_max_batch;
+    if (arith == FHS_ARITH_F64_FFT_MB2 && !d_bsk_mb) return fail(-3, "pair key not loaded (fhs_load_multibit_key)");
+    if (arith == FHS_ARITH_EXACT_NTT_MB2 && !d_bsk_ntt_mb)
+        return fail(-3, "pair key not loaded in the exact arithmetic (fhs_load_multibit_key)");
+    if (arith == FHS_ARITH_F64_FFT && !d_bsk_fft) return fail(-3, "Fourier-domain key not loaded");
     timer.begin(four ? 2 : 0, B, s);
     // A launch is cut into chunks of launch_chunk[arith] ciphertexts (0 = whole batch): every chunk starts all workgroups on
     // the first key element together again.  The kernels whose key does not fit the L2 window of a drifting launch need
@@ -420,37 +385,34 @@ int Context::blind_rotate(const uint64_t *d_ks, const uint32_t *d_lut_idx, const
         uint64_t *out = d_out ? d_out + off * BIG_CT : nullptr;
         uint64_t *const *outp = d_out_ptrs ? d_out_ptrs + off : nullptr;
         uint64_t *const *bodyp = d_body_ptrs ? d_body_ptrs + off : nullptr;   // rotation sharing (engine.cpp)
-        if (arith == 3) {
+        if (arith == FHS_ARITH_EXACT_NTT_MB2) {
             BlindRotateNttMb2Params p{};
             p.ks = ks; p.lut_idx = li; p.luts = d_luts;
-            p.bsk_ntt_mb = d_bsk_ntt_mb; p.tw = tw; p.crt_c = crt_c; p.mono = d_ntt_mono;
+            p.bsk_ntt_mb = d_bsk_ntt_mb.as<double>(); p.tw = tw; p.crt_c = crt_c; p.mono = d_ntt_mono;
             p.out = out; p.out_ptrs = outp; p.body_ptrs = bodyp; p.B = (int)n;
             e = launch_blind_rotate_ntt_mb2(p, s);
-        } else if (arith == 2) {
+        } else if (arith == FHS_ARITH_F64_FFT_MB2) {
             BlindRotateMb2Params p{};
             p.ks = ks; p.lut_idx = li; p.luts = d_luts;
-            p.bsk_mb = d_bsk_mb;
-            p.lanetab = d_fft_tables;
-            p.mono = d_fft_tables + 12 * 64 + 2 * 1024;
-            p.r16 = p.mono + 2 * 4096;
-            p.work_counter = d_work_counter;
+            p.bsk_mb = d_bsk_mb.as<double>();
+            p.lanetab = ft.lanetab; p.mono = ft.mono; p.r16 = ft.r16;
+            p.work_counter = d_work_counter.as<uint32_t>();
             p.slots = wg_slots;
             p.out = out; p.out_ptrs = outp; p.body_ptrs = bodyp; p.B = (int)n;
             e = launch_blind_rotate_mb2(p, s);
-        } else if (arith == 1) {
+        } else if (arith == FHS_ARITH_F64_FFT) {
             BlindRotateFftParams p{};
             p.ks = ks; p.lut_idx = li; p.luts = d_luts;
-            p.bsk_fft = d_bsk_fft;
-            p.lanetab = d_fft_tables;
-            p.weff = d_fft_tables + 12 * 64;
-            p.work_counter = d_work_counter;
+            p.bsk_fft = d_bsk_fft.as<double>();
+            p.lanetab = ft.lanetab; p.weff = ft.weff;
+            p.work_counter = d_work_counter.as<uint32_t>();
             p.slots = wg_slots;
             p.out = out; p.out_ptrs = outp; p.body_ptrs = bodyp; p.B = (int)n;
             e = four ? launch_blind_rotate_fft4(p, s) : launch_blind_rotate_fft(p, s);
         } else {
             BlindRotateParams p{};
             p.ks = ks; p.lut_idx = li; p.luts = d_luts;
-            p.bsk_ntt = d_bsk_ntt; p.tw = tw; p.crt_c = crt_c;
+            p.bsk_ntt = d_bsk_ntt.as<double>(); p.tw = tw; p.crt_c = crt_c;
             p.out = out; p.out_ptrs = outp; p.body_ptrs = bodyp; p.B = (int)n;
             e = launch_blind_rotate(p, s);
         }

@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/fhestring_hip.h"
 #include "dist.h"
 #include "fft_tables.h"
 #include "ntt_tables.h"
@@ -13,13 +14,32 @@
 
 namespace fhs {
 
-// grow-only device buffer
+// owner of one device allocation, grow-only.  A buffer that never reserved (or was released) holds nothing and its
+// destructor makes no HIP call.
 struct DevBuf {
     void *ptr = nullptr;
     size_t cap = 0;
-    hipError_t reserve(size_t bytes);
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { release(); }
+    hipError_t reserve(size_t bytes);         // scratch: at least 1 MB, so that a growing batch does not reallocate often
+    hipError_t reserve_exact(size_t bytes);   // key material, tables, the work counter: fixed sizes
     void release();
+    explicit operator bool() const { return ptr != nullptr; }
     template <class T> T *as() const { return reinterpret_cast<T *>(ptr); }
+};
+
+// the arithmetics fhs_set_arithmetic selects (FHS_ARITH_*, include/fhestring_hip.h)
+constexpr int N_ARITH = 4;
+constexpr bool is_f64_fft(int arith) { return arith == FHS_ARITH_F64_FFT || arith == FHS_ARITH_F64_FFT_MB2; }
+
+// where build_fft_key() put the f64-FFT tables inside Context::d_fft_tables
+struct FftTablePtrs {
+    const double *lanetab = nullptr;   // [12][64]
+    const double *weff = nullptr;      // [1024][2]
+    const double *mono = nullptr;      // [4096][2]
+    const double *r16 = nullptr;       // [16][2]
 };
 
 // HIP-event timing of the two PBS kernels on the stream they are launched on
@@ -49,31 +69,33 @@ class Context {
     std::string err;
     bool key_loaded = false;
 
-    // key material on device
-    int8_t *d_ksk_planes = nullptr;  // KSK as 8 byte planes in MFMA fragment order (ks_kernels.hip)
-    double *d_bsk_ntt = nullptr;
-    double *d_tables = nullptr;   // fwd_uni | fwd_lane | inv_uni | inv_lane
-    NttTables tw{};
+    // key material on device: every allocation has one owner, and a key is loaded exactly when its owner holds memory
+    DevBuf d_ksk_planes;             // int8: KSK as 8 byte planes in MFMA fragment order (ks_kernels.hip)
+    DevBuf d_bsk_ntt;                // double
+    DevBuf d_tables;                 // double: fwd_uni | fwd_lane | inv_uni | inv_lane | mono
+    NttTables tw{};                  // ... and where they landed
     double crt_c = 0;
 
-    // optional f64-FFT arithmetic (fft_kernels.hip): 0 = exact two-prime NTT (default), 1 = f64 FFT.
-    // Select before load_server_key: the Fourier-domain key is only built when the mode asks for it.
-    int arith = 0;
-    double *d_bsk_fft = nullptr;
-    uint64_t *d_bsk_std = nullptr;   // standard-domain key, kept for a later conversion to the Fourier domain (build_fft_key)
-    double *d_fft_tables = nullptr;   // lanetab[12][64] | weff[1024][2] | mono[4096][2] | r16[16][2]
-    uint32_t *d_work_counter = nullptr;   // persistent-workgroup ciphertext counter of the 2-wavefront FFT kernel
+    // the selected arithmetic, FHS_ARITH_* (default: exact two-prime NTT).  The server key may be loaded before or after
+    // an f64-FFT arithmetic is selected: the Fourier-domain key is built from the retained standard-domain key by whichever
+    // comes second (install_server_key / set_arithmetic -> build_fft_key).
+    int arith = FHS_ARITH_EXACT_NTT;
+    DevBuf d_bsk_fft;                // double: Fourier-domain key of FHS_ARITH_F64_FFT (fft_kernels.hip, fft4_kernels.hip)
+    DevBuf d_bsk_std;                // uint64: standard-domain key, kept for a later conversion to the Fourier domain
+    DevBuf d_fft_tables;             // double: lanetab | weff | mono | r16
+    FftTablePtrs ft;                 // ... and where they landed
+    DevBuf d_work_counter;           // uint32: persistent-workgroup ciphertext counter of the 2-wavefront FFT kernel (64 B)
     int wg_slots = 1024;                  // 4 workgroups per CU
-    // arith 2 (FHS_ARITH_F64_FFT_MB2): two key bits per external product (fftmb_kernels.hip); needs the pair key
-    double *d_bsk_mb = nullptr;       // [371][K1,K2,K3][4][1024] complex
-    double *d_bsk_ntt_mb = nullptr;   // arith 3 (FHS_ARITH_EXACT_NTT_MB2): [371][K1,K2,K3][4][2 primes][2048] residues
+    // pair keys of the two-key-bits-per-product arithmetics; they belong to the server key they were generated with
+    DevBuf d_bsk_mb;                 // double, FHS_ARITH_F64_FFT_MB2 (fftmb_kernels.hip): [371][K1,K2,K3][4][1024] complex
+    DevBuf d_bsk_ntt_mb;             // double, FHS_ARITH_EXACT_NTT_MB2: [371][K1,K2,K3][4][2 primes][2048] residues
     const double *d_ntt_mono = nullptr;   // [2][4096] inside d_tables
     // packed result download (pack_kernels.hip): the 11 automorphism keyswitch keys as residues modulo the two NTT primes
-    double *d_pack_key_ntt = nullptr;   // [11][3][2 cols][2 primes][2048]
+    DevBuf d_pack_key_ntt;           // double: [11][3][2 cols][2 primes][2048]
     int load_packing_key(const uint64_t *key);   // [FHS_PACK_KEY_WORDS] u64 standard domain (fhs_client_packing_key)
     int load_multibit_key(const uint64_t *bsk_mb2);   // [371][K1,K2,K3][4][2048] u64 standard domain (fhs_client_bsk_mb2)
-    int fft4_max_batch = 512;
-    size_t launch_chunk[4] = {0, 0, 0, 0};   // per arithmetic: ciphertexts per blind-rotation launch (0 = whole batch)         // batches up to this size use the 4-wavefront kernel (lower latency)
+    int fft4_max_batch = 512;                // batches up to this size use the 4-wavefront kernel (lower latency)
+    size_t launch_chunk[N_ARITH] = {};       // per arithmetic: ciphertexts per blind-rotation launch (0 = whole batch)
     int set_arithmetic(int mode);
     // keyswitch of a dense batch into ks_buf (timed as kernel kind 1); ks_buf must hold B rows
     int keyswitch(const uint64_t *d_in, size_t B, hipStream_t s);

@@ -1472,7 +1472,7 @@ int Engine::read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *
             p.leaves = ctx.pack_tab.as<PackLeaf>();
             p.src = ctx.pack_ws[lv & 1].as<uint64_t>();
             p.dst = ctx.pack_ws[(lv - 1) & 1].as<uint64_t>();
-            p.key_ntt = ctx.d_pack_key_ntt; p.tw = ctx.tw;
+            p.key_ntt = ctx.d_pack_key_ntt.as<double>(); p.tw = ctx.tw;
             e = launch_pack_level(p, ctx.stream);
         }
         uint16_t *d_mask = ctx.pack_out.as<uint16_t>(), *d_body = d_mask + groups * PACK_GROUP;

@@ -43,10 +43,11 @@ def test_bench_gpus_2_without_a_launcher_starts_two_ranks():
 
 
 def test_roofline_counters_are_tied_to_the_kernel_sources():
-    """profiles/r05_counters.json carries the git blob hashes of the sources each kernel was counted
+    """profiles/r*_counters.json carry the git blob hashes of the sources each kernel was counted
     on (fhestring_amd/kernel_sources.py computes them without git); bench.py withholds the counted figures for a kernel
     whose sources have moved on.  Here: the hash IS git's, the committed counters describe THIS tree for every
-    blind-rotation kernel, and a changed byte is noticed."""
+    blind-rotation kernel, and a changed byte is noticed.  Each kernel's entry is the one bench.py's load_counters()
+    uses: r02 ... r06 in order, a later file overriding an earlier one."""
     import json
     import subprocess
     from fhestring_amd import kernel_sources as ks
@@ -56,7 +57,9 @@ def test_roofline_counters_are_tied_to_the_kernel_sources():
         assert ks.blob_hash(open(path, "rb").read()) == want
     except (OSError, subprocess.CalledProcessError):
         pass                                                  # no git here: the hash function is still exercised below
-    counters = json.load(open(os.path.join(ROOT, "profiles", "r05_counters.json")))
+    counters = {}
+    for rnd in ("r02", "r03", "r04", "r05", "r06"):
+        counters.update(json.load(open(os.path.join(ROOT, "profiles", rnd + "_counters.json"))))
     import warnings
     for kernel in ("blind_rotate_fft_kernel", "blind_rotate_kernel", "blind_rotate_mb2_kernel",
                    "blind_rotate_ntt_mb2_kernel", "blind_rotate_fft4_kernel"):

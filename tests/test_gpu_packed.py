@@ -173,3 +173,38 @@ def test_states_and_key_file(ck, tmp_path):
         assert e.value.code == FHS_ERR_STATE
     finally:
         sk.close()
+
+
+def test_a_second_server_key_takes_everything_derived_from_the_first_with_it(ck):
+    """Reload on a context in the f64-FFT arithmetic that holds the pair key and the packing key of the first client: the
+    Fourier-domain key is rebuilt from the NEW standard-domain key (two bootstraps, the smallest batch with a non-trivial
+    pointer offset, decrypt under the second client's key), the pair key and the packing key are gone, close() is clean."""
+    import noise_util as nu
+    from fhestring_amd.api import FhsError, MyClientKey
+    from oracle import radix
+    ck2 = MyClientKey(4243)
+    sk = _server(ck, 1)
+    try:
+        ctx = sk.ctx
+        ctx.load_multibit_key(ck.bsk_mb2())
+        ctx.set_arithmetic(ctx.ARITH_F64_FFT_MB2)                                 # the pair key is there ...
+        ctx.set_arithmetic(ctx.ARITH_F64_FFT)
+        s = sk.upload_string(ck.encrypt_str_raw("ab", 0))
+        assert ck.decrypt_packed(sk.download_packed(s)) == "ab"                   # ... and so is the packing key
+        ctx.load_server_key(ck2.bsk(), ck2.ksk())
+        msgs = np.array([1, 2], np.uint64)
+        cts = np.stack([ck2.encrypt_char_raw(int(m))[0] for m in msgs])           # block 0 of the char = m & 3
+        got = ctx.pbs_batch(cts, np.zeros(2, np.uint32), radix.lut_poly("msg")[None, :])
+        _, glwe_sk2 = ck2.secret_keys()
+        e = nu.centred(nu.big_phase(got, glwe_sk2) - (msgs << np.uint64(59)), 64)
+        assert np.abs(e).max() < 2 ** 53, np.abs(e)                               # 1/64 of a message step, as test_gpu_margins
+        with pytest.raises(FhsError, match="pair key") as err:
+            ctx.set_arithmetic(ctx.ARITH_F64_FFT_MB2)
+        assert err.value.code == FHS_ERR_STATE and ctx.arithmetic == ctx.ARITH_F64_FFT
+        with pytest.raises(FhsError) as err:
+            sk.download_packed(s)
+        assert err.value.code == FHS_ERR_STATE
+    finally:
+        sk.close()
+        ck2.close()
+    assert sk.ctx._h is None

@@ -2,8 +2,9 @@
 
     python tools/fft4_timeline.py build           # here (no GPU, needs .git): ablations of the ROUND-5 kernel (git show R5_REV)
     python tools/fft4_timeline.py run [B ...]     # on the GPU box: default B = 64 256
-    python tools/fft4_timeline.py build_ab        # here: A/B builds of the round-6 remedies + the stamped build, current source
-    python tools/fft4_timeline.py run_ab [B ...]  # on the GPU box
+    python tools/fft4_timeline.py build_ab        # here (needs .git): A/B builds of the round-6 remedies (git show R6_REV),
+                                                  # the product kernel (ab_all) and the product kernel with stamps (ab_timeline)
+    python tools/fft4_timeline.py run_ab [B ...] [variant ...]  # on the GPU box
 
 Two instruments on copies of csrc/fft4_kernels.hip (TIMING ONLY; the product library is never touched):
 
@@ -23,6 +24,7 @@ SRC = os.path.join(ROOT, "fhestring_amd", "csrc")
 OUT = os.path.join(ROOT, "tools", "ablate_build")
 TL_ITER0, TL_ITERS, TL_STAMPS, TL_MAXB = 300, 32, 12, 256
 R5_REV = "bd97dce"           # the kernel the ablations (and profiles/r06_fft4_timeline_before.txt) describe
+R6_REV = "3d74b38"           # the last revision whose kernel carries the FFT4_* switches (profiles/r06_fft4_ab_timeline.txt)
 SEGMENTS_R5 = ["top -> barrier 1 passed (staged accumulator visible)",
                "rotated reads + subtract + decompose",
                "exchange write -> barrier 2 passed",
@@ -135,21 +137,55 @@ def build():
         print("built", name, flush=True)
 
 
+# the retired variants: the kernel of R6_REV under its own switches
 AB = {"ab_neither": ["-DFFT4_OVERLAP=0", "-DFFT4_HB_WIDE=2"], "ab_keys_early": ["-DFFT4_OVERLAP=0", "-DFFT4_KEY_SPREAD=0"],
       "ab_overlap": ["-DFFT4_OVERLAP=2", "-DFFT4_HB_WIDE=2"], "ab_overlap_keys_early": ["-DFFT4_KEY_SPREAD=0"],
       "ab_keys_spread": ["-DFFT4_OVERLAP=0"], "ab_overlap1_keys_spread": ["-DFFT4_OVERLAP=1"], "ab_reg_t1": ["-DFFT4_REG_T1=1"], "ab_xchg_f64": ["-DFFT4_XCHG_I32=0"],
-      "ab_reg_t1_t2": ["-DFFT4_REG_T1=1", "-DFFT4_REG_T2=1"], "ab_all": [],
-      "ab_timeline": ["-DFFT4_TIMELINE"]}
+      "ab_reg_t1_t2": ["-DFFT4_REG_T1=1", "-DFFT4_REG_T2=1"]}
+# the twelve stamps on the product kernel (ab_timeline): (anchor, k) puts TL(k) in front of the anchor, (anchor, k, True)
+# behind it; stamp 0 comes with TL_TOP
+TL_NOW = [
+    ("        // ---- rotate, subtract, decompose: z[r] = digit(k(r)) + i digit(k(r) + 1024) -", 0),
+    ("        __syncthreads();                              // staged accumulator of both halves visible\n", 1, True),
+    ("        if (!WIDE) __syncthreads();                   // all rotated reads done before the area is reused\n", 2),
+    ("            // all 8 partner points requested first", 3),
+    ("        wide_requests_key_chunk(1);\n", 4),
+    ("        // ---- last forward stage + publish, pointwise multiply-accumulate with GGSW_i -", 5),
+    ("        __builtin_amdgcn_s_setprio(2);\n", 6),
+    ("        // ---- inverse transform -", 7),
+    ("        stagesA_head<true>(z, w2, w4, w8);\n", 8),
+    ("            cplx o[8];\n#pragma unroll\n            for (int r = 0; r < 8; r++) o[r] = pair[pslot(lane + 64 * r)];\n", 9),
+    ("        // ---- back to the torus, update and restage the accumulator -", 10),
+    ("            if (r == 7 && h == 1) stage[lane] = acc[15];\n        }\n", 11, True),
+]
+
+
+def stamped(text):
+    """the product kernel with TL_HEAD and the twelve stamps; a drifted anchor fails here, at build time"""
+    head = '#include "fft_device.h"\n'
+    assert text.count(head) == 1, head
+    t = text.replace(head, head + TL_HEAD)
+    for anchor, k, *after in TL_NOW:
+        assert t.count(anchor) == 1, (k, t.count(anchor), anchor)
+        stamp = TL_TOP if k == 0 else "        TL(%d);\n" % k
+        t = t.replace(anchor, anchor + stamp if after else stamp + anchor)
+    return t
 
 
 def build_ab():
-    """A/B of the two round-6 remedies through their macros (csrc/fft4_kernels.hip): bit-identical results by construction"""
+    """ab_all: csrc/fft4_kernels.hip as it is; ab_timeline: the same with stamps; every other variant: the kernel of R6_REV
+    under its own switches (bit-identical results by construction, same digest)"""
     os.makedirs(OUT, exist_ok=True)
     objs = [os.path.join(SRC, f) for f in os.listdir(SRC) if f.endswith(".o") and f != "fft4_kernels.o"]
-    for name, flags in AB.items():
-        obj = os.path.join(OUT, "fft4_kernels_%s.o" % name)
+    product = open(os.path.join(SRC, "fft4_kernels.hip")).read()
+    r6 = subprocess.check_output(["git", "-C", ROOT, "show", R6_REV + ":fhestring_amd/csrc/fft4_kernels.hip"], text=True)
+    variants = [(name, r6, flags) for name, flags in AB.items()] + [("ab_all", product, []), ("ab_timeline", stamped(product), [])]
+    for name, text, flags in variants:
+        src = os.path.join(OUT, "fft4_kernels_%s.hip" % name)
+        open(src, "w").write(text)
+        obj = src.replace(".hip", ".o")
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I", SRC,
-                               "-Wno-unused-function", "-c", os.path.join(SRC, "fft4_kernels.hip"), "-o", obj] + flags)
+                               "-Wno-unused-function", "-c", src, "-o", obj] + flags)
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o",
                                os.path.join(OUT, "libfhs_fft4_%s.so" % name), obj] + objs + ["-lpthread", "-ldl"])
         os.remove(obj)
@@ -206,14 +242,22 @@ def worker(B):
 
 
 def run(sizes, names=None):
+    """one child process per variant and size, each under its own time limit; the first one that fails or runs out of
+    time ends the visit: nothing more is started on a GPU that may have faulted"""
     for B in sizes:
         for name in (names or V):
             lib = os.path.join(OUT, "libfhs_fft4_%s.so" % name)
             env = dict(os.environ, FHS_LIB_PATH=lib)
-            p = subprocess.run([sys.executable, os.path.abspath(__file__), "worker", str(B)], capture_output=True, text=True,
-                               env=env, cwd=ROOT, timeout=300)
+            try:
+                p = subprocess.run([sys.executable, os.path.abspath(__file__), "worker", str(B)], capture_output=True, text=True,
+                                   env=env, cwd=ROOT, timeout=300)
+            except subprocess.TimeoutExpired:
+                sys.exit("%-12s B=%d TIMED OUT after 300 s: stopped, the remaining variants were not run" % (name, B))
+            if p.returncode != 0:
+                sys.exit("%-12s B=%d FAILED (exit status %d): stopped, the remaining variants were not run\n%s"
+                         % (name, B, p.returncode, p.stderr[-400:]))
             out = [l for l in p.stdout.splitlines() if l.startswith(("B=", "TIMELINE", "  "))]
-            print("%-12s %s" % (name, "\n".join(out) if out else ("FAILED " + p.stderr[-400:])), flush=True)
+            print("%-12s %s" % (name, "\n".join(out)), flush=True)
 
 
 if __name__ == "__main__":
@@ -222,7 +266,10 @@ if __name__ == "__main__":
     elif sys.argv[1] == "build_ab":
         build_ab()
     elif sys.argv[1] == "run_ab":
-        run([int(a) for a in sys.argv[2:]] or [8, 64, 256, 300, 512], list(AB))
+        every = list(AB) + ["ab_all", "ab_timeline"]
+        names = [a for a in sys.argv[2:] if not a.isdigit()]
+        assert all(n in every for n in names), "variants: " + " ".join(every)
+        run([int(a) for a in sys.argv[2:] if a.isdigit()] or [8, 64, 256, 300, 512], names or every)
     elif sys.argv[1] == "worker":
         worker(int(sys.argv[2]))
     else:
