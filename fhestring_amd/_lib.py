@@ -392,6 +392,23 @@ def _declare(L):
     L.fhs_client_decrypt_packed_blocks.restype = i
     L.fhs_client_encrypt_blocks.argtypes = [vp, vp, sz, vp]
     L.fhs_client_encrypt_blocks.restype = i
+    # device-resident string store
+    L.fhs_store_put.argtypes = [vp, vp, sz, u64p]
+    L.fhs_store_put.restype = i
+    L.fhs_store_get.argtypes = [vp, u64, sz, sz, vp]
+    L.fhs_store_get.restype = i
+    L.fhs_store_drop.argtypes = [vp, u64]
+    L.fhs_store_drop.restype = i
+    L.fhs_store_info.argtypes = [vp, u64, C.POINTER(sz), C.POINTER(sz)]
+    L.fhs_store_info.restype = i
+    L.fhs_store_stats.argtypes = [vp, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]
+    L.fhs_store_stats.restype = i
+    L.fhs_store_export.argtypes = [vp, u64, vp, vp, vp]
+    L.fhs_store_export.restype = i
+    L.fhs_store_import.argtypes = [vp, vp, vp, vp, sz, u64p]
+    L.fhs_store_import.restype = i
+    L.fhs_pack_switch32.argtypes = [vp, vp, sz, vp, vp]
+    L.fhs_pack_switch32.restype = i
 
 
 class CaptureRec(C.Structure):

@@ -752,6 +752,88 @@ def pack_switch16(mask64, body64, n_blocks):
     return PackedFheString(n_blocks // 4, mask16, body16) if n_blocks % 4 == 0 else (mask16, body16)
 
 
+def pack_switch32(mask64, body64, n_blocks):
+    """fhs_pack_switch32: the string store's storage switch on the host, (x + 2^31) >> 32 -> CompactFheString (n_blocks a
+    multiple of 4) or, for any other block count, the raw (mask32, body32)."""
+    mask64 = np.ascontiguousarray(mask64, np.uint64)
+    body64 = np.ascontiguousarray(body64, np.uint64)
+    g = (n_blocks + PACK_GROUP - 1) // PACK_GROUP
+    assert mask64.size == g * POLY_N and body64.size == g * POLY_N
+    mask32, body32 = np.zeros((g, POLY_N), np.uint32), np.zeros(n_blocks, np.uint32)
+    if lib().fhs_pack_switch32(_ptr(mask64), _ptr(body64), n_blocks, _ptr(mask32), _ptr(body32)) != 0:
+        raise FhsError("fhs_pack_switch32 failed")
+    return CompactFheString(n_blocks // 4, mask32, body32) if n_blocks % 4 == 0 else (mask32, body32)
+
+
+STORE_MAX_CYCLES = 16          # FHS_STORE_MAX_CYCLES
+STORE_META_MAGIC = b"FHSSMET1"
+
+
+def store_meta_word(var=1, cycles=0, group=0):
+    """One meta word of fhs_store_export / fhs_store_import: bits 0-15 the noise figure, 16-23 the packing cycles,
+    32-63 the entry-local rotation group (0 = none)."""
+    return np.uint64(int(var) | int(cycles) << 16 | int(group) << 32)
+
+
+def store_export_to_bytes(compact, meta):
+    """Serialised form of an exported entry: the CompactFheString bytes, then magic FHSSMET1, n (u64) and 4n meta words."""
+    meta = np.ascontiguousarray(meta, np.uint64).reshape(-1)
+    assert meta.size == 4 * len(compact)
+    return compact.to_bytes() + STORE_META_MAGIC + np.uint64(len(compact)).tobytes() + meta.tobytes()
+
+
+def store_export_from_bytes(data):
+    """-> (CompactFheString, meta[4n]) of store_export_to_bytes."""
+    data = bytes(data)
+    if data[:8] != CompactFheString.MAGIC or len(data) < 16:
+        raise ValueError("not an exported store entry")
+    n = int(np.frombuffer(data, np.uint64, 1, 8)[0])
+    cut = 16 + 8192 * ((4 * n + 2047) // 2048) + 16 * n
+    if n > (1 << 24) or len(data) != cut + 16 + 32 * n or data[cut:cut + 8] != STORE_META_MAGIC or \
+            int(np.frombuffer(data, np.uint64, 1, cut + 8)[0]) != n:
+        raise ValueError("exported store entry of %d characters: wrong size or meta header" % n)
+    return CompactFheString.from_bytes(data[:cut]), np.frombuffer(data, np.uint64, 4 * n, cut + 16).copy()
+
+
+class StoredString:
+    """One entry of a context's device-resident string store (include/fhestring_hip.h): the string parked in HBM in the
+    compact format, 34 B per character, read back whole or by window with get()."""
+
+    def __init__(self, sk, entry_id):
+        self.sk, self.id = sk, int(entry_id)
+
+    def _info(self):
+        n, b = C.c_size_t(), C.c_size_t()
+        self.sk.ctx._check(self.sk.ctx._L.fhs_store_info(self.sk.ctx._h, self.id, C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
+
+    def __len__(self):
+        return self._info()[0]
+
+    @property
+    def device_bytes(self):
+        return self._info()[1]
+
+    def get(self, first_char=0, count=None):
+        """fhs_store_get: characters [first_char, first_char + count) as a fresh FheString (needs no key)."""
+        if count is None:
+            count = len(self) - first_char
+        hs = (C.c_uint64 * max(1, count))()
+        self.sk.ctx._check(self.sk.ctx._L.fhs_store_get(self.sk.ctx._h, self.id, int(first_char), int(count), hs))
+        return FheString([FheAsciiChar(self.sk, hs[i]) for i in range(count)])
+
+    def drop(self):
+        self.sk.ctx._check(self.sk.ctx._L.fhs_store_drop(self.sk.ctx._h, self.id))
+
+    def export(self):
+        """fhs_store_export -> (CompactFheString, meta[4n] u64); store_export_to_bytes serialises the pair."""
+        n = len(self)
+        c = CompactFheString(n, np.zeros(((4 * n + 2047) // 2048, 2048), np.uint32), np.zeros(4 * n, np.uint32))
+        meta = np.zeros(4 * n, np.uint64)
+        self.sk.ctx._check(self.sk.ctx._L.fhs_store_export(self.sk.ctx._h, self.id, _ptr(c.mask32), _ptr(c.body32), _ptr(meta)))
+        return c, meta
+
+
 def expand_compressed_server_key(seed, bsk_bodies, ksk_bodies):
     """fhs_expand_compressed_server_key: host expansion to the standard-domain (bsk, ksk) of fhs_load_server_key."""
     seed = np.ascontiguousarray(seed, np.uint32)
@@ -912,6 +994,32 @@ class MyServerKey:
         self.ctx._check(self.ctx._L.fhs_upload_string_public(self.ctx._h, _ptr(cstr.mask32), _ptr(cstr.body32), len(cstr),
                                                              first_char, count, hs))
         return FheString([FheAsciiChar(self, hs[i]) for i in range(count)])
+
+    # ---- device-resident string store ---------------------------------------
+    def store_put(self, fhe_string):
+        """fhs_store_put: parks the string in HBM at 34 B per character -> StoredString.  The handles stay valid; release
+        them (drop the FheString) to get the pool blocks back.  Needs the packing key."""
+        chars = list(fhe_string.chars if isinstance(fhe_string, FheString) else fhe_string)
+        eid = C.c_uint64(0)
+        self.ctx._check(self.ctx._L.fhs_store_put(self.ctx._h, _harr(chars), len(chars), C.byref(eid)))
+        return StoredString(self, eid.value)
+
+    def store_import(self, compact, meta=None):
+        """fhs_store_import: an entry from host memory (a StoredString.export(), or with meta=None a public-key encrypted
+        CompactFheString parked as it arrives) -> StoredString."""
+        if meta is not None:
+            meta = np.ascontiguousarray(meta, np.uint64).reshape(-1)
+            assert meta.size == 4 * len(compact)
+        eid = C.c_uint64(0)
+        self.ctx._check(self.ctx._L.fhs_store_import(self.ctx._h, _ptr(compact.mask32), _ptr(compact.body32),
+                                                     None if meta is None else _ptr(meta), len(compact), C.byref(eid)))
+        return StoredString(self, eid.value)
+
+    def store_stats(self):
+        """fhs_store_stats -> dict(entries, chars, device_bytes)."""
+        e, n, b = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self.ctx._check(self.ctx._L.fhs_store_stats(self.ctx._h, C.byref(e), C.byref(n), C.byref(b)))
+        return {"entries": int(e.value), "chars": int(n.value), "device_bytes": int(b.value)}
 
     def import_device(self, d_ptr):
         return FheAsciiChar(self, self.ctx._L.fhs_import_device(self.ctx._h, C.c_void_p(d_ptr)))

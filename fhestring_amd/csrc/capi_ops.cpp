@@ -220,6 +220,59 @@ int fhs_debug_download_string_packed64(fhs_ctx *c, const fhs_char_t *chars, size
 int fhs_download_string_packed(fhs_ctx *c, const fhs_char_t *chars, size_t n, void *mask16, void *body16) {
     return fhs_debug_download_string_packed64(c, chars, n, mask16, body16, nullptr, nullptr);
 }
+
+// ---- device-resident string store ----
+int fhs_store_put(fhs_ctx *c, const fhs_char_t *chars, size_t n, uint64_t *id_out) {
+    if (!c || !id_out || (n && !chars)) return bad(c);
+    *id_out = 0;
+    std::vector<Bid> b(4 * n);
+    for (size_t i = 0; i < n; i++) {
+        if (!c->eng.valid_char(chars[i])) return bad(c);
+        const Bid *cb = c->eng.char_blocks(chars[i]);
+        for (int k = 0; k < 4; k++) b[4 * i + k] = cb[k];
+    }
+    return c->eng.store_put(b.data(), b.size(), id_out);
+}
+int fhs_store_get(fhs_ctx *c, uint64_t id, size_t first_char, size_t count, fhs_char_t *out) {
+    if (!c || (count && !out)) return bad(c);
+    const Engine::StoreEntry *ent = c->eng.store_entry(id);
+    if (!ent) return c->eng.ctx.fail(FHS_ERR_ARG, "string store: unknown entry id");
+    const size_t n_chars = ent->n_blocks / 4;
+    if (first_char > n_chars || count > n_chars - first_char) return c->eng.ctx.fail(FHS_ERR_ARG, "string store: window outside the entry");
+    std::vector<Bid> b(4 * count);
+    if (int rc = c->eng.store_get(id, 4 * first_char, 4 * count, b.data())) return rc;
+    for (size_t i = 0; i < count; i++) out[i] = c->eng.new_char(&b[4 * i]);
+    return FHS_OK;
+}
+int fhs_store_drop(fhs_ctx *c, uint64_t id) {
+    if (!c) return FHS_ERR_ARG;
+    return c->eng.store_drop(id);
+}
+int fhs_store_info(fhs_ctx *c, uint64_t id, size_t *n_chars, size_t *device_bytes) {
+    if (!c) return FHS_ERR_ARG;
+    const Engine::StoreEntry *ent = c->eng.store_entry(id);
+    if (!ent) return c->eng.ctx.fail(FHS_ERR_ARG, "string store: unknown entry id");
+    if (n_chars) *n_chars = ent->n_blocks / 4;
+    if (device_bytes) *device_bytes = ent->bytes();
+    return FHS_OK;
+}
+int fhs_store_stats(fhs_ctx *c, size_t *entries, size_t *chars, size_t *device_bytes) {
+    if (!c) return FHS_ERR_ARG;
+    size_t blocks = 0;
+    c->eng.store_stats(entries, &blocks, device_bytes);
+    if (chars) *chars = blocks / 4;
+    return FHS_OK;
+}
+int fhs_store_export(fhs_ctx *c, uint64_t id, void *mask32, void *body32, uint64_t *meta) {
+    if (!c || !mask32 || !body32 || !meta) return bad(c);
+    return c->eng.store_export(id, static_cast<uint32_t *>(mask32), static_cast<uint32_t *>(body32), meta);
+}
+int fhs_store_import(fhs_ctx *c, const void *mask32, const void *body32, const uint64_t *meta, size_t n, uint64_t *id_out) {
+    if (!c || !id_out) return bad(c);
+    *id_out = 0;
+    if (n > ((size_t)1 << 24) || (n && (!mask32 || !body32))) return bad(c);
+    return c->eng.store_import(static_cast<const uint32_t *>(mask32), static_cast<const uint32_t *>(body32), meta, 4 * n, id_out);
+}
 }  // extern "C"
 int fhs_read_packing_key_file(const char *path, std::vector<uint64_t> &key);   // client.cpp
 extern "C" {

@@ -3,6 +3,7 @@
 #include "../../include/fhestring_hip.h"
 #include "pk_kernels.h"
 #include "seeded_kernels.h"
+#include "store_kernels.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -51,6 +52,7 @@ void Engine::shutdown() {
         if (c.p) (void)hipHostFree(c.p);
     }
     staging_.clear();
+    store_.clear();                                  // entries die with the context
     plan_buf_.release();
     tick_buf_.release();
     batch_in_.release();
@@ -157,6 +159,7 @@ bool Engine::ensure_staging(size_t n_blocks) {
         if (upload_dev_) { (void)hipStreamSynchronize(ctx.stream); (void)hipFree(upload_dev_); }
         upload_pin_ = upload_dev_ = nullptr;
         upload_words_ = 0;
+        table_cursor_ = TABLE_CURSOR_RESET;
         const size_t want = std::max<size_t>(n_blocks, 260) * (BIG_CT + 1);
         void *hp = nullptr, *dp = nullptr;
         if (hipHostMalloc(&hp, want * 8, hipHostMallocDefault) == hipSuccess && hipMalloc(&dp, want * 8) == hipSuccess) {
@@ -210,6 +213,28 @@ int Engine::plan_upload(size_t count, Bid *out) {
 bool Engine::begin_pass(size_t rows) {
     if (!ensure_staging(std::max<size_t>(rows, 1))) return false;
     (void)hipEventSynchronize(upload_done_);         // (no-op before the first copy)
+    table_cursor_ = TABLE_CURSOR_RESET;              // the pass writes the buffer from word 0
+    return true;
+}
+// A pass that sends a pointer table ALONE (store_get): consecutive passes take consecutive segments of the pinned buffer
+// and of its device mirror, so the host only waits when the buffer wraps (or after a pass of the other kind).  The copy
+// of a table is queued behind everything on the stream, a whole launch group included: waiting for the previous table
+// before writing the next one would tie a caller that restores string k + 1 while the GPU works on string k (fhs_submit /
+// fhs_pump) to the GPU's pace.
+bool Engine::begin_table_pass(size_t n, size_t &at) {
+    if (!ensure_staging(1) || n > upload_words_) return false;
+    if (table_cursor_ == TABLE_CURSOR_RESET || table_cursor_ + n > upload_words_) {
+        (void)hipEventSynchronize(upload_done_);
+        table_cursor_ = 0;
+    }
+    at = table_cursor_;
+    table_cursor_ += n;
+    return true;
+}
+bool Engine::send_table_pass(size_t n, Bid *out, size_t at) {
+    if (!new_mat_blocks(n, out, upload_pin_ + at)) return false;
+    if (hipMemcpyAsync(upload_dev_ + at, upload_pin_ + at, n * 8, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) return false;
+    (void)hipEventRecord(upload_done_, ctx.stream);
     return true;
 }
 bool Engine::send_pass(size_t n, Bid *out, size_t ptr_at, size_t words) {
@@ -1355,12 +1380,15 @@ int Engine::materialize_lin(Bid b) {
     // the materialised block IS the linear combination: it keeps its noise (a download followed by further use of the
     // same handle must not look like a fresh bootstrap output to the bookkeeping)
     const int64_t v = sum_c2(b);
+    uint8_t packs = 0;                                // the largest packing count among the terms (string store)
+    for (const Term &t : n.terms) packs = std::max(packs, nodes_[t.blk].packs);
     std::vector<Term> old;
     old.swap(n.terms);
     n.kind = BlockNode::MAT;
     n.var = (uint16_t)std::min<int64_t>(std::max<int64_t>(v, 1), 65535);
     n.dev = o;
     n.level = 0;
+    n.packs = packs;
     for (const Term &t : old) release(t.blk);
     return 0;
 }
@@ -1436,45 +1464,60 @@ int Engine::read_many(const Bid *b, size_t count, uint64_t *host_out) {
     return 0;
 }
 
-int Engine::read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *body16, uint64_t *mask64, uint64_t *body64) {
-    if (planner) return ctx.fail(-3, "planner context: nothing is computed, there is nothing to download");
-    if (!ctx.d_pack_key_ntt) return ctx.fail(-3, "packing key not loaded (fhs_load_packing_key)");
-    if (count == 0) return 0;
+// ---- packing: what the packed download and the string store share --------------------------------------------------
+int Engine::prepare_packing(const Bid *b, size_t count) {
     (void)hipSetDevice(ctx.device);
     if (int rc = flush()) return rc;
     for (size_t i = 0; i < count; i++)                               // as read_many: linear combinations become blocks first
         if (nodes_[b[i]].kind == BlockNode::LIN)
             if (int rc = materialize_lin(b[i])) return rc;
-    // level lv of a group writes (2048 >> lv) GLWEs of 32 KB: level 1 is 32 MB, level 2 16 MB, ping-pong between two
-    // buffers; four groups in flight keep the workspace at 192 MB
+    for (size_t i = 0; i < count; i++)
+        if (nodes_[b[i]].kind != BlockNode::TRIV && nodes_[b[i]].kind != BlockNode::MAT)
+            return ctx.fail(-3, "internal: block not materialised");
+    return 0;
+}
+
+// One pass: the leaf table of n blocks (groups = ceil(n / 2048) <= 4) and the 11 tree levels, enqueued on the stream;
+// the level-11 GLWEs [groups][2][2048] are left in ctx.pack_ws[0].
+// Level lv of a group writes (2048 >> lv) GLWEs of 32 KB: level 1 is 32 MB, level 2 16 MB, ping-pong between two
+// buffers; four groups in flight keep the workspace at 192 MB.
+hipError_t Engine::pack_tree_pass(const Bid *b, size_t n, size_t groups) {
+    constexpr size_t GLWE_BYTES = 2 * POLY_N * 8;
+    std::vector<PackLeaf> leaves(n);
+    for (size_t k = 0; k < n; k++) {
+        const BlockNode &nd = nodes_[b[k]];
+        if (nd.kind == BlockNode::TRIV) leaves[k] = {nullptr, (uint64_t)nd.triv << DELTA_LOG};
+        else leaves[k] = {nd.dev, 0};
+    }
+    hipError_t e = ctx.pack_tab.reserve(n * sizeof(PackLeaf));
+    if (e == hipSuccess) e = ctx.pack_ws[0].reserve(groups * (POLY_N / 2) * GLWE_BYTES);
+    if (e == hipSuccess) e = ctx.pack_ws[1].reserve(groups * (POLY_N / 4) * GLWE_BYTES);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(ctx.pack_tab.ptr, leaves.data(), n * sizeof(PackLeaf), hipMemcpyHostToDevice, ctx.stream);
+    for (int lv = 1; lv <= PACK_TREE_LEVELS && e == hipSuccess; lv++) {
+        PackLevelParams p{};
+        p.lv = lv; p.groups = (int)groups; p.total = (uint32_t)n;
+        p.leaves = ctx.pack_tab.as<PackLeaf>();
+        p.src = ctx.pack_ws[lv & 1].as<uint64_t>();
+        p.dst = ctx.pack_ws[(lv - 1) & 1].as<uint64_t>();
+        p.key_ntt = ctx.d_pack_key_ntt.as<double>(); p.tw = ctx.tw;
+        e = launch_pack_level(p, ctx.stream);
+    }
+    return e;
+}
+
+int Engine::read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *body16, uint64_t *mask64, uint64_t *body64) {
+    if (planner) return ctx.fail(-3, "planner context: nothing is computed, there is nothing to download");
+    if (!ctx.d_pack_key_ntt) return ctx.fail(-3, "packing key not loaded (fhs_load_packing_key)");
+    if (count == 0) return 0;
+    if (int rc = prepare_packing(b, count)) return rc;
     constexpr size_t MAX_GROUPS = 4, GLWE_BYTES = 2 * POLY_N * 8;
-    std::vector<PackLeaf> leaves;
     std::vector<uint64_t> wide;
     for (size_t done = 0; done < count;) {
         const size_t n = std::min(MAX_GROUPS * PACK_GROUP, count - done);
         const size_t groups = (n + PACK_GROUP - 1) / PACK_GROUP;
-        leaves.resize(n);
-        for (size_t k = 0; k < n; k++) {
-            const BlockNode &nd = nodes_[b[done + k]];
-            if (nd.kind == BlockNode::TRIV) leaves[k] = {nullptr, (uint64_t)nd.triv << DELTA_LOG};
-            else if (nd.kind == BlockNode::MAT) leaves[k] = {nd.dev, 0};
-            else return ctx.fail(-3, "internal: block not materialised");
-        }
-        hipError_t e = ctx.pack_tab.reserve(n * sizeof(PackLeaf));
-        if (e == hipSuccess) e = ctx.pack_ws[0].reserve(groups * (POLY_N / 2) * GLWE_BYTES);
-        if (e == hipSuccess) e = ctx.pack_ws[1].reserve(groups * (POLY_N / 4) * GLWE_BYTES);
-        if (e == hipSuccess) e = ctx.pack_out.reserve(groups * 2 * PACK_GROUP * sizeof(uint16_t));
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(ctx.pack_tab.ptr, leaves.data(), n * sizeof(PackLeaf), hipMemcpyHostToDevice, ctx.stream);
-        for (int lv = 1; lv <= PACK_TREE_LEVELS && e == hipSuccess; lv++) {
-            PackLevelParams p{};
-            p.lv = lv; p.groups = (int)groups; p.total = (uint32_t)n;
-            p.leaves = ctx.pack_tab.as<PackLeaf>();
-            p.src = ctx.pack_ws[lv & 1].as<uint64_t>();
-            p.dst = ctx.pack_ws[(lv - 1) & 1].as<uint64_t>();
-            p.key_ntt = ctx.d_pack_key_ntt.as<double>(); p.tw = ctx.tw;
-            e = launch_pack_level(p, ctx.stream);
-        }
+        hipError_t e = ctx.pack_out.reserve(groups * 2 * PACK_GROUP * sizeof(uint16_t));
+        if (e == hipSuccess) e = pack_tree_pass(b + done, n, groups);
         uint16_t *d_mask = ctx.pack_out.as<uint16_t>(), *d_body = d_mask + groups * PACK_GROUP;
         if (e == hipSuccess) e = launch_pack_switch16(ctx.pack_ws[0].as<uint64_t>(), d_mask, d_body, (int)groups, (uint32_t)n, ctx.stream);
         if (e == hipSuccess)
@@ -1493,6 +1536,177 @@ int Engine::read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *
             }
         done += n;
     }
+    return 0;
+}
+
+// ---- device-resident string store -------------------------------------------------------------------------------------
+const Engine::StoreEntry *Engine::store_entry(uint64_t id) const {
+    auto it = store_.find(id);
+    return it == store_.end() ? nullptr : &it->second;
+}
+
+void Engine::store_stats(size_t *entries, size_t *blocks, size_t *bytes) const {
+    size_t nb = 0, by = 0;
+    for (const auto &kv : store_) { nb += kv.second.n_blocks; by += kv.second.bytes(); }
+    if (entries) *entries = store_.size();
+    if (blocks) *blocks = nb;
+    if (bytes) *bytes = by;
+}
+
+int Engine::store_drop(uint64_t id) {
+    auto it = store_.find(id);
+    if (it == store_.end()) return ctx.fail(-1, "string store: unknown entry id");
+    if (it->second.buf) {                                            // a queued expansion may still read it
+        (void)hipSetDevice(ctx.device);
+        (void)hipStreamSynchronize(ctx.stream);
+    }
+    store_.erase(it);
+    return 0;
+}
+
+int Engine::store_put(const Bid *b, size_t count, uint64_t *id_out) {
+    if (!planner && !ctx.d_pack_key_ntt) return ctx.fail(-3, "packing key not loaded (fhs_load_packing_key)");
+    if (count == 0) return ctx.fail(-1, "string store: an entry holds at least one character");
+    if (planner) {
+        if (int rc = flush()) return rc;                             // sums stay sums on a planner: their figure is what counts
+    } else if (int rc = prepare_packing(b, count)) return rc;
+    // what the bookkeeping knows about every block (a sum that was just materialised carries its figure and the largest
+    // packing count of its terms; the planner's unmaterialised sum is read the same way)
+    StoreEntry ent;
+    ent.n_blocks = count;
+    ent.var.resize(count); ent.cycles.resize(count); ent.rot.resize(count);
+    for (size_t i = 0; i < count; i++) {
+        const BlockNode &nd = nodes_[b[i]];
+        int packs = 0;
+        if (nd.kind == BlockNode::MAT) packs = nd.packs;
+        else if (nd.kind == BlockNode::LIN)
+            for (const Term &t : nd.terms) packs = std::max<int>(packs, nodes_[t.blk].packs);
+        else if (nd.kind != BlockNode::TRIV) return ctx.fail(-3, "internal: block not materialised");
+        if (packs + 1 > STORE_MAX_CYCLES)
+            return ctx.fail(-4, "string store: a block would exceed FHS_STORE_MAX_CYCLES packings without a bootstrap in between");
+        // a trivial block is packed as the trivial leaf it is and comes back as an ordinary ciphertext
+        ent.var[i] = nd.kind == BlockNode::TRIV ? 1 : (uint16_t)std::min<int64_t>(std::max<int64_t>(sum_c2(b[i]), 1), 65535);
+        ent.cycles[i] = (uint8_t)(packs + 1);
+        ent.rot[i] = nd.kind == BlockNode::MAT ? nd.rot : 0;
+    }
+    if (!planner) {
+        hipError_t e = ent.buf.reserve_exact(ent.bytes());
+        uint32_t *mask32 = ent.buf.as<uint32_t>(), *body32 = mask32 + ent.groups() * POLY_N;
+        constexpr size_t MAX_GROUPS = 4;
+        for (size_t done = 0; done < count && e == hipSuccess;) {     // pass p starts at group 4 p of the entry
+            const size_t n = std::min(MAX_GROUPS * PACK_GROUP, count - done);
+            const size_t groups = (n + PACK_GROUP - 1) / PACK_GROUP;
+            e = pack_tree_pass(b + done, n, groups);
+            if (e == hipSuccess)
+                e = launch_store_switch32(ctx.pack_ws[0].as<uint64_t>(), mask32, body32, (uint32_t)(done / PACK_GROUP), (int)groups,
+                                          (uint32_t)n, ctx.stream);
+            done += n;
+        }
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
+        if (e != hipSuccess) return ctx.hip_fail(e, "string store: put");
+    }
+    const uint64_t id = ++store_ids_;
+    StoreEntry &dst = store_[id];
+    dst.n_blocks = ent.n_blocks;
+    std::swap(dst.buf.ptr, ent.buf.ptr); std::swap(dst.buf.cap, ent.buf.cap);
+    dst.var.swap(ent.var); dst.cycles.swap(ent.cycles); dst.rot.swap(ent.rot);
+    *id_out = id;
+    return 0;
+}
+
+int Engine::store_get(uint64_t id, size_t first, size_t count, Bid *out) {
+    const StoreEntry *ent = store_entry(id);
+    if (!ent) return ctx.fail(-1, "string store: unknown entry id");
+    if (first > ent->n_blocks || count > ent->n_blocks - first) return ctx.fail(-1, "string store: window outside the entry");
+    for (size_t i = 0; i < count; i++) out[i] = 0;
+    if (planner) {
+        (void)plan_upload(count, out);
+    } else {
+        (void)hipSetDevice(ctx.device);
+        const uint32_t *mask32 = ent->buf.as<uint32_t>(), *body32 = mask32 + ent->groups() * POLY_N;
+        // as from_public_many, but masks and bodies are already on the device: the pinned buffer carries the destination
+        // pointers alone (8 B per block)
+        constexpr size_t MAX_BATCH = 4096;
+        for (size_t done = 0, n; done < count; done += n) {
+            n = std::min(MAX_BATCH, count - done);
+            const size_t t0 = first + done, g0 = t0 / FHS_PK_GROUP;
+            size_t at = 0;
+            if (!begin_table_pass(n, at) || !send_table_pass(n, out + done, at) ||
+                launch_expand_public_blocks(mask32 + g0 * POLY_N, body32 + t0,
+                                            reinterpret_cast<uint64_t *const *>(upload_dev_ + at), (uint32_t)(t0 % FHS_PK_GROUP),
+                                            (int)n, ctx.stream) != hipSuccess) {
+                (void)undo_upload(out, count);
+                return ctx.fail(-2, "string store: get failed (device allocation, copy or expansion launch)");
+            }
+        }
+    }
+    for (size_t i = 0; i < count; i++) {
+        BlockNode &nd = nodes_[out[i]];
+        nd.var = ent->var[first + i];
+        nd.rot = ent->rot[first + i];
+        nd.packs = ent->cycles[first + i];
+    }
+    return 0;
+}
+
+int Engine::store_export(uint64_t id, uint32_t *mask32, uint32_t *body32, uint64_t *meta) {
+    const StoreEntry *ent = store_entry(id);
+    if (!ent) return ctx.fail(-1, "string store: unknown entry id");
+    if (planner) return ctx.fail(-3, "planner context: nothing is computed, there is nothing to export");
+    (void)hipSetDevice(ctx.device);
+    const size_t mask_bytes = ent->groups() * POLY_N * 4;
+    hipError_t e = hipMemcpyAsync(mask32, ent->buf.ptr, mask_bytes, hipMemcpyDeviceToHost, ctx.stream);
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(body32, ent->buf.as<uint8_t>() + mask_bytes, ent->n_blocks * 4, hipMemcpyDeviceToHost, ctx.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
+    if (e != hipSuccess) return ctx.hip_fail(e, "string store: export");
+    std::unordered_map<uint32_t, uint32_t> local;                    // engine id -> 1..k in order of first appearance
+    for (size_t i = 0; i < ent->n_blocks; i++) {
+        uint64_t g = 0;
+        if (ent->rot[i]) {
+            auto it = local.find(ent->rot[i]);
+            g = it != local.end() ? it->second : (local[ent->rot[i]] = (uint32_t)local.size() + 1);
+        }
+        meta[i] = (uint64_t)ent->var[i] | (uint64_t)ent->cycles[i] << 16 | g << 32;
+    }
+    return 0;
+}
+
+int Engine::store_import(const uint32_t *mask32, const uint32_t *body32, const uint64_t *meta, size_t n_blocks, uint64_t *id_out) {
+    if (n_blocks == 0) return ctx.fail(-1, "string store: an entry holds at least one character");
+    StoreEntry ent;
+    ent.n_blocks = n_blocks;
+    ent.var.assign(n_blocks, 1); ent.cycles.assign(n_blocks, 0); ent.rot.assign(n_blocks, 0);
+    uint32_t k = 0;
+    if (meta) {
+        for (size_t i = 0; i < n_blocks; i++) {
+            const uint64_t var = meta[i] & 0xffff, cyc = (meta[i] >> 16) & 0xff, grp = meta[i] >> 32;
+            if (var < 1 || cyc > (uint64_t)STORE_MAX_CYCLES || (meta[i] >> 24 & 0xff) || grp > n_blocks)
+                return ctx.fail(-1, "string store: import refuses a meta word (var >= 1, cycles <= FHS_STORE_MAX_CYCLES, groups 1..k)");
+            ent.var[i] = (uint16_t)var; ent.cycles[i] = (uint8_t)cyc; ent.rot[i] = (uint32_t)grp;
+            k = std::max(k, (uint32_t)grp);
+        }
+    }
+    if (!planner) {
+        (void)hipSetDevice(ctx.device);
+        const size_t mask_bytes = ent.groups() * POLY_N * 4;
+        // mask32 and body32 are separate host arrays: each goes to its place in the ONE allocation
+        hipError_t e = ent.buf.reserve_exact(ent.bytes());
+        if (e == hipSuccess) e = hipMemcpyAsync(ent.buf.ptr, mask32, mask_bytes, hipMemcpyHostToDevice, ctx.stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(ent.buf.as<uint8_t>() + mask_bytes, body32, n_blocks * 4, hipMemcpyHostToDevice, ctx.stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
+        if (e != hipSuccess) return ctx.hip_fail(e, "string store: import");
+    }
+    // the entry's k groups get k fresh engine ids, drawn once per entry
+    std::vector<uint32_t> fresh(k + 1, 0);
+    for (uint32_t g = 1; g <= k; g++) fresh[g] = ++rot_counter_ ? rot_counter_ : ++rot_counter_;
+    for (size_t i = 0; i < n_blocks; i++) ent.rot[i] = fresh[ent.rot[i]];
+    const uint64_t id = ++store_ids_;
+    StoreEntry &dst = store_[id];
+    dst.n_blocks = ent.n_blocks;
+    std::swap(dst.buf.ptr, ent.buf.ptr); std::swap(dst.buf.cap, ent.buf.cap);
+    dst.var.swap(ent.var); dst.cycles.swap(ent.cycles); dst.rot.swap(ent.rot);
+    *id_out = id;
     return 0;
 }
 

@@ -45,6 +45,9 @@ struct BlockNode {
                              // share a blind rotation (plan_job); 0 = counts as a rotation of its own
     uint32_t rot = 0;        // MAT: rotation group (non-zero for the leader and the followers of ONE shared blind rotation):
                              // their noises are correlated, the bookkeeping adds their coefficients before squaring
+    uint8_t packs = 0;       // MAT: ring packings inside this block's noise (a block restored from the string store: the entry's
+                             // cycle count; a materialised sum: the maximum over its terms; 0 for everything else, every
+                             // bootstrap output included).  True variance <= var * (1 + packs * 2^-11.6).
     uint64_t ready_tick = 0; // MAT produced by a scheduled (not yet enqueued) job level: the tick that writes it
     Bid src = 0;             // PBS: input block
     uint64_t *dev = nullptr; // MAT: device ciphertext (2049 u64)
@@ -153,6 +156,32 @@ class Engine {
     // packed download (pack_kernels.hip): ring-packs the blocks in groups of 2048 and stores them at 16 bits; mask16
     // [groups][2048], body16 [count].  mask64 / body64 (diagnostic, may be null): the 64-bit GLWEs [groups][2048].
     int read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *body16, uint64_t *mask64, uint64_t *body64);
+    // ---- device-resident string store (store_kernels.hip; include/fhestring_hip.h, "device-resident string store") ----
+    // An entry is one block sequence parked in the compact-string format: mask32[ceil(n / 2048)][2048] | body32[n] in ONE
+    // device allocation of its exact size, plus what the bookkeeping knew about every block at store_put (host side).
+    struct StoreEntry {
+        size_t n_blocks = 0;
+        DevBuf buf;                       // empty on a planner context
+        std::vector<uint16_t> var;        // BlockNode::var (1 for a trivial block: it comes back as an ordinary ciphertext)
+        std::vector<uint8_t> cycles;      // packings inside the block's noise, this entry's included (0: imported fresh)
+        std::vector<uint32_t> rot;        // BlockNode::rot, the engine's id verbatim
+        size_t groups() const { return (n_blocks + 2047) / 2048; }
+        size_t bytes() const { return groups() * 2048 * 4 + n_blocks * 4; }
+    };
+    static constexpr int STORE_MAX_CYCLES = 16;   // FHS_STORE_MAX_CYCLES
+    // Parks `count` blocks (any block read_packed takes; pending work is flushed, sums are materialised) through the packing
+    // tree and the 32-bit switch, all on the device.  A planner context records the metadata only.
+    int store_put(const Bid *b, size_t count, uint64_t *id_out);
+    // Blocks [first, first + count) of an entry as fresh MAT blocks with the entry's var / rot / cycles restored: passes of
+    // up to 4096 blocks, only the destination pointer table crosses the bus.  Needs no key.
+    int store_get(uint64_t id, size_t first, size_t count, Bid *out);
+    int store_drop(uint64_t id);
+    const StoreEntry *store_entry(uint64_t id) const;
+    void store_stats(size_t *entries, size_t *blocks, size_t *bytes) const;
+    // meta[t]: bits 0-15 var, 16-23 cycles, 32-63 the rotation group renumbered 1..k within the entry (0 = none)
+    int store_export(uint64_t id, uint32_t *mask32, uint32_t *body32, uint64_t *meta);
+    // one H2D copy, no kernel; meta == nullptr: every block a fresh upload (var 1, no group, no packing)
+    int store_import(const uint32_t *mask32, const uint32_t *body32, const uint64_t *meta, size_t n_blocks, uint64_t *id_out);
     // flushes if needed (do_flush = false: the caller has made sure the block's tick is enqueued); wait=false: enqueue only
     int copy_block_to_device(Bid b, uint64_t *d_out, bool wait = true, bool do_flush = true);
     uint64_t blocks_live() const { return live_dev_blocks_; }
@@ -210,6 +239,10 @@ class Engine {
     int plan_upload(size_t count, Bid *out);
     bool begin_pass(size_t rows);
     bool send_pass(size_t n, Bid *out, size_t ptr_at, size_t words);
+    static constexpr size_t TABLE_CURSOR_RESET = ~(size_t)0;
+    size_t table_cursor_ = TABLE_CURSOR_RESET;                 // next free word of the pinned buffer for a pointer-table pass
+    bool begin_table_pass(size_t n, size_t &at);
+    bool send_table_pass(size_t n, Bid *out, size_t at);
     uint64_t *alloc_block();
     void free_block(uint64_t *p);
 
@@ -301,6 +334,12 @@ class Engine {
 
     Bid new_node();
     int materialize_lin(Bid b);
+    // What read_packed and store_put share: flush, sums become blocks; then per pass of up to four groups the leaf table
+    // and the 11 tree levels, which leave the pass's GLWEs [groups][2][2048] in ctx.pack_ws[0].
+    int prepare_packing(const Bid *b, size_t count);
+    hipError_t pack_tree_pass(const Bid *b, size_t n, size_t groups);
+    std::map<uint64_t, StoreEntry> store_;
+    uint64_t store_ids_ = 0;             // ids handed out: never reused inside a context
 };
 
 // RAII reference to a block

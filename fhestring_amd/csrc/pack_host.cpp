@@ -264,6 +264,18 @@ int fhs_pack_switch16(const uint64_t *mask64, const uint64_t *body64, size_t n_b
     return FHS_OK;
 }
 
+int fhs_pack_switch32(const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, void *mask32_, void *body32_) {
+    uint32_t *mask32 = static_cast<uint32_t *>(mask32_), *body32 = static_cast<uint32_t *>(body32_);
+    if (n_blocks && (!mask64 || !body64 || !mask32 || !body32)) return FHS_ERR_ARG;
+    auto sw = [](uint64_t x) { return (uint32_t)((x + (1ull << 31)) >> 32); };
+    for (size_t g = 0; g * FHS_PACK_GROUP < n_blocks; g++) {
+        const size_t count = std::min<size_t>(FHS_PACK_GROUP, n_blocks - g * FHS_PACK_GROUP);
+        for (int i = 0; i < N; i++) mask32[g * N + i] = sw(mask64[g * N + i]);
+        for (size_t j = 0; j < count; j++) body32[g * FHS_PACK_GROUP + j] = sw(body64[g * N + j]);
+    }
+    return FHS_OK;
+}
+
 int fhs_debug_pack_node(const uint64_t *key, int lv, const uint64_t *e, const uint64_t *o, uint64_t *out) {
     if (!key || !e || !o || !out || lv < 1 || lv > FHS_PACK_TREE_LEVELS) return FHS_ERR_ARG;
     HostKey hk;

@@ -633,6 +633,55 @@ int fhs_expand_public_str(const void *mask32, const void *body32, size_t n_total
 int fhs_upload_string_public(fhs_ctx *ctx, const void *mask32, const void *body32, size_t n_total, size_t first_char,
                              size_t count, fhs_char_t *out);
 
+/* ---- device-resident string store: strings parked packed, expanded on demand --------------------------------
+ * A string a context keeps between requests costs 65 568 B of HBM per character as pool blocks.  The store parks it as
+ * the output of the packing tree above with every word rounded to 32 bits, (x + 2^31) >> 32 -- word for word the compact
+ * string format of the public-key uploads -- and the sample extraction of fhs_upload_string_public brings it back, whole
+ * or by window, straight from device memory: 34 B per character at rest (4097 characters: 139 280 B instead of 268 MB).
+ * An ENTRY is one block sequence: block t = 4 x character + digit sits in group t / 2048 at coefficient t % 2048, stored
+ * as mask32[ceil(4n / 2048)][2048] followed by body32[4n] (the sizes of fhs_public_str_words) in ONE device allocation
+ * of exactly that size.  Ids are non-zero and never reused inside a context.  A table of short strings is parked as ONE
+ * entry (concatenated) and read by window; there is no per-string entry table.  Entries survive a server-key reload,
+ * like handles, and die with the context.
+ * Noise: a restored block carries the packing noise, sigma 2^43.1 (the 32-bit rounding's 2^35.2
+ * disappears under it) against a bootstrap output's 2^48.9, i.e. 2^-11.6 of one sum c^2 unit per packing, which the
+ * integer figure cannot show.  The store therefore keeps per block, on the host: the figure of fhs_char_sum_c2 at put (a
+ * sum is materialised and keeps its figure; a TRIVIAL block is packed as the trivial leaf it is and comes back as an
+ * ordinary ciphertext with figure 1: constant folding does not survive parking), the rotation group (members of one
+ * shared blind rotation stay charged as fully correlated, also across windows read at different times), and the number
+ * of packings inside the block's noise, `cycles`.  put stores the block's count + 1 and refuses a block that would
+ * exceed FHS_STORE_MAX_CYCLES with FHS_ERR_LIMIT; get hands the count back to the block; a sum takes the maximum over
+ * its terms; every bootstrap starts at 0 again.  The true variance of a block is <= figure x (1 + cycles x 2^-11.6), and
+ * at 16 cycles sqrt(16) x 2^43.1 = 2^45.1 stays below the 2^46 that bounds packing noise: the limit only ever meets data
+ * that is parked and re-parked without being computed on. */
+#define FHS_STORE_MAX_CYCLES 16
+/* Parks n characters (any handle fhs_download takes; they are left as fhs_download_string_packed leaves them, and the
+ * caller releases them when it wants the pool blocks back).  *id_out receives the entry id.  FHS_ERR_STATE without a
+ * packing key (also after a server-key reload dropped it), FHS_ERR_ARG for n = 0, FHS_ERR_LIMIT see above.  A planner
+ * context records the bookkeeping and allocates nothing. */
+int fhs_store_put(fhs_ctx *ctx, const fhs_char_t *chars, size_t n, uint64_t *id_out);
+/* Characters [first_char, first_char + count) of an entry as FRESH handles (out[count]) owned by the caller: only the
+ * destination pointers cross the bus (8 B per block).  Needs no key.  FHS_ERR_ARG for an unknown id or a window outside
+ * the entry.  A planner context records one upload per block. */
+int fhs_store_get(fhs_ctx *ctx, uint64_t id, size_t first_char, size_t count, fhs_char_t *out);
+int fhs_store_drop(fhs_ctx *ctx, uint64_t id);                 /* frees the allocation; FHS_ERR_ARG for an unknown id */
+/* Characters and bytes of device memory of one entry (8192 ceil(4n / 2048) + 16 n) / of all entries of the context. */
+int fhs_store_info(fhs_ctx *ctx, uint64_t id, size_t *n_chars, size_t *device_bytes);
+int fhs_store_stats(fhs_ctx *ctx, size_t *entries, size_t *chars, size_t *device_bytes);
+/* An entry to host memory and back (disk, another context of the same client key).  mask32 / body32: arrays of uint32_t
+ * sized by fhs_public_str_words(n).  meta[4n], one word per block: bits 0-15 the figure (>= 1), bits 16-23 cycles
+ * (<= FHS_STORE_MAX_CYCLES), bits 24-31 zero, bits 32-63 the rotation group, renumbered 1..k within the entry (0 = none);
+ * import draws k fresh groups.  import is one host-to-device copy and no kernel.  meta == NULL declares every block a
+ * fresh upload (figure 1, no group, cycles 0): a public-key encrypted string can be parked as it arrives, without ever
+ * being expanded whole.  import checks the ranges above and otherwise TRUSTS the figures, as fhs_char_set_noise trusts
+ * its caller.  export: FHS_ERR_STATE on a planner context (it holds no ciphertext). */
+int fhs_store_export(fhs_ctx *ctx, uint64_t id, void *mask32, void *body32, uint64_t *meta /*[4n]*/);
+int fhs_store_import(fhs_ctx *ctx, const void *mask32, const void *body32, const uint64_t *meta /*may be NULL*/, size_t n,
+                     uint64_t *id_out);
+/* Host reference of the store's storage switch, next to fhs_pack_switch16: every word -> (x + 2^31) >> 32;
+ * mask32[groups][2048], body32[n_blocks]. */
+int fhs_pack_switch32(const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, void *mask32, void *body32);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,26 @@ int main() {
         CHECK(fhs_char_sum_c2(c, hs[599], &c2) == FHS_OK && c2 == 1);
         for (fhs_char_t h : hs) CHECK(fhs_release(c, h) == FHS_OK);
     }
+    {   // the string store's host side on the planner: entry table, windows, meta words, one entry left to the context
+        std::vector<uint32_t> m32(2 * 2048, 0), b32(4 * 600, 0);
+        std::vector<uint64_t> meta(4 * 600, 1 | 3ull << 16 | 2ull << 32);
+        std::vector<fhs_char_t> hs(600);
+        uint64_t id = 0, id2 = 0, c2 = 0;
+        size_t n = 0, bytes = 0;
+        CHECK(fhs_store_import(c, m32.data(), b32.data(), meta.data(), 600, &id) == FHS_OK && id != 0);
+        meta[2399] = 0;
+        CHECK(fhs_store_import(c, m32.data(), b32.data(), meta.data(), 600, &id2) == FHS_ERR_ARG && id2 == 0);
+        CHECK(fhs_store_info(c, id, &n, &bytes) == FHS_OK && n == 600 && bytes == 2 * 8192 + 16 * 600);
+        CHECK(fhs_store_get(c, id, 590, 11, hs.data()) == FHS_ERR_ARG);
+        CHECK(fhs_store_get(c, id, 0, 600, hs.data()) == FHS_OK);
+        CHECK(fhs_store_put(c, hs.data(), 600, &id2) == FHS_OK && id2 != id && id2 != 0);
+        CHECK(fhs_store_drop(c, id) == FHS_OK && fhs_store_drop(c, id) == FHS_ERR_ARG);
+        for (fhs_char_t h : hs) CHECK(fhs_release(c, h) == FHS_OK);
+        CHECK(fhs_store_get(c, id2, 599, 1, hs.data()) == FHS_OK);
+        CHECK(fhs_char_sum_c2(c, hs[0], &c2) == FHS_OK && c2 == 1);
+        CHECK(fhs_release(c, hs[0]) == FHS_OK);
+        CHECK(fhs_store_stats(c, &n, nullptr, &bytes) == FHS_OK && n == 1 && bytes == 2 * 8192 + 16 * 600);
+    }
     for (int r = 0; r < 2; r++) {
         // a compressed upload on the planner (handles only), then the all-at-once plan walked as rank r of 2 would:
         // fhs_flush_plan builds whole levels with the level builder of every flush, level_exec counts this rank's slice
