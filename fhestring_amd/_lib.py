@@ -251,6 +251,8 @@ def _declare(L):
     L.fhs_debug_char_terms.restype = i
     L.fhs_debug_lut_poly.argtypes = [i, vp]
     L.fhs_debug_lut_poly.restype = i
+    L.fhs_debug_live_resources.argtypes = [vp]
+    L.fhs_debug_live_resources.restype = i
     L.fhs_debug_capture_live.argtypes = [vp, i]
     L.fhs_debug_capture_live.restype = i
     L.fhs_debug_capture_read.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
@@ -420,6 +422,14 @@ class Stats(C.Structure):
     _fields_ = [("pbs_executed", C.c_uint64), ("pbs_folded", C.c_uint64), ("levels", C.c_uint64),
                 ("max_level_width", C.c_uint64), ("blocks_live", C.c_uint64), ("max_input_sum_c2", C.c_uint64), ("pbs_shared", C.c_uint64),
                 ("pbs_extracted", C.c_uint64)]
+
+
+def live_resources():
+    """fhs_debug_live_resources: [device bytes, pinned bytes, events, streams] this library holds now, acquisitions so far."""
+    out = (C.c_uint64 * 5)()
+    if lib().fhs_debug_live_resources(out):
+        raise FhsError("fhs_debug_live_resources failed")
+    return list(out)
 
 
 def fft_tables():

@@ -33,9 +33,7 @@ int fhs_ctx_create_planner(fhs_ctx **out) {
 }
 
 void fhs_ctx_destroy(fhs_ctx *ctx) {
-    if (!ctx) return;
-    ctx->eng.shutdown();
-    delete ctx;
+    delete ctx;   // ~Engine waits for the stream; every resource goes with its owner
 }
 
 const char *fhs_last_error(const fhs_ctx *ctx) { return ctx ? ctx->eng.ctx.err.c_str() : "null context"; }
@@ -137,12 +135,11 @@ int fhs_debug_chacha20_device(fhs_ctx *ctx, const uint32_t key[8], uint32_t coun
     if (hipSetDevice(c.device) != hipSuccess) return c.fail(FHS_ERR_HIP, "hipSetDevice failed");
     fhs::SeedKey k;
     for (int i = 0; i < 8; i++) k.w[i] = key[i];
-    uint64_t *d = nullptr;
-    hipError_t e = hipMalloc(&d, n * 8);
-    if (e == hipSuccess) e = fhs::launch_chacha20_stream(k, counter, nonce, d, n, c.stream);
+    fhs::DevBuf d;
+    hipError_t e = d.reserve_exact(n * 8);
+    if (e == hipSuccess) e = fhs::launch_chacha20_stream(k, counter, nonce, d.as<uint64_t>(), n, c.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
-    if (e == hipSuccess) e = hipMemcpy(out, d, n * 8, hipMemcpyDeviceToHost);
-    if (d) (void)hipFree(d);
+    if (e == hipSuccess) e = hipMemcpy(out, d.ptr, n * 8, hipMemcpyDeviceToHost);
     return e == hipSuccess ? FHS_OK : c.hip_fail(e, "device keystream");
 }
 
@@ -227,6 +224,12 @@ int fhs_debug_char_terms(fhs_ctx *ctx, fhs_char_t h, uint64_t *out, size_t cap, 
     if (!out) return FHS_OK;
     if (cap < v.size()) return ctx->eng.ctx.fail(FHS_ERR_ARG, "fhs_debug_char_terms: buffer too small");
     std::copy(v.begin(), v.end(), out);
+    return FHS_OK;
+}
+
+int fhs_debug_live_resources(uint64_t out[5]) {
+    if (!out) return FHS_ERR_ARG;
+    fhs::live_resources(out);
     return FHS_OK;
 }
 

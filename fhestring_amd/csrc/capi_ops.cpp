@@ -302,7 +302,7 @@ int fhs_export_device_async(fhs_ctx *c, fhs_char_t a, uint64_t *d_blocks) {
     }
     return FHS_OK;
 }
-void *fhs_stream_handle(fhs_ctx *c) { return c ? reinterpret_cast<void *>(c->eng.ctx.stream) : nullptr; }
+void *fhs_stream_handle(fhs_ctx *c) { return c ? static_cast<hipStream_t>(c->eng.ctx.stream) : nullptr; }
 
 int fhs_set_mode(fhs_ctx *c, int mode) {
     if (!c || (mode != FHS_MODE_AS_WRITTEN && mode != FHS_MODE_FUSED)) return bad(c);

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <thread>
+#include <utility>
 
 namespace fhs {
 
@@ -20,57 +21,35 @@ constexpr size_t BSK_BYTES = (size_t)LWE_N * 4 * POLY_N * sizeof(uint64_t);
         if (e__ != hipSuccess) return hip_fail(e__, what); \
     } while (0)
 
-hipError_t DevBuf::reserve(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    return reserve_exact(std::max(bytes, (size_t)1 << 20));
-}
-hipError_t DevBuf::reserve_exact(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    release();
-    hipError_t e = hipMalloc(&ptr, bytes);
-    if (e == hipSuccess) cap = bytes;
-    else ptr = nullptr;
-    return e;
-}
-void DevBuf::release() {
-    if (ptr) (void)hipFree(ptr);
-    ptr = nullptr;
-    cap = 0;
-}
-
-hipEvent_t KernelTimer::get() {
-    if (!pool.empty()) {
-        hipEvent_t e = pool.back();
-        pool.pop_back();
-        return e;
-    }
-    hipEvent_t e;
-    (void)hipEventCreate(&e);
+Event KernelTimer::get() {
+    if (pool.empty()) return Event();
+    Event e = std::move(pool.back());
+    pool.pop_back();
     return e;
 }
 void KernelTimer::begin(int kind, uint64_t u, hipStream_t s) {
     if (!enabled) return;
     if (pending.size() > 4096) resolve();
     Pending p{get(), get(), kind, u, 1};
-    (void)hipEventRecord(p.e0, s);
-    pending.push_back(p);
+    (void)hipEventRecord(p.e0.get(), s);
+    pending.push_back(std::move(p));
 }
 void KernelTimer::end(hipStream_t s, uint32_t kernel_launches) {
     if (!enabled || pending.empty()) return;
     pending.back().launches = kernel_launches ? kernel_launches : 1;
-    (void)hipEventRecord(pending.back().e1, s);
+    (void)hipEventRecord(pending.back().e1.get(), s);
 }
 void KernelTimer::resolve() {
     for (auto &p : pending) {
-        (void)hipEventSynchronize(p.e1);
+        (void)hipEventSynchronize(p.e1.peek());
         float t = 0;
-        if (hipEventElapsedTime(&t, p.e0, p.e1) == hipSuccess) {
+        if (hipEventElapsedTime(&t, p.e0.peek(), p.e1.peek()) == hipSuccess) {
             ms[p.kind] += t;
             n[p.kind] += p.launches;
             units[p.kind] += p.units;
         }
-        pool.push_back(p.e0);
-        pool.push_back(p.e1);
+        pool.push_back(std::move(p.e0));
+        pool.push_back(std::move(p.e1));
     }
     pending.clear();
 }
@@ -78,12 +57,6 @@ void KernelTimer::reset() {
     resolve();
     for (int k = 0; k < 3; k++) { ms[k] = 0; n[k] = 0; units[k] = 0; }
 }
-void KernelTimer::destroy() {
-    resolve();
-    for (auto e : pool) (void)hipEventDestroy(e);
-    pool.clear();
-}
-
 int Context::hip_fail(hipError_t e, const char *what) {
     err = std::string(what) + ": " + hipGetErrorString(e);
     return -2;
@@ -122,10 +95,10 @@ int Context::init(int device_id) {
             if (*end != ',') break;
         }
         if (mask.empty() || bits == 0 || bits > cus) return fail(-1, "FHS_STREAM_CU_MASK: expected hex words selecting 1.." + std::to_string(cus) + " CUs");
-        HIP_TRY(hipExtStreamCreateWithCUMask(&stream, (uint32_t)mask.size(), mask.data()), "hipExtStreamCreateWithCUMask");
+        HIP_TRY(stream.create(mask.data(), (uint32_t)mask.size()), "hipExtStreamCreateWithCUMask");
         cus = bits;
     } else {
-        HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking), "hipStreamCreate");
+        HIP_TRY(stream.create(), "hipStreamCreate");
     }
     wg_slots = 4 * cus;
     // two-bit f64 kernel: one round of resident workgroups per launch (its 73 MB key only stays inside the L2 window
@@ -142,17 +115,10 @@ int Context::init(int device_id) {
     return 0;
 }
 
-void Context::shutdown() {
+Context::~Context() {
     if (stream) (void)hipStreamSynchronize(stream);
     dist.shutdown();
-    timer.destroy();
-    for (DevBuf *b : {&xchg_send, &xchg_recv, &dig_buf, &ks_buf, &ms_buf, &in_buf, &out_buf, &lutidx_buf, &luts_buf, &tab_buf,
-                      &pack_ws[0], &pack_ws[1], &pack_tab, &pack_out,
-                      &d_ksk_planes, &d_bsk_ntt, &d_tables, &d_bsk_fft, &d_bsk_std, &d_fft_tables, &d_work_counter,
-                      &d_bsk_mb, &d_bsk_ntt_mb, &d_pack_key_ntt})
-        b->release();
-    if (stream) (void)hipStreamDestroy(stream);
-    stream = nullptr;
+    timer.resolve();
 }
 
 int Context::load_server_key(const uint64_t *bsk, const uint64_t *ksk) {

@@ -9,26 +9,11 @@
 #include "../../include/fhestring_hip.h"
 #include "dist.h"
 #include "fft_tables.h"
+#include "hip_owners.h"
 #include "ntt_tables.h"
 #include "pbs_kernels.h"
 
 namespace fhs {
-
-// owner of one device allocation, grow-only.  A buffer that never reserved (or was released) holds nothing and its
-// destructor makes no HIP call.
-struct DevBuf {
-    void *ptr = nullptr;
-    size_t cap = 0;
-    DevBuf() = default;
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { release(); }
-    hipError_t reserve(size_t bytes);         // scratch: at least 1 MB, so that a growing batch does not reallocate often
-    hipError_t reserve_exact(size_t bytes);   // key material, tables, the work counter: fixed sizes
-    void release();
-    explicit operator bool() const { return ptr != nullptr; }
-    template <class T> T *as() const { return reinterpret_cast<T *>(ptr); }
-};
 
 // the arithmetics fhs_set_arithmetic selects (FHS_ARITH_*, include/fhestring_hip.h)
 constexpr int N_ARITH = 4;
@@ -44,9 +29,9 @@ struct FftTablePtrs {
 
 // HIP-event timing of the two PBS kernels on the stream they are launched on
 struct KernelTimer {
-    struct Pending { hipEvent_t e0, e1; int kind; uint64_t units; uint32_t launches; };
+    struct Pending { Event e0, e1; int kind; uint64_t units; uint32_t launches; };
     std::vector<Pending> pending;
-    std::vector<hipEvent_t> pool;
+    std::vector<Event> pool;         // resolved events wait here for the next launch; they go with the timer
     // 0 = blind rotation (exact NTT kernel, or the 2-wavefront FFT kernel), 1 = keyswitch,
     // 2 = blind rotation on the 4-wavefront FFT kernel (batches <= fft4_max_batch)
     double ms[3] = {0, 0, 0};
@@ -54,18 +39,17 @@ struct KernelTimer {
                                      // the per-launch average then is what `rocprofv3 --kernel-trace --stats` reports per kernel)
     uint64_t units[3] = {0, 0, 0};   // PBS covered by the timed launches
     bool enabled = true;
-    hipEvent_t get();
+    Event get();
     void begin(int kind, uint64_t units, hipStream_t s);
     void end(hipStream_t s, uint32_t kernel_launches = 1);
     void resolve();   // synchronises pending events and accumulates
     void reset();
-    void destroy();
 };
 
 class Context {
   public:
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;                   // declared before every buffer: the buffers go first, then the stream
     std::string err;
     bool key_loaded = false;
 
@@ -114,7 +98,7 @@ class Context {
     KernelTimer timer;
 
     int init(int device_id);
-    void shutdown();
+    ~Context();                      // waits for the stream, closes the exchange, resolves the timer; then the members go
     int fail(int code, const std::string &msg) { err = msg; return code; }
     int hip_fail(hipError_t e, const char *what);
 

@@ -101,25 +101,18 @@ int Dist::all_gather(const void *d_send, void *d_recv, size_t bytes, hipStream_t
     }
     if (!host_fn_) { err = "no distributed transport (call fhs_dist_init first)"; return -3; }
     const size_t total = bytes * (size_t)world;
-    if (h_cap_ < total) {
-        if (h_send_) (void)hipHostFree(h_send_);
-        if (h_recv_) (void)hipHostFree(h_recv_);
-        h_send_ = h_recv_ = nullptr;
-        h_cap_ = 0;
-        if (hipHostMalloc(&h_send_, total) != hipSuccess || hipHostMalloc(&h_recv_, total) != hipSuccess) {
-            err = "hipHostMalloc (exchange staging) failed";
-            return -2;
-        }
-        h_cap_ = total;
+    if (h_send_.reserve_exact(total) != hipSuccess || h_recv_.reserve_exact(total) != hipSuccess) {
+        err = "hipHostMalloc (exchange staging) failed";
+        return -2;
     }
-    hipError_t e = hipMemcpyAsync(h_send_, d_send, bytes, hipMemcpyDeviceToHost, s);
+    hipError_t e = hipMemcpyAsync(h_send_.ptr, d_send, bytes, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { err = std::string("exchange download: ") + hipGetErrorString(e); return -2; }
-    if (int rc = host_fn_(host_user_, h_send_, h_recv_, bytes)) {
+    if (int rc = host_fn_(host_user_, h_send_.ptr, h_recv_.ptr, bytes)) {
         err = "host all-gather callback failed (" + std::to_string(rc) + ")";
         return -2;
     }
-    e = hipMemcpyAsync(d_recv, h_recv_, total, hipMemcpyHostToDevice, s);
+    e = hipMemcpyAsync(d_recv, h_recv_.ptr, total, hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);   // the staging buffer is reused by the next exchange
     if (e != hipSuccess) { err = std::string("exchange upload: ") + hipGetErrorString(e); return -2; }
     return 0;
@@ -134,10 +127,8 @@ void Dist::shutdown(bool abort) {
     else if (comm_ && rccl().CommAbort) (void)rccl().CommAbort(comm_);
     comm_ = nullptr;
     host_fn_ = nullptr;
-    if (h_send_) (void)hipHostFree(h_send_);
-    if (h_recv_) (void)hipHostFree(h_recv_);
-    h_send_ = h_recv_ = nullptr;
-    h_cap_ = 0;
+    h_send_.release();
+    h_recv_.release();
     rank = 0;
     world = 1;
     n_gathers = bytes_sent = 0;

@@ -9,6 +9,8 @@
 #include <cstddef>
 #include <string>
 
+#include "hip_owners.h"
+
 namespace fhs {
 
 typedef int (*HostAllGatherFn)(void *user, const void *send, void *recv, size_t bytes_per_rank);
@@ -35,8 +37,7 @@ class Dist {
     void *comm_ = nullptr;            // ncclComm_t
     HostAllGatherFn host_fn_ = nullptr;
     void *host_user_ = nullptr;
-    void *h_send_ = nullptr, *h_recv_ = nullptr;
-    size_t h_cap_ = 0;
+    PinnedBuf h_send_, h_recv_;       // staging of the host transport
 };
 
 }  // namespace fhs

@@ -1,87 +1,43 @@
 #include "engine.h"
-#include "pack_kernels.h"
 #include "../../include/fhestring_hip.h"
-#include "pk_kernels.h"
-#include "seeded_kernels.h"
-#include "store_kernels.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <thread>
 #include <map>
 
 namespace fhs {
-
-namespace {
-constexpr size_t POOL_STRIDE = 2050;        // u64 words per pooled block (16-byte aligned rows)
-constexpr size_t POOL_CHUNK_BLOCKS = 2048;  // 33.6 MB per hipMalloc
-}  // namespace
 
 int Engine::on_key_loaded() {
     if (!d_luts_) {
         std::vector<uint64_t> host((size_t)LUT_COUNT * POLY_N);
         for (int id = 0; id < LUT_COUNT; id++) make_lut_poly(id, host.data() + (size_t)id * POLY_N);
-        hipError_t e = hipMalloc(&d_luts_, host.size() * 8);
+        hipError_t e = d_luts_.reserve_exact(host.size() * 8);
         if (e != hipSuccess) return ctx.hip_fail(e, "hipMalloc luts");
-        e = hipMemcpy(d_luts_, host.data(), host.size() * 8, hipMemcpyHostToDevice);
+        e = hipMemcpy(d_luts_.ptr, host.data(), host.size() * 8, hipMemcpyHostToDevice);
         if (e != hipSuccess) return ctx.hip_fail(e, "copy luts");
     }
     return 0;
 }
 
-void Engine::shutdown() {
-    if (planner) return;
-    if (ctx.stream) (void)hipStreamSynchronize(ctx.stream);
-    for (void *c : chunks_) (void)hipFree(c);
-    chunks_.clear();
-    free_blocks_.clear();
-    if (d_luts_) (void)hipFree(d_luts_);
-    d_luts_ = nullptr;
-    if (last_group_done_) (void)hipEventDestroy(last_group_done_);
-    last_group_done_ = nullptr;
-    if (upload_done_) (void)hipEventDestroy(upload_done_);
-    upload_done_ = nullptr;
-    if (upload_pin_) (void)hipHostFree(upload_pin_);
-    if (upload_dev_) (void)hipFree(upload_dev_);
-    upload_pin_ = upload_dev_ = nullptr;
-    upload_words_ = 0;
-    for (Staging &c : staging_) {
-        if (c.done) (void)hipEventDestroy(c.done);
-        if (c.p) (void)hipHostFree(c.p);
-    }
-    staging_.clear();
-    store_.clear();                                  // entries die with the context
-    plan_buf_.release();
-    tick_buf_.release();
-    batch_in_.release();
-    ctx.shutdown();
+Engine::~Engine() {
+    if (!planner && ctx.stream) (void)hipStreamSynchronize(ctx.stream);
 }
 
-uint64_t *Engine::alloc_block() {
-    if (planner) {                                   // distinct non-null tokens, never dereferenced
-        live_dev_blocks_++;
-        return reinterpret_cast<uint64_t *>((uintptr_t)0x1000 + 8 * (uintptr_t)(++planner_tokens_));
-    }
-    if (free_blocks_.empty()) {
-        void *c = nullptr;
-        if (hipMalloc(&c, POOL_CHUNK_BLOCKS * POOL_STRIDE * 8) != hipSuccess) return nullptr;
-        chunks_.push_back(c);
-        uint64_t *base = static_cast<uint64_t *>(c);
-        for (size_t i = POOL_CHUNK_BLOCKS; i-- > 0;) free_blocks_.push_back(base + i * POOL_STRIDE);
-    }
-    uint64_t *p = free_blocks_.back();
-    free_blocks_.pop_back();
-    live_dev_blocks_++;
-    return p;
+bool BlockPool::grow() {
+    DevBuf c;
+    if (c.reserve_exact(CHUNK_BLOCKS * STRIDE * 8) != hipSuccess) return false;
+    uint64_t *base = c.as<uint64_t>();
+    for (size_t i = CHUNK_BLOCKS; i-- > 0;) free_.push_back(base + i * STRIDE);
+    chunks_.push_back(std::move(c));
+    return true;
 }
-void Engine::free_block(uint64_t *p) {
-    // A scheduled job level that has not been enqueued yet may still read this block: it becomes reusable once every
-    // tick scheduled so far is in the stream (stream order then protects the readers).
-    if (!planner && last_sched_tick_ >= next_tick_) free_after_[last_sched_tick_].push_back(p);
-    else if (!planner) free_blocks_.push_back(p);
-    live_dev_blocks_--;
+void BlockPool::tick_enqueued(uint64_t tick) {
+    while (!free_after_.empty() && free_after_.begin()->first <= tick) {
+        for (uint64_t *p : free_after_.begin()->second) free_.push_back(p);
+        free_after_.erase(free_after_.begin());
+    }
 }
 
 Bid Engine::new_node() {
@@ -132,217 +88,6 @@ Bid Engine::triv(int v) {
     Bid id = new_node();
     nodes_[id].kind = BlockNode::TRIV;
     nodes_[id].triv = (uint8_t)(v & 31);
-    return id;
-}
-
-Bid Engine::from_host(const uint64_t *ct) {
-    if (!planner) (void)hipSetDevice(ctx.device);   // one process may see several GPUs (torch sets its own current device)
-    uint64_t *d = alloc_block();
-    if (!d) return 0;
-    if (!planner && hipMemcpyAsync(d, ct, BIG_CT * 8, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) {
-        free_block(d);
-        return 0;
-    }
-    Bid id = new_node();
-    nodes_[id].kind = BlockNode::MAT;
-    nodes_[id].dev = d;
-    if (planner && trace_plan) { trace_.push_back(TR_UPLOAD); trace_.push_back((uint64_t)(uintptr_t)d); }
-    return id;
-}
-
-// pinned host buffer + device mirror for `n_blocks` rows and their pointer table (uploads and downloads of whole strings)
-bool Engine::ensure_staging(size_t n_blocks) {
-    const size_t words = n_blocks * BIG_CT + n_blocks;
-    if (upload_words_ < words) {
-        if (upload_done_) (void)hipEventSynchronize(upload_done_);
-        if (upload_pin_) (void)hipHostFree(upload_pin_);
-        if (upload_dev_) { (void)hipStreamSynchronize(ctx.stream); (void)hipFree(upload_dev_); }
-        upload_pin_ = upload_dev_ = nullptr;
-        upload_words_ = 0;
-        table_cursor_ = TABLE_CURSOR_RESET;
-        const size_t want = std::max<size_t>(n_blocks, 260) * (BIG_CT + 1);
-        void *hp = nullptr, *dp = nullptr;
-        if (hipHostMalloc(&hp, want * 8, hipHostMallocDefault) == hipSuccess && hipMalloc(&dp, want * 8) == hipSuccess) {
-            upload_pin_ = static_cast<uint64_t *>(hp);
-            upload_dev_ = static_cast<uint64_t *>(dp);
-            upload_words_ = want;
-        } else {
-            if (hp) (void)hipHostFree(hp);
-            if (dp) (void)hipFree(dp);
-        }
-    }
-    return upload_pin_ && (upload_done_ || hipEventCreateWithFlags(&upload_done_, hipEventDisableTiming) == hipSuccess);
-}
-
-// ---- whole-string uploads: what the three variants share -----------------------------------------------------------
-int Engine::undo_upload(Bid *out, size_t count) {
-    for (size_t i = 0; i < count; i++) {
-        if (out[i]) release(out[i]);
-        out[i] = 0;
-    }
-    return -1;
-}
-
-// `n` fresh pool blocks as MAT nodes in out[0..n); their device pointers go to ptrs[0..n) (the pass's pointer table in
-// the pinned buffer).  false: the pool is exhausted (the caller undoes the whole upload).
-bool Engine::new_mat_blocks(size_t n, Bid *out, uint64_t *ptrs) {
-    for (size_t k = 0; k < n; k++) {
-        uint64_t *d = alloc_block();
-        if (!d) return false;
-        out[k] = new_node();
-        nodes_[out[k]].kind = BlockNode::MAT;
-        nodes_[out[k]].dev = d;
-        ptrs[k] = (uint64_t)(uintptr_t)d;
-    }
-    return true;
-}
-
-// the planner's upload: blocks and nodes only, one TR_UPLOAD per block in block order
-int Engine::plan_upload(size_t count, Bid *out) {
-    for (size_t i = 0; i < count; i++) {
-        uint64_t tok = 0;
-        (void)new_mat_blocks(1, out + i, &tok);
-        if (trace_plan) { trace_.push_back(TR_UPLOAD); trace_.push_back(tok); }
-    }
-    return 0;
-}
-
-// One pass through the pinned buffer.  begin: the buffer holds `rows` full rows (0: its minimum size, 533 k words) and
-// the previous copy has left it.  send: the pass's `n` blocks are allocated, their pointers written at word `ptr_at`,
-// `words` words copied to the device mirror and the event behind the copy recorded.
-bool Engine::begin_pass(size_t rows) {
-    if (!ensure_staging(std::max<size_t>(rows, 1))) return false;
-    (void)hipEventSynchronize(upload_done_);         // (no-op before the first copy)
-    table_cursor_ = TABLE_CURSOR_RESET;              // the pass writes the buffer from word 0
-    return true;
-}
-// A pass that sends a pointer table ALONE (store_get): consecutive passes take consecutive segments of the pinned buffer
-// and of its device mirror, so the host only waits when the buffer wraps (or after a pass of the other kind).  The copy
-// of a table is queued behind everything on the stream, a whole launch group included: waiting for the previous table
-// before writing the next one would tie a caller that restores string k + 1 while the GPU works on string k (fhs_submit /
-// fhs_pump) to the GPU's pace.
-bool Engine::begin_table_pass(size_t n, size_t &at) {
-    if (!ensure_staging(1) || n > upload_words_) return false;
-    if (table_cursor_ == TABLE_CURSOR_RESET || table_cursor_ + n > upload_words_) {
-        (void)hipEventSynchronize(upload_done_);
-        table_cursor_ = 0;
-    }
-    at = table_cursor_;
-    table_cursor_ += n;
-    return true;
-}
-bool Engine::send_table_pass(size_t n, Bid *out, size_t at) {
-    if (!new_mat_blocks(n, out, upload_pin_ + at)) return false;
-    if (hipMemcpyAsync(upload_dev_ + at, upload_pin_ + at, n * 8, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) return false;
-    (void)hipEventRecord(upload_done_, ctx.stream);
-    return true;
-}
-bool Engine::send_pass(size_t n, Bid *out, size_t ptr_at, size_t words) {
-    if (!new_mat_blocks(n, out, upload_pin_ + ptr_at)) return false;
-    if (hipMemcpyAsync(upload_dev_, upload_pin_, words * 8, hipMemcpyHostToDevice, ctx.stream) != hipSuccess) return false;
-    (void)hipEventRecord(upload_done_, ctx.stream);
-    return true;
-}
-
-int Engine::from_host_many(const uint64_t *cts, size_t count, Bid *out) {
-    for (size_t i = 0; i < count; i++) out[i] = 0;
-    auto one_by_one = [&](size_t from) {
-        for (size_t i = from; i < count; i++)
-            if (!(out[i] = from_host(cts + i * BIG_CT))) return undo_upload(out, count);
-        return 0;
-    };
-    if (planner || count < 4) return one_by_one(0);
-    (void)hipSetDevice(ctx.device);
-    // staging: [count x 2049 words][count destination pointers], pinned on the host and mirrored on the device: one copy,
-    // one scatter launch (pool blocks are not neighbours once the free list has been through a few operations)
-    constexpr size_t MAX_BATCH = 2048;               // 33.6 MB per pass
-    for (size_t done = 0, n; done < count; done += n) {
-        n = std::min(MAX_BATCH, count - done);
-        if (!begin_pass(n)) return one_by_one(done);                 // no staging memory: block by block
-        {
-            // pageable -> pinned: one thread copies ~10 GB/s, which for the 537 MB of two 4097-character strings is as long
-            // as their (threaded) client encryption; large passes are split over a few host threads
-            const size_t bytes = n * BIG_CT * 8;
-            const unsigned nt = bytes >= ((size_t)8 << 20) ? std::min(8u, std::max(1u, std::thread::hardware_concurrency())) : 1;
-            if (nt <= 1) {
-                std::memcpy(upload_pin_, cts + done * BIG_CT, bytes);
-            } else {
-                const char *src = reinterpret_cast<const char *>(cts + done * BIG_CT);
-                char *dst = reinterpret_cast<char *>(upload_pin_);
-                const size_t part = (bytes / nt + 4095) & ~(size_t)4095;
-                std::vector<std::thread> th;
-                for (unsigned t = 1; t < nt; t++) {
-                    const size_t lo = std::min(bytes, t * part), hi = std::min(bytes, (t + 1) * part);
-                    if (hi > lo) th.emplace_back([=] { std::memcpy(dst + lo, src + lo, hi - lo); });
-                }
-                std::memcpy(dst, src, std::min(bytes, part));
-                for (auto &x : th) x.join();
-            }
-        }
-        if (!send_pass(n, out + done, n * BIG_CT, n * BIG_CT + n) ||
-            launch_scatter_blocks(upload_dev_, reinterpret_cast<uint64_t *const *>(upload_dev_ + n * BIG_CT), (int)n, ctx.stream) != hipSuccess)
-            return undo_upload(out, count);
-    }
-    return 0;
-}
-
-int Engine::from_compressed_many(const uint32_t seed[8], const uint64_t *bodies, size_t count, uint64_t first_block,
-                                 Bid *out) {
-    for (size_t i = 0; i < count; i++) out[i] = 0;
-    if (planner) return plan_upload(count, out);
-    (void)hipSetDevice(ctx.device);
-    SeedKey key;
-    for (int i = 0; i < 8; i++) key.w[i] = seed[i];
-    // staging: [n bodies][n destination pointers] (16 B per block) in the pinned buffer of from_host_many: 4096 blocks
-    // per pass
-    constexpr size_t MAX_BATCH = 4096;
-    for (size_t done = 0, n; done < count; done += n) {
-        n = std::min(MAX_BATCH, count - done);
-        if (!begin_pass(0)) return undo_upload(out, count);
-        std::memcpy(upload_pin_, bodies + done, n * 8);
-        if (!send_pass(n, out + done, n, 2 * n) ||
-            launch_expand_seeded_blocks(key, first_block + done, upload_dev_, (int)n, ctx.stream) != hipSuccess)
-            return undo_upload(out, count);
-    }
-    return 0;
-}
-
-int Engine::from_public_many(const uint32_t *mask32, const uint32_t *body32, size_t count, uint64_t first_block, Bid *out) {
-    for (size_t i = 0; i < count; i++) out[i] = 0;
-    if (planner) return plan_upload(count, out);
-    (void)hipSetDevice(ctx.device);
-    // staging, in the pinned buffer of from_host_many: [n destination pointers][n u32 bodies][u32 masks of the groups
-    // the pass touches, 2048 each] -- at most three groups for 4096 blocks
-    constexpr size_t MAX_BATCH = 4096;
-    for (size_t done = 0, n; done < count; done += n) {
-        n = std::min(MAX_BATCH, count - done);
-        const uint64_t t0 = first_block + done;
-        const size_t g0 = (size_t)(t0 / FHS_PK_GROUP), groups = (size_t)((t0 + n - 1) / FHS_PK_GROUP) - g0 + 1;
-        const size_t body_at = n, mask_at = n + (n + 1) / 2, words = mask_at + groups * (BIG_N / 2);
-        if (!begin_pass(0)) return undo_upload(out, count);
-        std::memcpy(upload_pin_ + body_at, body32 + t0, n * 4);
-        std::memcpy(upload_pin_ + mask_at, mask32 + g0 * BIG_N, groups * BIG_N * 4);
-        if (!send_pass(n, out + done, 0, words) ||
-            launch_expand_public_blocks(reinterpret_cast<const uint32_t *>(upload_dev_ + mask_at),
-                                        reinterpret_cast<const uint32_t *>(upload_dev_ + body_at),
-                                        reinterpret_cast<uint64_t *const *>(upload_dev_), (uint32_t)(t0 % FHS_PK_GROUP), (int)n,
-                                        ctx.stream) != hipSuccess)
-            return undo_upload(out, count);
-    }
-    return 0;
-}
-
-Bid Engine::from_device(const uint64_t *d_ct) {
-    if (!planner) (void)hipSetDevice(ctx.device);
-    uint64_t *d = alloc_block();
-    if (!d) return 0;
-    if (!planner && hipMemcpyAsync(d, d_ct, BIG_CT * 8, hipMemcpyDeviceToDevice, ctx.stream) != hipSuccess) {
-        free_block(d);
-        return 0;
-    }
-    Bid id = new_node();
-    nodes_[id].kind = BlockNode::MAT;
-    nodes_[id].dev = d;
     return id;
 }
 
@@ -516,8 +261,8 @@ Bid Engine::pbs(Bid x, int lut) {
         bool go = ready >= auto_flush_pending;
         peel_limit_ = 0;
         const size_t round = balance_slots ? balance_slots : 1024;
-        if (!go && ready >= round && !planner && !level_parallel && last_group_done_ && (++idle_poll_ & 255) == 0) {
-            go = hipEventQuery(last_group_done_) == hipSuccess;
+        if (!go && ready >= round && !planner && !level_parallel && last_group_done_.peek() && (++idle_poll_ & 255) == 0) {
+            go = hipEventQuery(last_group_done_.peek()) == hipSuccess;
             // an idle GPU gets whole rounds of the persistent kernel only: 1 191 ready rows launched as they are cost two
             // rounds; the remainder stays pending (it is ready, and joins the next launch)
             peel_limit_ = ready / round * round;
@@ -973,11 +718,7 @@ int Engine::pump(size_t n_ticks) {
         sched_.erase(first);
         if (int rc = run_tick(levels)) return rc;
         next_tick_ = tick + 1;
-        // blocks freed while ticks <= `tick` were still pending are safe to hand out now
-        while (!free_after_.empty() && free_after_.begin()->first <= tick) {
-            for (uint64_t *p : free_after_.begin()->second) free_blocks_.push_back(p);
-            free_after_.erase(free_after_.begin());
-        }
+        pool_.tick_enqueued(tick);
     }
     if (sched_.empty() && last_sched_tick_ >= next_tick_) next_tick_ = last_sched_tick_ + 1;
     return 0;
@@ -986,25 +727,19 @@ int Engine::pump(size_t n_ticks) {
 int Engine::upload_plan(void *d_dst, const void *src, size_t bytes) {
     Staging *st = nullptr;
     for (Staging &c : staging_)
-        if (!c.busy || hipEventQuery(c.done) == hipSuccess) { c.busy = false; if (!st || c.cap >= bytes) st = &c; }
+        if (!c.busy || hipEventQuery(c.done.peek()) == hipSuccess) { c.busy = false; if (!st || c.buf.cap >= bytes) st = &c; }
     if (!st && staging_.size() < 8) { staging_.emplace_back(); st = &staging_.back(); }
     if (!st) {                                           // every buffer is in flight: wait for the oldest
         st = &staging_[0];
-        if (hipEventSynchronize(st->done) != hipSuccess) return ctx.fail(-2, "staging wait failed");
+        if (hipEventSynchronize(st->done.peek()) != hipSuccess) return ctx.fail(-2, "staging wait failed");
         st->busy = false;
     }
-    if (st->cap < bytes) {
-        if (st->p) (void)hipHostFree(st->p);
-        st->p = nullptr; st->cap = 0;
-        const size_t want = std::max(bytes + bytes / 2, (size_t)1 << 20);
-        if (hipHostMalloc(&st->p, want) != hipSuccess) return ctx.fail(-2, "hipHostMalloc (plan staging) failed");
-        st->cap = want;
-    }
-    if (!st->done && hipEventCreateWithFlags(&st->done, hipEventDisableTiming) != hipSuccess)
-        return ctx.fail(-2, "hipEventCreate failed");
-    std::memcpy(st->p, src, bytes);
-    hipError_t e = hipMemcpyAsync(d_dst, st->p, bytes, hipMemcpyHostToDevice, ctx.stream);
-    if (e == hipSuccess) e = hipEventRecord(st->done, ctx.stream);
+    if (st->buf.cap < bytes && st->buf.reserve(bytes + bytes / 2) != hipSuccess)      // (at least 1 MB)
+        return ctx.fail(-2, "hipHostMalloc (plan staging) failed");
+    if (!st->done.get()) return ctx.fail(-2, "hipEventCreate failed");
+    std::memcpy(st->buf.ptr, src, bytes);
+    hipError_t e = hipMemcpyAsync(d_dst, st->buf.ptr, bytes, hipMemcpyHostToDevice, ctx.stream);
+    if (e == hipSuccess) e = hipEventRecord(st->done.peek(), ctx.stream);
     if (e != hipSuccess) return ctx.hip_fail(e, "plan upload");
     st->busy = true;
     return 0;
@@ -1064,15 +799,15 @@ Engine::GroupView Engine::pack_group(const TickLevel *levels, size_t n_levels, s
 
 // room for a group of `width` rows whose packed form takes `bytes`; a buffer that grows waits for the stream (queued
 // launches read the old one)
+hipError_t Engine::grow_synced(DevBuf &b, size_t want) {
+    if (b.cap >= want) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(ctx.stream);
+    return e == hipSuccess ? b.reserve(want) : e;
+}
 int Engine::ensure_group_buffers(size_t width, size_t bytes) {
-    auto grow = [&](DevBuf &b, size_t want) {
-        if (b.cap >= want) return hipSuccess;
-        hipError_t e = hipStreamSynchronize(ctx.stream);
-        return e == hipSuccess ? b.reserve(want) : e;
-    };
-    hipError_t e = grow(tick_buf_, bytes);
-    if (e == hipSuccess) e = grow(batch_in_, width * BIG_CT * 8);
-    if (e == hipSuccess) e = grow(ctx.ks_buf, width * SMALL_CT * 8);
+    hipError_t e = grow_synced(tick_buf_, bytes);
+    if (e == hipSuccess) e = grow_synced(batch_in_, width * BIG_CT * 8);
+    if (e == hipSuccess) e = grow_synced(ctx.ks_buf, width * SMALL_CT * 8);
     return e == hipSuccess ? 0 : ctx.hip_fail(e, "tick buffers");
 }
 
@@ -1127,7 +862,7 @@ int Engine::launch_rows(const GroupView &v, size_t lo, size_t cnt, uint64_t *den
         row0 += w;
     }
     if (int rc = ctx.keyswitch(batch_in_.as<uint64_t>(), cnt, ctx.stream)) return rc;
-    return ctx.blind_rotate(ctx.ks_buf.as<uint64_t>(), d_lut + lo, d_luts_, dense_out, dense_out ? nullptr : d_out + lo, cnt,
+    return ctx.blind_rotate(ctx.ks_buf.as<uint64_t>(), d_lut + lo, d_luts_.as<uint64_t>(), dense_out, dense_out ? nullptr : d_out + lo, cnt,
                             ctx.stream, v.n_ext && !dense_out ? d_body + lo : nullptr);
 }
 
@@ -1197,12 +932,9 @@ int Engine::run_tick(std::vector<TickLevel> &levels, bool sharded) {
             free_bodies();
         }
     } else {
-        if (ctx.xchg_send.cap < cap * BIG_CT * 8 || ctx.xchg_recv.cap < world * cap * BIG_CT * 8) {
-            hipError_t e = hipStreamSynchronize(ctx.stream);
-            if (e == hipSuccess) e = ctx.xchg_send.reserve(cap * BIG_CT * 8);
-            if (e == hipSuccess) e = ctx.xchg_recv.reserve(world * cap * BIG_CT * 8);
-            if (e != hipSuccess) return ctx.hip_fail(e, "level exchange buffers");
-        }
+        hipError_t e = grow_synced(ctx.xchg_send, cap * BIG_CT * 8);
+        if (e == hipSuccess) e = grow_synced(ctx.xchg_recv, world * cap * BIG_CT * 8);
+        if (e != hipSuccess) return ctx.hip_fail(e, "level exchange buffers");
         if (cnt)
             if (int rc = launch_rows(v, lo, cnt, ctx.xchg_send.as<uint64_t>(), nullptr, 0, 0)) return rc;
         if (int rc = ctx.dist.all_gather(ctx.xchg_send.ptr, ctx.xchg_recv.ptr, cap * BIG_CT * 8, ctx.stream, ctx.err)) return rc;
@@ -1210,8 +942,7 @@ int Engine::run_tick(std::vector<TickLevel> &levels, bool sharded) {
                                   reinterpret_cast<uint64_t *const *>(tick_buf_.as<uint8_t>() + v.off_out), width))
             return rc;
     }
-    if (!last_group_done_) (void)hipEventCreateWithFlags(&last_group_done_, hipEventDisableTiming);
-    if (last_group_done_) (void)hipEventRecord(last_group_done_, ctx.stream);
+    if (hipEvent_t done = last_group_done_.get()) (void)hipEventRecord(done, ctx.stream);
     return 0;
 }
 
@@ -1268,12 +999,9 @@ int Engine::gather_blocks(const Bid *local, size_t n, std::vector<Bid> &out) {
         return 0;
     }
     if (hipSetDevice(ctx.device) != hipSuccess) return ctx.fail(-2, "hipSetDevice failed");
-    if (ctx.xchg_send.cap < n * row || ctx.xchg_recv.cap < world * n * row) {
-        hipError_t e = hipStreamSynchronize(ctx.stream);
-        if (e == hipSuccess) e = ctx.xchg_send.reserve(n * row);
-        if (e == hipSuccess) e = ctx.xchg_recv.reserve(world * n * row);
-        if (e != hipSuccess) return ctx.hip_fail(e, "exchange buffers");
-    }
+    hipError_t e = grow_synced(ctx.xchg_send, n * row);
+    if (e == hipSuccess) e = grow_synced(ctx.xchg_recv, world * n * row);
+    if (e != hipSuccess) return ctx.hip_fail(e, "exchange buffers");
     for (size_t k = 0; k < n; k++)
         if ((rc = copy_block_to_device(local[k], ctx.xchg_send.as<uint64_t>() + k * BIG_CT, false, false))) return rc;
     if ((rc = ctx.dist.all_gather(ctx.xchg_send.ptr, ctx.xchg_recv.ptr, n * row, ctx.stream, ctx.err))) return rc;
@@ -1350,409 +1078,6 @@ int Engine::commit_level(size_t k, const uint64_t *d_all) {
     }
     if (k + 1 == planned_.size()) planned_.clear();
     return 0;
-}
-
-int Engine::materialize_lin(Bid b) {
-    BlockNode &n = nodes_[b];
-    if (n.kind != BlockNode::LIN) return 0;
-    if (planner) return ctx.fail(-3, "planner context: nothing is computed");
-    std::vector<LinTerm> terms;
-    for (const Term &t : n.terms) {
-        const BlockNode &tb = nodes_[t.blk];
-        if (tb.kind != BlockNode::MAT) return ctx.fail(-3, "internal: lincomb term pending after flush");
-        terms.push_back({tb.dev, t.coef});
-    }
-    LinDesc d{0, (uint32_t)terms.size(), (uint64_t)(n.konst & 31) << DELTA_LOG};
-    const size_t total = sizeof(LinDesc) + terms.size() * sizeof(LinTerm);
-    std::vector<uint8_t> host(total);
-    std::memcpy(host.data(), &d, sizeof(d));
-    std::memcpy(host.data() + sizeof(d), terms.data(), terms.size() * sizeof(LinTerm));
-    hipError_t e = hipStreamSynchronize(ctx.stream);   // plan_buf_ may be in use by queued launches
-    if (e == hipSuccess) e = plan_buf_.reserve(total);
-    if (e == hipSuccess) e = hipMemcpyAsync(plan_buf_.ptr, host.data(), total, hipMemcpyHostToDevice, ctx.stream);
-    if (e != hipSuccess) return ctx.hip_fail(e, "materialize upload");
-    uint64_t *o = alloc_block();
-    if (!o) return ctx.fail(-2, "device block pool exhausted");
-    e = launch_lincomb(plan_buf_.as<LinDesc>(),
-                       reinterpret_cast<const LinTerm *>(plan_buf_.as<uint8_t>() + sizeof(LinDesc)), o, 1,
-                       ctx.stream);
-    if (e != hipSuccess) return ctx.hip_fail(e, "lincomb launch");
-    // the materialised block IS the linear combination: it keeps its noise (a download followed by further use of the
-    // same handle must not look like a fresh bootstrap output to the bookkeeping)
-    const int64_t v = sum_c2(b);
-    uint8_t packs = 0;                                // the largest packing count among the terms (string store)
-    for (const Term &t : n.terms) packs = std::max(packs, nodes_[t.blk].packs);
-    std::vector<Term> old;
-    old.swap(n.terms);
-    n.kind = BlockNode::MAT;
-    n.var = (uint16_t)std::min<int64_t>(std::max<int64_t>(v, 1), 65535);
-    n.dev = o;
-    n.level = 0;
-    n.packs = packs;
-    for (const Term &t : old) release(t.blk);
-    return 0;
-}
-
-int Engine::read_block(Bid b, uint64_t *host_out) {
-    if (planner) return ctx.fail(-3, "planner context: nothing is computed, there is nothing to download");
-    (void)hipSetDevice(ctx.device);
-    int rc = flush();
-    if (rc) return rc;
-    if (nodes_[b].kind == BlockNode::TRIV) {
-        std::memset(host_out, 0, BIG_CT * 8);
-        host_out[BIG_N] = (uint64_t)nodes_[b].triv << DELTA_LOG;
-        return 0;
-    }
-    if (nodes_[b].kind == BlockNode::LIN && (rc = materialize_lin(b))) return rc;
-    if (nodes_[b].kind != BlockNode::MAT) return ctx.fail(-3, "internal: block not materialised");
-    hipError_t e = hipMemcpyAsync(host_out, nodes_[b].dev, BIG_CT * 8, hipMemcpyDeviceToHost, ctx.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
-    if (e != hipSuccess) return ctx.hip_fail(e, "download");
-    return 0;
-}
-
-int Engine::read_many(const Bid *b, size_t count, uint64_t *host_out) {
-    if (planner) return ctx.fail(-3, "planner context: nothing is computed, there is nothing to download");
-    if (count == 0) return 0;
-    (void)hipSetDevice(ctx.device);
-    if (int rc = flush()) return rc;
-    for (size_t i = 0; i < count; i++)                               // linear combinations become blocks of their own first
-        if (nodes_[b[i]].kind == BlockNode::LIN)
-            if (int rc = materialize_lin(b[i])) return rc;
-    constexpr size_t MAX_BATCH = 2048;
-    for (size_t done = 0; done < count;) {
-        const size_t n = std::min(MAX_BATCH, count - done);
-        if (count < 4 || !ensure_staging(n)) {
-            // too few blocks to matter, or no staging memory: block by block
-            for (size_t i = done; i < done + n; i++)
-                if (int rc = read_block(b[i], host_out + i * BIG_CT)) return rc;
-            done += n;
-            continue;
-        }
-        if (upload_done_) (void)hipEventSynchronize(upload_done_);   // the staging buffer is shared with the uploads
-        size_t n_dev = 0;
-        for (size_t k = 0; k < n; k++) {
-            const BlockNode &nd = nodes_[b[done + k]];
-            if (nd.kind == BlockNode::TRIV) { upload_pin_[n * BIG_CT + k] = 0; continue; }
-            if (nd.kind != BlockNode::MAT) return ctx.fail(-3, "internal: block not materialised");
-            upload_pin_[n * BIG_CT + k] = (uint64_t)(uintptr_t)nd.dev;
-            n_dev++;
-        }
-        // trivial blocks have no device row: point them at the first real block (their rows are overwritten on the host)
-        uint64_t any = 0;
-        for (size_t k = 0; k < n && !any; k++) any = upload_pin_[n * BIG_CT + k];
-        if (n_dev) {
-            for (size_t k = 0; k < n; k++)
-                if (!upload_pin_[n * BIG_CT + k]) upload_pin_[n * BIG_CT + k] = any;
-            hipError_t e = hipMemcpyAsync(upload_dev_ + n * BIG_CT, upload_pin_ + n * BIG_CT, n * 8, hipMemcpyHostToDevice, ctx.stream);
-            if (e == hipSuccess)
-                e = launch_gather_rows(reinterpret_cast<const uint64_t *const *>(upload_dev_ + n * BIG_CT), upload_dev_, (int)n, ctx.stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(upload_pin_, upload_dev_, n * BIG_CT * 8, hipMemcpyDeviceToHost, ctx.stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
-            if (e != hipSuccess) return ctx.hip_fail(e, "download");
-            std::memcpy(host_out + done * BIG_CT, upload_pin_, n * BIG_CT * 8);
-        }
-        for (size_t k = 0; k < n; k++) {
-            const BlockNode &nd = nodes_[b[done + k]];
-            if (nd.kind != BlockNode::TRIV) continue;
-            uint64_t *row = host_out + (done + k) * BIG_CT;
-            std::memset(row, 0, BIG_CT * 8);
-            row[BIG_N] = (uint64_t)nd.triv << DELTA_LOG;
-        }
-        done += n;
-    }
-    return 0;
-}
-
-// ---- packing: what the packed download and the string store share --------------------------------------------------
-int Engine::prepare_packing(const Bid *b, size_t count) {
-    (void)hipSetDevice(ctx.device);
-    if (int rc = flush()) return rc;
-    for (size_t i = 0; i < count; i++)                               // as read_many: linear combinations become blocks first
-        if (nodes_[b[i]].kind == BlockNode::LIN)
-            if (int rc = materialize_lin(b[i])) return rc;
-    for (size_t i = 0; i < count; i++)
-        if (nodes_[b[i]].kind != BlockNode::TRIV && nodes_[b[i]].kind != BlockNode::MAT)
-            return ctx.fail(-3, "internal: block not materialised");
-    return 0;
-}
-
-// One pass: the leaf table of n blocks (groups = ceil(n / 2048) <= 4) and the 11 tree levels, enqueued on the stream;
-// the level-11 GLWEs [groups][2][2048] are left in ctx.pack_ws[0].
-// Level lv of a group writes (2048 >> lv) GLWEs of 32 KB: level 1 is 32 MB, level 2 16 MB, ping-pong between two
-// buffers; four groups in flight keep the workspace at 192 MB.
-hipError_t Engine::pack_tree_pass(const Bid *b, size_t n, size_t groups) {
-    constexpr size_t GLWE_BYTES = 2 * POLY_N * 8;
-    std::vector<PackLeaf> leaves(n);
-    for (size_t k = 0; k < n; k++) {
-        const BlockNode &nd = nodes_[b[k]];
-        if (nd.kind == BlockNode::TRIV) leaves[k] = {nullptr, (uint64_t)nd.triv << DELTA_LOG};
-        else leaves[k] = {nd.dev, 0};
-    }
-    hipError_t e = ctx.pack_tab.reserve(n * sizeof(PackLeaf));
-    if (e == hipSuccess) e = ctx.pack_ws[0].reserve(groups * (POLY_N / 2) * GLWE_BYTES);
-    if (e == hipSuccess) e = ctx.pack_ws[1].reserve(groups * (POLY_N / 4) * GLWE_BYTES);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(ctx.pack_tab.ptr, leaves.data(), n * sizeof(PackLeaf), hipMemcpyHostToDevice, ctx.stream);
-    for (int lv = 1; lv <= PACK_TREE_LEVELS && e == hipSuccess; lv++) {
-        PackLevelParams p{};
-        p.lv = lv; p.groups = (int)groups; p.total = (uint32_t)n;
-        p.leaves = ctx.pack_tab.as<PackLeaf>();
-        p.src = ctx.pack_ws[lv & 1].as<uint64_t>();
-        p.dst = ctx.pack_ws[(lv - 1) & 1].as<uint64_t>();
-        p.key_ntt = ctx.d_pack_key_ntt.as<double>(); p.tw = ctx.tw;
-        e = launch_pack_level(p, ctx.stream);
-    }
-    return e;
-}
-
-int Engine::read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *body16, uint64_t *mask64, uint64_t *body64) {
-    if (planner) return ctx.fail(-3, "planner context: nothing is computed, there is nothing to download");
-    if (!ctx.d_pack_key_ntt) return ctx.fail(-3, "packing key not loaded (fhs_load_packing_key)");
-    if (count == 0) return 0;
-    if (int rc = prepare_packing(b, count)) return rc;
-    constexpr size_t MAX_GROUPS = 4, GLWE_BYTES = 2 * POLY_N * 8;
-    std::vector<uint64_t> wide;
-    for (size_t done = 0; done < count;) {
-        const size_t n = std::min(MAX_GROUPS * PACK_GROUP, count - done);
-        const size_t groups = (n + PACK_GROUP - 1) / PACK_GROUP;
-        hipError_t e = ctx.pack_out.reserve(groups * 2 * PACK_GROUP * sizeof(uint16_t));
-        if (e == hipSuccess) e = pack_tree_pass(b + done, n, groups);
-        uint16_t *d_mask = ctx.pack_out.as<uint16_t>(), *d_body = d_mask + groups * PACK_GROUP;
-        if (e == hipSuccess) e = launch_pack_switch16(ctx.pack_ws[0].as<uint64_t>(), d_mask, d_body, (int)groups, (uint32_t)n, ctx.stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(mask16 + done, d_mask, groups * PACK_GROUP * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(body16 + done, d_body, n * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx.stream);
-        if (e == hipSuccess && mask64 && body64) {
-            wide.resize(groups * 2 * POLY_N);
-            e = hipMemcpyAsync(wide.data(), ctx.pack_ws[0].ptr, groups * GLWE_BYTES, hipMemcpyDeviceToHost, ctx.stream);
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
-        if (e != hipSuccess) return ctx.hip_fail(e, "packed download");
-        if (mask64 && body64)
-            for (size_t g = 0; g < groups; g++) {
-                std::memcpy(mask64 + done + g * POLY_N, wide.data() + g * 2 * POLY_N, POLY_N * 8);
-                std::memcpy(body64 + done + g * POLY_N, wide.data() + (g * 2 + 1) * POLY_N, POLY_N * 8);
-            }
-        done += n;
-    }
-    return 0;
-}
-
-// ---- device-resident string store -------------------------------------------------------------------------------------
-const Engine::StoreEntry *Engine::store_entry(uint64_t id) const {
-    auto it = store_.find(id);
-    return it == store_.end() ? nullptr : &it->second;
-}
-
-void Engine::store_stats(size_t *entries, size_t *blocks, size_t *bytes) const {
-    size_t nb = 0, by = 0;
-    for (const auto &kv : store_) { nb += kv.second.n_blocks; by += kv.second.bytes(); }
-    if (entries) *entries = store_.size();
-    if (blocks) *blocks = nb;
-    if (bytes) *bytes = by;
-}
-
-int Engine::store_drop(uint64_t id) {
-    auto it = store_.find(id);
-    if (it == store_.end()) return ctx.fail(-1, "string store: unknown entry id");
-    if (it->second.buf) {                                            // a queued expansion may still read it
-        (void)hipSetDevice(ctx.device);
-        (void)hipStreamSynchronize(ctx.stream);
-    }
-    store_.erase(it);
-    return 0;
-}
-
-int Engine::store_put(const Bid *b, size_t count, uint64_t *id_out) {
-    if (!planner && !ctx.d_pack_key_ntt) return ctx.fail(-3, "packing key not loaded (fhs_load_packing_key)");
-    if (count == 0) return ctx.fail(-1, "string store: an entry holds at least one character");
-    if (planner) {
-        if (int rc = flush()) return rc;                             // sums stay sums on a planner: their figure is what counts
-    } else if (int rc = prepare_packing(b, count)) return rc;
-    // what the bookkeeping knows about every block (a sum that was just materialised carries its figure and the largest
-    // packing count of its terms; the planner's unmaterialised sum is read the same way)
-    StoreEntry ent;
-    ent.n_blocks = count;
-    ent.var.resize(count); ent.cycles.resize(count); ent.rot.resize(count);
-    for (size_t i = 0; i < count; i++) {
-        const BlockNode &nd = nodes_[b[i]];
-        int packs = 0;
-        if (nd.kind == BlockNode::MAT) packs = nd.packs;
-        else if (nd.kind == BlockNode::LIN)
-            for (const Term &t : nd.terms) packs = std::max<int>(packs, nodes_[t.blk].packs);
-        else if (nd.kind != BlockNode::TRIV) return ctx.fail(-3, "internal: block not materialised");
-        if (packs + 1 > STORE_MAX_CYCLES)
-            return ctx.fail(-4, "string store: a block would exceed FHS_STORE_MAX_CYCLES packings without a bootstrap in between");
-        // a trivial block is packed as the trivial leaf it is and comes back as an ordinary ciphertext
-        ent.var[i] = nd.kind == BlockNode::TRIV ? 1 : (uint16_t)std::min<int64_t>(std::max<int64_t>(sum_c2(b[i]), 1), 65535);
-        ent.cycles[i] = (uint8_t)(packs + 1);
-        ent.rot[i] = nd.kind == BlockNode::MAT ? nd.rot : 0;
-    }
-    if (!planner) {
-        hipError_t e = ent.buf.reserve_exact(ent.bytes());
-        uint32_t *mask32 = ent.buf.as<uint32_t>(), *body32 = mask32 + ent.groups() * POLY_N;
-        constexpr size_t MAX_GROUPS = 4;
-        for (size_t done = 0; done < count && e == hipSuccess;) {     // pass p starts at group 4 p of the entry
-            const size_t n = std::min(MAX_GROUPS * PACK_GROUP, count - done);
-            const size_t groups = (n + PACK_GROUP - 1) / PACK_GROUP;
-            e = pack_tree_pass(b + done, n, groups);
-            if (e == hipSuccess)
-                e = launch_store_switch32(ctx.pack_ws[0].as<uint64_t>(), mask32, body32, (uint32_t)(done / PACK_GROUP), (int)groups,
-                                          (uint32_t)n, ctx.stream);
-            done += n;
-        }
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
-        if (e != hipSuccess) return ctx.hip_fail(e, "string store: put");
-    }
-    const uint64_t id = ++store_ids_;
-    StoreEntry &dst = store_[id];
-    dst.n_blocks = ent.n_blocks;
-    std::swap(dst.buf.ptr, ent.buf.ptr); std::swap(dst.buf.cap, ent.buf.cap);
-    dst.var.swap(ent.var); dst.cycles.swap(ent.cycles); dst.rot.swap(ent.rot);
-    *id_out = id;
-    return 0;
-}
-
-int Engine::store_get(uint64_t id, size_t first, size_t count, Bid *out) {
-    const StoreEntry *ent = store_entry(id);
-    if (!ent) return ctx.fail(-1, "string store: unknown entry id");
-    if (first > ent->n_blocks || count > ent->n_blocks - first) return ctx.fail(-1, "string store: window outside the entry");
-    for (size_t i = 0; i < count; i++) out[i] = 0;
-    if (planner) {
-        (void)plan_upload(count, out);
-    } else {
-        (void)hipSetDevice(ctx.device);
-        const uint32_t *mask32 = ent->buf.as<uint32_t>(), *body32 = mask32 + ent->groups() * POLY_N;
-        // as from_public_many, but masks and bodies are already on the device: the pinned buffer carries the destination
-        // pointers alone (8 B per block)
-        constexpr size_t MAX_BATCH = 4096;
-        for (size_t done = 0, n; done < count; done += n) {
-            n = std::min(MAX_BATCH, count - done);
-            const size_t t0 = first + done, g0 = t0 / FHS_PK_GROUP;
-            size_t at = 0;
-            if (!begin_table_pass(n, at) || !send_table_pass(n, out + done, at) ||
-                launch_expand_public_blocks(mask32 + g0 * POLY_N, body32 + t0,
-                                            reinterpret_cast<uint64_t *const *>(upload_dev_ + at), (uint32_t)(t0 % FHS_PK_GROUP),
-                                            (int)n, ctx.stream) != hipSuccess) {
-                (void)undo_upload(out, count);
-                return ctx.fail(-2, "string store: get failed (device allocation, copy or expansion launch)");
-            }
-        }
-    }
-    for (size_t i = 0; i < count; i++) {
-        BlockNode &nd = nodes_[out[i]];
-        nd.var = ent->var[first + i];
-        nd.rot = ent->rot[first + i];
-        nd.packs = ent->cycles[first + i];
-    }
-    return 0;
-}
-
-int Engine::store_export(uint64_t id, uint32_t *mask32, uint32_t *body32, uint64_t *meta) {
-    const StoreEntry *ent = store_entry(id);
-    if (!ent) return ctx.fail(-1, "string store: unknown entry id");
-    if (planner) return ctx.fail(-3, "planner context: nothing is computed, there is nothing to export");
-    (void)hipSetDevice(ctx.device);
-    const size_t mask_bytes = ent->groups() * POLY_N * 4;
-    hipError_t e = hipMemcpyAsync(mask32, ent->buf.ptr, mask_bytes, hipMemcpyDeviceToHost, ctx.stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(body32, ent->buf.as<uint8_t>() + mask_bytes, ent->n_blocks * 4, hipMemcpyDeviceToHost, ctx.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
-    if (e != hipSuccess) return ctx.hip_fail(e, "string store: export");
-    std::unordered_map<uint32_t, uint32_t> local;                    // engine id -> 1..k in order of first appearance
-    for (size_t i = 0; i < ent->n_blocks; i++) {
-        uint64_t g = 0;
-        if (ent->rot[i]) {
-            auto it = local.find(ent->rot[i]);
-            g = it != local.end() ? it->second : (local[ent->rot[i]] = (uint32_t)local.size() + 1);
-        }
-        meta[i] = (uint64_t)ent->var[i] | (uint64_t)ent->cycles[i] << 16 | g << 32;
-    }
-    return 0;
-}
-
-int Engine::store_import(const uint32_t *mask32, const uint32_t *body32, const uint64_t *meta, size_t n_blocks, uint64_t *id_out) {
-    if (n_blocks == 0) return ctx.fail(-1, "string store: an entry holds at least one character");
-    StoreEntry ent;
-    ent.n_blocks = n_blocks;
-    ent.var.assign(n_blocks, 1); ent.cycles.assign(n_blocks, 0); ent.rot.assign(n_blocks, 0);
-    uint32_t k = 0;
-    if (meta) {
-        for (size_t i = 0; i < n_blocks; i++) {
-            const uint64_t var = meta[i] & 0xffff, cyc = (meta[i] >> 16) & 0xff, grp = meta[i] >> 32;
-            if (var < 1 || cyc > (uint64_t)STORE_MAX_CYCLES || (meta[i] >> 24 & 0xff) || grp > n_blocks)
-                return ctx.fail(-1, "string store: import refuses a meta word (var >= 1, cycles <= FHS_STORE_MAX_CYCLES, groups 1..k)");
-            ent.var[i] = (uint16_t)var; ent.cycles[i] = (uint8_t)cyc; ent.rot[i] = (uint32_t)grp;
-            k = std::max(k, (uint32_t)grp);
-        }
-    }
-    if (!planner) {
-        (void)hipSetDevice(ctx.device);
-        const size_t mask_bytes = ent.groups() * POLY_N * 4;
-        // mask32 and body32 are separate host arrays: each goes to its place in the ONE allocation
-        hipError_t e = ent.buf.reserve_exact(ent.bytes());
-        if (e == hipSuccess) e = hipMemcpyAsync(ent.buf.ptr, mask32, mask_bytes, hipMemcpyHostToDevice, ctx.stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(ent.buf.as<uint8_t>() + mask_bytes, body32, n_blocks * 4, hipMemcpyHostToDevice, ctx.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
-        if (e != hipSuccess) return ctx.hip_fail(e, "string store: import");
-    }
-    // the entry's k groups get k fresh engine ids, drawn once per entry
-    std::vector<uint32_t> fresh(k + 1, 0);
-    for (uint32_t g = 1; g <= k; g++) fresh[g] = ++rot_counter_ ? rot_counter_ : ++rot_counter_;
-    for (size_t i = 0; i < n_blocks; i++) ent.rot[i] = fresh[ent.rot[i]];
-    const uint64_t id = ++store_ids_;
-    StoreEntry &dst = store_[id];
-    dst.n_blocks = ent.n_blocks;
-    std::swap(dst.buf.ptr, ent.buf.ptr); std::swap(dst.buf.cap, ent.buf.cap);
-    dst.var.swap(ent.var); dst.cycles.swap(ent.cycles); dst.rot.swap(ent.rot);
-    *id_out = id;
-    return 0;
-}
-
-int Engine::copy_block_to_device(Bid b, uint64_t *d_out, bool wait, bool do_flush) {
-    if (planner) return ctx.fail(-3, "planner context: nothing is computed");
-    (void)hipSetDevice(ctx.device);
-    int rc = do_flush ? flush() : 0;
-    if (rc) return rc;
-    hipError_t e;
-    if (nodes_[b].kind == BlockNode::TRIV) {
-        // body = triv << 59: only its high word is non-zero, written by a 32-bit memset (no host buffer in flight)
-        const uint64_t body = (uint64_t)nodes_[b].triv << DELTA_LOG;
-        e = hipMemsetAsync(d_out, 0, BIG_CT * 8, ctx.stream);
-        if (e == hipSuccess)
-            e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(reinterpret_cast<uint32_t *>(d_out + BIG_N) + 1),
-                                  (int)(uint32_t)(body >> 32), 1, ctx.stream);
-    } else {
-        if (nodes_[b].kind == BlockNode::LIN && (rc = materialize_lin(b))) return rc;
-        if (nodes_[b].kind != BlockNode::MAT) return ctx.fail(-3, "internal: block not materialised");
-        e = hipMemcpyAsync(d_out, nodes_[b].dev, BIG_CT * 8, hipMemcpyDeviceToDevice, ctx.stream);
-    }
-    if (e == hipSuccess && wait) e = hipStreamSynchronize(ctx.stream);
-    if (e != hipSuccess) return ctx.hip_fail(e, "export");
-    return 0;
-}
-
-uint64_t Engine::new_char(const Bid b[4]) {
-    uint64_t h;
-    if (!free_chars_.empty()) {
-        h = free_chars_.back();
-        free_chars_.pop_back();
-    } else {
-        chars_.emplace_back();
-        h = chars_.size();
-    }
-    CharRec &c = chars_[h - 1];
-    for (int i = 0; i < 4; i++) c.b[i] = b[i];
-    c.used = true;
-    return h;
-}
-
-void Engine::free_char(uint64_t h) {
-    CharRec &c = chars_[h - 1];
-    for (int i = 0; i < 4; i++) release(c.b[i]);
-    c.used = false;
-    free_chars_.push_back(h);
 }
 
 }  // namespace fhs

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "context.h"
+#include "engine_resources.h"
 #include "luts.h"
 
 namespace fhs {
@@ -73,7 +74,9 @@ class Engine {
     bool planner = false;
 
     int on_key_loaded();
-    void shutdown();
+    // a real context waits for its stream (nothing queued may read what the members are about to free); a planner makes
+    // no HIP call
+    ~Engine();
 
     // ---- block graph (all returned ids carry one reference owned by the caller) ----
     Bid triv(int v);
@@ -184,7 +187,7 @@ class Engine {
     int store_import(const uint32_t *mask32, const uint32_t *body32, const uint64_t *meta, size_t n_blocks, uint64_t *id_out);
     // flushes if needed (do_flush = false: the caller has made sure the block's tick is enqueued); wait=false: enqueue only
     int copy_block_to_device(Bid b, uint64_t *d_out, bool wait = true, bool do_flush = true);
-    uint64_t blocks_live() const { return live_dev_blocks_; }
+    uint64_t blocks_live() const { return pool_.live(); }
 
     // ---- debug: capture of PBS inputs (the linear-combination results entering keyswitch) ----
     // Noise-margin tests download a sample of every level's inputs and measure their phase error with the client
@@ -224,30 +227,18 @@ class Engine {
     std::vector<CharRec> chars_;
     std::vector<uint64_t> free_chars_;
 
-    // device block pool
-    std::vector<void *> chunks_;
-    uint64_t *upload_pin_ = nullptr, *upload_dev_ = nullptr;   // staging of from_host_many: pinned host side, device side
-    size_t upload_words_ = 0;
-    hipEvent_t upload_done_ = nullptr;           // the last copy out of upload_pin_
-    std::vector<uint64_t *> free_blocks_;
-    uint64_t live_dev_blocks_ = 0;
-    uint64_t planner_tokens_ = 0;
-    bool ensure_staging(size_t n_blocks);
-    // whole-string uploads (from_host_many / from_compressed_many / from_public_many)
+    BlockPool pool_{planner};
+    uint64_t *alloc_block() { return pool_.alloc(); }
+    void free_block(uint64_t *p) { pool_.free(p, last_sched_tick_, next_tick_); }
+    // whole-string uploads (from_host_many / from_compressed_many / from_public_many) and store_get
+    TransferBuffer xfer_;
     int undo_upload(Bid *out, size_t count);                   // releases what was made, zeroes out[], returns -1
+    Bid copy_in(const uint64_t *src, hipMemcpyKind kind);
     bool new_mat_blocks(size_t n, Bid *out, uint64_t *ptrs);
     int plan_upload(size_t count, Bid *out);
-    bool begin_pass(size_t rows);
-    bool send_pass(size_t n, Bid *out, size_t ptr_at, size_t words);
-    static constexpr size_t TABLE_CURSOR_RESET = ~(size_t)0;
-    size_t table_cursor_ = TABLE_CURSOR_RESET;                 // next free word of the pinned buffer for a pointer-table pass
-    bool begin_table_pass(size_t n, size_t &at);
-    bool send_table_pass(size_t n, Bid *out, size_t at);
-    uint64_t *alloc_block();
-    void free_block(uint64_t *p);
+    bool send_pass(size_t n, Bid *out, size_t ptr_at, size_t at, size_t words);
 
-    // LUT table on device (catalogue)
-    uint64_t *d_luts_ = nullptr;
+    DevBuf d_luts_;                      // LUT table on device (catalogue)
     DevBuf plan_buf_, batch_in_;
 
     // rotation sharing (plan_job): a follower row is a further sample extraction of its leader's blind rotation
@@ -269,7 +260,6 @@ class Engine {
     std::vector<TickLevel> planned_;      // plan_flush: whole levels waiting for exec_level / commit_level
     size_t planned_max_width_ = 0;
     std::map<uint64_t, std::vector<TickLevel>> sched_;            // tick -> job levels to run in that launch group
-    std::map<uint64_t, std::vector<uint64_t *>> free_after_;      // blocks reusable once that tick has been enqueued
     uint64_t next_tick_ = 1, last_sched_tick_ = 0;
     bool manual_jobs_ = false;           // the caller schedules jobs itself (fhs_submit): no automatic partial flushes
     bool in_auto_flush_ = false;
@@ -279,6 +269,7 @@ class Engine {
     // ---- one launch group (engine.cpp): byte offsets of its packed form in tick_buf_ ----
     struct GroupView { size_t width = 0, n_ext = 0, off_terms = 0, off_lut = 0, off_out = 0, off_body = 0, off_ext = 0, total = 0; };
     GroupView pack_group(const TickLevel *levels, size_t n_levels, std::vector<uint8_t> &host) const;
+    hipError_t grow_synced(DevBuf &b, size_t want);      // a buffer that grows waits for the stream first
     int ensure_group_buffers(size_t width, size_t bytes);
     int upload_group(const TickLevel *levels, size_t n_levels, GroupView &v);
     int launch_rows(const GroupView &v, size_t lo, size_t cnt, uint64_t *dense_out, const TickLevel *levels, size_t n_levels,
@@ -316,12 +307,12 @@ class Engine {
     size_t depth1_rotations() const { return n_depth1_solo_ + depth1_keys_.size(); }
     void depth1_add(const BlockNode &n) { if (n.nk) depth1_keys_[n.nk]++; else n_depth1_solo_++; }
     size_t peel_limit_ = 0;              // automatic partial flush of an idle GPU: take this many ready rows (0 = all)
-    hipEvent_t last_group_done_ = nullptr;   // recorded behind every launch group: tells whether the GPU has run dry
+    Event last_group_done_{hipEventDisableTiming};   // recorded behind every launch group: tells whether the GPU has run dry
     uint32_t idle_poll_ = 0;
     // Pinned staging for plan uploads: a hipMemcpyAsync from PAGEABLE memory blocks the host until the stream reaches
     // the copy, i.e. until the previous launch group has finished -- the host could never plan ahead of the GPU.  A small
     // ring of pinned buffers, each guarded by an event recorded after its copy, keeps the upload asynchronous.
-    struct Staging { void *p = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool busy = false; };
+    struct Staging { PinnedBuf buf; Event done{hipEventDisableTiming}; bool busy = false; };
     std::vector<Staging> staging_;
     int upload_plan(void *d_dst, const void *src, size_t bytes);
 

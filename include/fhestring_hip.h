@@ -379,6 +379,11 @@ int fhs_debug_plan_trace(fhs_ctx *ctx, int on);
 int fhs_debug_plan_read(fhs_ctx *ctx, uint64_t *out, size_t cap, size_t *n);
 int fhs_debug_char_terms(fhs_ctx *ctx, fhs_char_t h, uint64_t *out, size_t cap, size_t *n);
 int fhs_debug_lut_poly(int lut_id, uint64_t *out);
+/* Process-wide figures of what THIS library holds through its resource owners (nothing of another library or process:
+ * the device-wide hipMemGetInfo cannot carry an exact assertion on a shared machine): out[0] live device bytes,
+ * out[1] live pinned host bytes, out[2] live events, out[3] live streams, out[4] acquisitions since process start.
+ * After every context is destroyed words 0..3 are zero; a planner context acquires nothing. */
+int fhs_debug_live_resources(uint64_t out[5]);
 
 /* ---- statistics ----------------------------------------------------------------
  * fhs_stats grows at its END when a counter is added (round 5: pbs_extracted): a host must be compiled against the

@@ -22,3 +22,23 @@ def test_oracle_under_asan_ubsan():
 
 def test_host_code_under_asan_ubsan():
     _run("fhestring_amd/csrc", "asan", "fhestring_amd/asan_host_test", "host sanitizer run ok")
+
+
+def test_planner_acquires_no_hip_resource():
+    """The same ownership figures through the Python binding (fhs_debug_live_resources), without a sanitizer: a planner
+    context records and levelises a replace of 65 / 2 / 2 characters, and after close() the library holds no device
+    memory, no pinned memory, no event and no stream, and has acquired nothing on the way."""
+    import gc
+    from fhestring_amd._lib import live_resources
+    from fhestring_amd.api import MyServerKey
+    gc.collect()                                     # contexts of earlier tests that nothing refers to any more
+    before = live_resources()
+    sk = MyServerKey.planner()
+    sk.set_mode(1)
+    keep = sk.replace(sk.dummy_string(65), sk.dummy_string(2), sk.dummy_string(2))
+    sk.flush()
+    assert sk.stats()["pbs_executed"] > 0
+    sk.close()
+    after = live_resources()
+    assert after[:4] == [0, 0, 0, 0] and after[4] == before[4], (before, after)
+    del keep

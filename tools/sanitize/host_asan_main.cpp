@@ -24,6 +24,8 @@ static std::vector<fhs_char_t> dummy(fhs_ctx *c, size_t n) {
 }
 
 int main() {
+    uint64_t res0[5], res1[5];
+    CHECK(fhs_debug_live_resources(res0) == FHS_OK && fhs_debug_live_resources(nullptr) == FHS_ERR_ARG);
     // ---- client -----------------------------------------------------------------------------------------------
     fhs_client *ck = nullptr;
     CHECK(fhs_client_create_insecure_seeded(42, &ck) == FHS_OK);
@@ -256,6 +258,29 @@ int main() {
     CHECK(w1 == 254 && c1 == 257);
     CHECK(fhs_str_find(c, nullptr, 3, nullptr, 0, nullptr) != FHS_OK);   // argument errors do not crash
     fhs_ctx_destroy(c);
+    {   // a planner destroyed with work outstanding: submitted but unpumped jobs, one store entry, live char handles --
+        // nothing is released by hand, every owner and container goes with the context (the leak checker watches)
+        fhs_ctx *d = nullptr;
+        CHECK(fhs_ctx_create_planner(&d) == FHS_OK && fhs_set_mode(d, 1) == FHS_OK);
+        auto s = dummy(d, 20);
+        std::vector<fhs_char_t> up(s.size());
+        uint64_t id = 0;
+        CHECK(fhs_str_to_upper(d, s.data(), s.size(), up.data()) == FHS_OK && fhs_submit(d) == FHS_OK);
+        CHECK(fhs_store_put(d, s.data(), s.size(), &id) == FHS_OK && id != 0);
+        fhs_char_t r = 0;
+        CHECK(fhs_str_contains_clear(d, up.data(), up.size(), "ab", 2, &r) == FHS_OK && fhs_submit(d) == FHS_OK);
+        fhs_ctx_destroy(d);
+    }
+    {   // no device here: creation fails, the half-built object carries the error text and is destroyed like any other
+        fhs_ctx *d = nullptr;
+        CHECK(fhs_ctx_create(9999, &d) != FHS_OK && d != nullptr && std::strlen(fhs_last_error(d)) > 10);
+        fhs_ctx_destroy(d);
+        fhs_ctx_destroy(nullptr);
+    }
+    // every owner is gone, and the planners and the failed creation acquired nothing
+    CHECK(fhs_debug_live_resources(res1) == FHS_OK);
+    for (int k = 0; k < 4; k++) CHECK(res1[k] == 0);
+    CHECK(res1[4] == res0[4]);
     fhs_client_destroy(ck);
     fhs_client_destroy(ck2);
     std::printf(fails ? "FAILED\n" : "host sanitizer run ok\n");
