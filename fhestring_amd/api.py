@@ -3,13 +3,15 @@ import ctypes as C
 
 import numpy as np
 
+from . import cabi
 from ._lib import FhsError, lib, check_single_hip_runtime
 
-BIG_CT = 2049
-SMALL_CT = 743
-POLY_N = 2048
-PACK_GROUP = 2048                     # blocks per packed GLWE (FHS_PACK_GROUP)
-PACK_KEY_WORDS = 11 * 3 * 2 * 2048    # FHS_PACK_KEY_WORDS
+_K = dict(cabi.parse_header()["consts"])      # the header's FHS_* #defines
+BIG_CT = _K["FHS_BIG_CT"]
+SMALL_CT = _K["FHS_SMALL_CT"]
+POLY_N = _K["FHS_POLY_N"]
+PACK_GROUP = _K["FHS_PACK_GROUP"]             # blocks per packed GLWE
+PACK_KEY_WORDS = _K["FHS_PACK_KEY_WORDS"]
 
 
 def _ptr(a):
@@ -54,10 +56,10 @@ class Context:
             err.code = rc
             raise err
 
-    ARITH_EXACT_NTT = 0
-    ARITH_F64_FFT = 1
-    ARITH_F64_FFT_MB2 = 2
-    ARITH_EXACT_NTT_MB2 = 3
+    ARITH_EXACT_NTT = _K["FHS_ARITH_EXACT_NTT"]
+    ARITH_F64_FFT = _K["FHS_ARITH_F64_FFT"]
+    ARITH_F64_FFT_MB2 = _K["FHS_ARITH_F64_FFT_MB2"]
+    ARITH_EXACT_NTT_MB2 = _K["FHS_ARITH_EXACT_NTT_MB2"]
 
     def set_arithmetic(self, arith):
         """fhs_set_arithmetic: 0 ARITH_EXACT_NTT (default), 1 ARITH_F64_FFT, 2 ARITH_F64_FFT_MB2 (select before
@@ -184,12 +186,12 @@ class Context:
 # `public_parameters` is accepted and ignored by every operation, like the reference's dead parameter;
 # PublicParameters itself is real: it encrypts without the client key (PublicParameters.encrypt).
 # ---------------------------------------------------------------------------------------------
-CHAR_WORDS = 4 * BIG_CT
-MAX_FIND_LENGTH = 255
-MAX_REPETITIONS = 16
+CHAR_WORDS = _K["FHS_CHAR_WORDS"]
+MAX_FIND_LENGTH = _K["FHS_MAX_FIND_LENGTH"]
+MAX_REPETITIONS = _K["FHS_MAX_REPETITIONS"]
 STRING_PADDING = 1
-MODE_AS_WRITTEN = 0
-MODE_FUSED = 1
+MODE_AS_WRITTEN = _K["FHS_MODE_AS_WRITTEN"]
+MODE_FUSED = _K["FHS_MODE_FUSED"]
 
 
 class MyClientKey:
@@ -765,7 +767,7 @@ def pack_switch32(mask64, body64, n_blocks):
     return CompactFheString(n_blocks // 4, mask32, body32) if n_blocks % 4 == 0 else (mask32, body32)
 
 
-STORE_MAX_CYCLES = 16          # FHS_STORE_MAX_CYCLES
+STORE_MAX_CYCLES = _K["FHS_STORE_MAX_CYCLES"]
 STORE_META_MAGIC = b"FHSSMET1"
 
 

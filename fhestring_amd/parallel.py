@@ -12,10 +12,12 @@ import ctypes as C
 
 import numpy as np
 
+from . import cabi
 from ._lib import lib
 
-CHAR_WORDS = 4 * 2049
-ID_BYTES = 128
+_K = dict(cabi.parse_header()["consts"])
+CHAR_WORDS = _K["FHS_CHAR_WORDS"]
+ID_BYTES = _K["FHS_DIST_ID_BYTES"]
 
 
 def plan_windows(n_chars, m, world):

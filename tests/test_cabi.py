@@ -25,6 +25,66 @@ def test_library_exports_every_declared_symbol():
     assert not missing, missing
 
 
+def _header_functions():
+    """{name: number of parameters} straight from the header's text (not through fhestring_amd.cabi)"""
+    text = open(os.path.join(ROOT, "include", "fhestring_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"typedef[^;{]*\([^;]*;", "", text)                     # the callback typedef is no function
+    return {name: 0 if params.strip() == "void" else params.count(",") + 1
+            for name, params in re.findall(r"\b(fhs_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text)}
+
+
+def test_every_header_function_has_a_derived_prototype():
+    """_lib._declare is a loop over the header: every function is declared, with the header's arity; a handful of
+    prototypes are pinned as literals so that a change of the derivation rule shows."""
+    import ctypes as C
+    import fhestring_amd
+    L = fhestring_amd.lib()
+    want = _header_functions()
+    assert sorted(want) == _declared() and len(want) >= 186
+    for name, arity in want.items():
+        f = getattr(L, name)
+        assert f.argtypes is not None and len(f.argtypes) == arity, name
+    vp, u64, sz, i = C.c_void_p, C.c_uint64, C.c_size_t, C.c_int
+    assert (L.fhs_eq.restype, L.fhs_eq.argtypes) == (u64, [vp, u64, u64])
+    assert (L.fhs_ctx_create.restype, L.fhs_ctx_create.argtypes) == (i, [i, vp])
+    assert (L.fhs_client_decrypt_str.restype, L.fhs_client_decrypt_str.argtypes) == (i, [vp, vp, sz, C.c_char_p, vp])
+    assert (L.fhs_last_error.restype, L.fhs_last_error.argtypes) == (C.c_char_p, [vp])
+    assert (L.fhs_client_bsk.restype, L.fhs_client_bsk.argtypes) == (C.POINTER(u64), [vp])
+    assert (L.fhs_store_get.restype, L.fhs_store_get.argtypes) == (i, [vp, u64, sz, sz, vp])
+
+
+def test_structs_are_the_headers():
+    import ctypes as C
+    from fhestring_amd._lib import CaptureRec, Stats
+    assert C.sizeof(Stats) == 64 and C.sizeof(CaptureRec) == 32
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "fhestring_hip.h")).read(), flags=re.S)
+    for cls, name in ((Stats, "fhs_stats"), (CaptureRec, "fhs_capture_rec")):
+        body = re.search(r"typedef\s+struct\s*\{([^{}]*)\}\s*%s\s*;" % name, text).group(1)
+        fields = [n.strip() for decl in body.split(";") if decl.strip() for n in decl.split(None, 1)[1].split(",")]
+        assert [f for f, _ in cls._fields_] == fields, name
+    assert [f for f, _ in Stats._fields_][0] == "pbs_executed" and [f for f, _ in CaptureRec._fields_][-1] == "width"
+    assert dict(CaptureRec._fields_)["sum_c2"] is C.c_int64 and dict(CaptureRec._fields_)["konst"] is C.c_int32
+
+
+def test_void_pointer_parameters_take_what_the_wrappers_pass_and_nothing_looser():
+    """Pointer parameters are c_void_p: it accepts every kind of object the wrappers hand over, and still rejects a bare
+    ndarray, so a wrapper that forgets _ptr() fails loudly instead of passing garbage."""
+    import ctypes as C
+    a = np.zeros(4, np.uint64)
+    word = C.c_uint64()
+    for ok in ((C.c_uint64 * 4)(), C.byref(word), a.ctypes.data_as(C.c_void_p), a.ctypes.data_as(C.POINTER(C.c_uint64)),
+               a.ctypes.data_as(C.POINTER(C.c_double)), C.create_string_buffer(16), b"bytes", None, a.ctypes.data,
+               C.c_char_p(b"x")):
+        C.c_void_p.from_param(ok)
+    for bad in (a, 1.5, [1, 2]):
+        with pytest.raises(TypeError):
+            C.c_void_p.from_param(bad)
+    import fhestring_amd
+    with pytest.raises(C.ArgumentError):                    # refused while converting: the function is never entered
+        fhestring_amd.lib().fhs_fft_mono_table(np.zeros(8192))
+
+
 def test_no_gpu_fails_loudly_not_silently():
     import torch
     import fhestring_amd
@@ -205,8 +265,6 @@ def test_monomial_table_of_the_two_bit_kernel_matches_the_oracle_on_this_host():
     from oracle import core
     got, want = np.zeros(8192), np.zeros(8192)
     L = lib()
-    L.fhs_fft_mono_table.argtypes = [C.c_void_p]
-    L.fhs_fft_mono_table.restype = None
     L.fhs_fft_mono_table(got.ctypes.data_as(C.c_void_p))
     O = core.lib()
     O.orc_fft_mono_table.argtypes = [C.c_void_p]
@@ -274,8 +332,6 @@ def test_client_generator_is_chacha20_and_os_seeded_by_default():
             qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14)
         return [(x[i] + st[i]) & 0xFFFFFFFF for i in range(16)]
     assert block(list(key), 1, list(nonce)) == list(out)
-    L.fhs_chacha20_stream.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.fhs_chacha20_stream.restype = None
     for start in (1, 0xFFFFFFE0):
         n_blocks = 40
         draws = (C.c_uint64 * (8 * n_blocks))()

@@ -1,7 +1,6 @@
 """Compressed (seeded) ciphertexts and server keys on the host: the client's seeded encryption, the public-data-only
 expansion, the pinned stream convention of include/fhestring_hip.h, noise, seeds, sizes, validity of the compressed
 server key under the CPU oracle, and the planner's view of a compressed upload."""
-import ctypes as C
 import random
 
 import numpy as np
@@ -28,8 +27,6 @@ def _ascii(rng, n):
 def _stream(seed, domain, sid, n, counter=0):
     import fhestring_amd
     L = fhestring_amd.lib()
-    L.fhs_chacha20_stream.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.fhs_chacha20_stream.restype = None
     key = np.ascontiguousarray(seed, np.uint32)
     nonce = np.array([domain, sid & 0xFFFFFFFF, sid >> 32], np.uint32)
     out = np.zeros(n, np.uint64)

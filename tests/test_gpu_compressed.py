@@ -30,11 +30,8 @@ def sk(ck):
 
 
 def _host_stream(key, counter, nonce, n):
-    import ctypes as C
     import fhestring_amd
     L = fhestring_amd.lib()
-    L.fhs_chacha20_stream.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.fhs_chacha20_stream.restype = None
     k, nn = np.array(key, np.uint32), np.array(nonce, np.uint32)
     out = np.zeros(n, np.uint64)
     L.fhs_chacha20_stream(k.ctypes.data, counter, nn.ctypes.data, out.ctypes.data, n)

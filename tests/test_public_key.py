@@ -39,8 +39,6 @@ def _ascii(rng, n):
 def _stream(seed, domain, sid, n):
     import fhestring_amd
     L = fhestring_amd.lib()
-    L.fhs_chacha20_stream.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
-    L.fhs_chacha20_stream.restype = None
     key = np.ascontiguousarray(seed, np.uint32)
     nonce = np.array([domain, sid & 0xFFFFFFFF, sid >> 32], np.uint32)
     out = np.zeros(n, np.uint64)

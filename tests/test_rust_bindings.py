@@ -170,8 +170,6 @@ def test_abi_classes_agree_with_the_ctypes_binding_the_gpu_tests_use():
     checked = 0
     for name, (ret, args) in r.items():
         f = getattr(L, name)
-        if f.argtypes is None:
-            continue                              # not declared in _lib.py (diagnostics called with explicit casts)
         got = [_abi_class_ctypes(t) for t in f.argtypes]
         assert got == [_abi_class_rust(a) for a in args], (name, got, args)
         if ret is None:
@@ -179,4 +177,4 @@ def test_abi_classes_agree_with_the_ctypes_binding_the_gpu_tests_use():
         else:
             assert _abi_class_ctypes(f.restype) == _abi_class_rust(ret), (name, f.restype, ret)
         checked += 1
-    assert checked >= 100, checked
+    assert checked == len(r), checked
