@@ -3,6 +3,7 @@
 #include <new>
 
 #include "capi_internal.h"
+#include "keyfile.h"
 #include "luts.h"
 #include "seeded_kernels.h"
 
@@ -86,10 +87,6 @@ void fhs_fft_mono_table(double *mono /*[4096][2]*/) {
     std::copy(t.mono.begin(), t.mono.end(), mono);
 }
 
-int fhs_read_server_key_file(const char *path, std::vector<uint64_t> &bsk, std::vector<uint64_t> &ksk);
-
-int fhs_read_multibit_key_file(const char *path, std::vector<uint64_t> &mb);
-
 int fhs_load_multibit_key_file(fhs_ctx *ctx, const char *path) {
     if (!ctx || !path) return FHS_ERR_ARG;
     std::vector<uint64_t> mb;
@@ -113,9 +110,6 @@ int fhs_load_compressed_server_key(fhs_ctx *ctx, const uint32_t seed[8], const u
     if (rc) return rc;
     return ctx->eng.on_key_loaded();
 }
-
-int fhs_read_compressed_server_key_file(const char *path, uint32_t seed[8], std::vector<uint64_t> &bsk_bodies,
-                                        std::vector<uint64_t> &ksk_bodies);
 
 int fhs_load_compressed_server_key_file(fhs_ctx *ctx, const char *path) {
     if (!ctx || !path) return FHS_ERR_ARG;

@@ -2,6 +2,7 @@
 #include <algorithm>
 
 #include "capi_internal.h"
+#include "keyfile.h"
 
 using namespace fhs;
 
@@ -273,9 +274,6 @@ int fhs_store_import(fhs_ctx *c, const void *mask32, const void *body32, const u
     if (n > ((size_t)1 << 24) || (n && (!mask32 || !body32))) return bad(c);
     return c->eng.store_import(static_cast<const uint32_t *>(mask32), static_cast<const uint32_t *>(body32), meta, 4 * n, id_out);
 }
-}  // extern "C"
-int fhs_read_packing_key_file(const char *path, std::vector<uint64_t> &key);   // client.cpp
-extern "C" {
 int fhs_load_packing_key_file(fhs_ctx *c, const char *path) {
     if (!c || !path) return FHS_ERR_ARG;
     std::vector<uint64_t> key;

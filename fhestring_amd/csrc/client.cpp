@@ -9,16 +9,17 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 #include <mutex>
-#include <thread>
 #include <vector>
 
 #include "../../include/fhestring_hip.h"
 #include "chacha_rng.h"
+#include "host_ntt.h"
+#include "host_parallel.h"
+#include "keyfile.h"
 #include "pbs_kernels.h"
 
 namespace {
@@ -26,7 +27,6 @@ namespace {
 using namespace fhs;
 using namespace fhs_rng;
 constexpr double LWE_NOISE = 7.069849454709433e-6;
-constexpr int PBS_BASE_LOG = 23;
 
 }  // namespace
 
@@ -64,6 +64,33 @@ void mul_binary(const uint64_t *a, const uint64_t *s, uint64_t *out) {
     }
 }
 
+// The 58-bit torus grid of the bootstrapping and packing keys: masks are truncated to it, bodies rounded (round_to_grid).
+constexpr uint64_t GRID_MASK = ~((1ull << BSK_QUANT_BITS) - 1);
+
+// The two body rows of GGSW(msg) from its two mask rows, msg a key bit or a product of key bits: one level of base 2^23,
+// body[r] = mask[r] (*) S + noise + the row's message, -msg S 2^(64-23) for row 0 and msg 2^(64-23) for row 1, on the
+// grid.  2 x 2048 draws of `noise`, row 0 first.
+void ggsw_bodies(const fhs_client *ck, uint64_t msg, Rng &noise, const uint64_t *const mask[2], uint64_t *const body[2]) {
+    std::vector<uint64_t> prod(POLY_N);
+    for (int r = 0; r < 2; r++) {
+        mul_binary(mask[r], ck->glwe_sk.data(), prod.data());
+        for (int n = 0; n < POLY_N; n++) {
+            uint64_t m;
+            if (r == 0) m = (uint64_t)0 - ((msg * ck->glwe_sk[n]) << (64 - PBS_BASE_LOG));
+            else m = n == 0 ? msg << (64 - PBS_BASE_LOG) : 0;
+            body[r][n] = round_to_grid(prod[n] + noise.noise(GLWE_NOISE) + m, BSK_QUANT_BITS);
+        }
+    }
+}
+// GGSW(msg) in the layout of the bootstrapping keys, [row][mask, body][2048]: 2 x 2048 draws of `mask`, row 0 first
+void ggsw_encrypt(const fhs_client *ck, uint64_t msg, Rng &mask, Rng &noise, uint64_t *out) {
+    for (int r = 0; r < 2; r++)
+        for (int n = 0; n < POLY_N; n++) out[r * 2 * POLY_N + n] = mask.next() & GRID_MASK;
+    const uint64_t *const m[2] = {out, out + 2 * POLY_N};
+    uint64_t *const b[2] = {out + POLY_N, out + 3 * POLY_N};
+    ggsw_bodies(ck, msg, noise, m, b);
+}
+
 void keygen(fhs_client *ck) {
     Rng r(ck->key, 1, DOM_SECRET);
     ck->lwe_sk.resize(LWE_N);
@@ -72,45 +99,24 @@ void keygen(fhs_client *ck) {
     for (auto &b : ck->glwe_sk) b = r.next() >> 63;
     ck->bsk.assign((size_t)LWE_N * 4 * POLY_N, 0);
     ck->ksk.assign((size_t)BIG_N * KS_LEVEL * SMALL_CT, 0);
-    const uint64_t qmask = ~((1ull << BSK_QUANT_BITS) - 1), qhalf = 1ull << (BSK_QUANT_BITS - 1);
-    unsigned nt = std::max(1u, std::min(32u, std::thread::hardware_concurrency()));
-    // bootstrapping key: GGSW_i(lwe_sk[i]) with one level of base 2^23, on the 58-bit torus grid
-    auto bsk_work = [&](unsigned tid) {
-        std::vector<uint64_t> prod(POLY_N);
-        for (int i = tid; i < LWE_N; i += nt) {
-            Rng g(ck->key, 1000 + i, DOM_MASK), e(ck->key, 1000 + i, DOM_NOISE);
-            for (int row = 0; row < 2; row++) {
-                uint64_t *mask = ck->bsk.data() + (((size_t)i * 2 + row) * 2 + 0) * POLY_N;
-                uint64_t *body = mask + POLY_N;
-                for (int n = 0; n < POLY_N; n++) mask[n] = g.next() & qmask;
-                mul_binary(mask, ck->glwe_sk.data(), prod.data());
-                for (int n = 0; n < POLY_N; n++) {
-                    uint64_t m;
-                    if (row == 0) m = (uint64_t)0 - ((ck->lwe_sk[i] * ck->glwe_sk[n]) << (64 - PBS_BASE_LOG));
-                    else m = n == 0 ? ck->lwe_sk[i] << (64 - PBS_BASE_LOG) : 0;
-                    body[n] = (prod[n] + e.noise(GLWE_NOISE) + m + qhalf) & qmask;
-                }
-            }
-        }
-    };
+    // bootstrapping key: GGSW_i(lwe_sk[i])
+    parallel_for(LWE_N, host_threads(32), 1, [&](size_t i) {
+        Rng g(ck->key, 1000 + i, DOM_MASK), e(ck->key, 1000 + i, DOM_NOISE);
+        ggsw_encrypt(ck, ck->lwe_sk[i], g, e, ck->bsk.data() + i * 4 * POLY_N);
+    });
     // keyswitching key: ksk[i][l] = LWE_small(glwe_sk[i] * 2^(64 - 3(l+1)))
-    auto ksk_work = [&](unsigned tid) {
-        for (int i = tid; i < BIG_N; i += nt) {
-            Rng g(ck->key, 100000 + i, DOM_MASK), e(ck->key, 100000 + i, DOM_NOISE);
-            for (int l = 0; l < KS_LEVEL; l++) {
-                uint64_t *ct = ck->ksk.data() + ((size_t)i * KS_LEVEL + l) * SMALL_CT;
-                uint64_t acc = 0;
-                for (int j = 0; j < LWE_N; j++) {
-                    ct[j] = g.next();
-                    acc += ct[j] * ck->lwe_sk[j];
-                }
-                ct[LWE_N] = acc + e.noise(LWE_NOISE) + (ck->glwe_sk[i] << (64 - KS_BASE_LOG * (l + 1)));
+    parallel_for(BIG_N, host_threads(32), 1, [&](size_t i) {
+        Rng g(ck->key, 100000 + i, DOM_MASK), e(ck->key, 100000 + i, DOM_NOISE);
+        for (int l = 0; l < KS_LEVEL; l++) {
+            uint64_t *ct = ck->ksk.data() + (i * KS_LEVEL + l) * SMALL_CT;
+            uint64_t acc = 0;
+            for (int j = 0; j < LWE_N; j++) {
+                ct[j] = g.next();
+                acc += ct[j] * ck->lwe_sk[j];
             }
+            ct[LWE_N] = acc + e.noise(LWE_NOISE) + (ck->glwe_sk[i] << (64 - KS_BASE_LOG * (l + 1)));
         }
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; t++) th.emplace_back([&, t] { bsk_work(t); ksk_work(t); });
-    for (auto &x : th) x.join();
+    });
 }
 
 // Pair key of the two-bits-per-product blind rotation (fftmb_kernels.hip): for every pair (s, s') = (lwe_sk[2p],
@@ -118,32 +124,13 @@ void keygen(fhs_client *ck) {
 // level of base 2^23, 58-bit grid) and their own mask / noise streams.
 void keygen_mb2(fhs_client *ck) {
     ck->bsk_mb2.assign((size_t)(LWE_N / 2) * 3 * 4 * POLY_N, 0);
-    const uint64_t qmask = ~((1ull << BSK_QUANT_BITS) - 1), qhalf = 1ull << (BSK_QUANT_BITS - 1);
-    unsigned nt = std::max(1u, std::min(32u, std::thread::hardware_concurrency()));
-    auto work = [&](unsigned tid) {
-        std::vector<uint64_t> prod(POLY_N);
-        for (int g = tid; g < (LWE_N / 2) * 3; g += nt) {
-            const int p = g / 3, t = g % 3;
-            const uint64_t s1 = ck->lwe_sk[2 * p], s2 = ck->lwe_sk[2 * p + 1];
-            const uint64_t msg = t == 0 ? s1 & (1 - s2) : t == 1 ? (1 - s1) & s2 : s1 & s2;
-            Rng gm(ck->key, 2000000 + g, DOM_MASK), e(ck->key, 2000000 + g, DOM_NOISE);
-            for (int row = 0; row < 2; row++) {
-                uint64_t *mask = ck->bsk_mb2.data() + (((size_t)g * 2 + row) * 2 + 0) * POLY_N;
-                uint64_t *body = mask + POLY_N;
-                for (int n = 0; n < POLY_N; n++) mask[n] = gm.next() & qmask;
-                mul_binary(mask, ck->glwe_sk.data(), prod.data());
-                for (int n = 0; n < POLY_N; n++) {
-                    uint64_t m;
-                    if (row == 0) m = (uint64_t)0 - ((msg * ck->glwe_sk[n]) << (64 - PBS_BASE_LOG));
-                    else m = n == 0 ? msg << (64 - PBS_BASE_LOG) : 0;
-                    body[n] = (prod[n] + e.noise(GLWE_NOISE) + m + qhalf) & qmask;
-                }
-            }
-        }
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 0; t < nt; t++) th.emplace_back([&, t] { work(t); });
-    for (auto &x : th) x.join();
+    parallel_for((LWE_N / 2) * 3, host_threads(32), 1, [&](size_t g) {
+        const size_t p = g / 3, t = g % 3;
+        const uint64_t s1 = ck->lwe_sk[2 * p], s2 = ck->lwe_sk[2 * p + 1];
+        const uint64_t msg = t == 0 ? s1 & (1 - s2) : t == 1 ? (1 - s1) & s2 : s1 & s2;
+        Rng gm(ck->key, 2000000 + g, DOM_MASK), e(ck->key, 2000000 + g, DOM_NOISE);
+        ggsw_encrypt(ck, msg, gm, e, ck->bsk_mb2.data() + g * 4 * POLY_N);
+    });
 }
 
 void encrypt_block_with(const fhs_client *ck, Rng &mask, Rng &noise, uint64_t m, uint64_t *ct) {
@@ -157,30 +144,12 @@ void encrypt_block(fhs_client *ck, uint64_t m, uint64_t *ct) { encrypt_block_wit
 // host threads for the per-character work of one string (encryption: 16 KB of ChaCha20 keystream and a 2048-term masked
 // sum per block; decryption: a 2048-term product): config 5 hands over 2 x 4097 characters = 537 MB of ciphertext, which
 // one thread needs ~0.16 s for -- as long as the GPU needs for the whole op (VERDICT r4 "missing 5")
-unsigned string_threads(size_t n_chars) {
-    unsigned hw = std::max(1u, std::min(32u, std::thread::hardware_concurrency()));
-    if (const char *e = std::getenv("FHS_CLIENT_THREADS")) hw = (unsigned)std::max(1, std::atoi(e));   // tests: 1 = sequential
-    return (unsigned)std::max<size_t>(1, std::min<size_t>(hw, n_chars / 32));
-}
+// FHS_CLIENT_THREADS overrides the machine's count (tests: 1 = sequential).
 template <class F>
 void for_each_char(size_t n, F &&f) {
-    const unsigned nt = string_threads(n);
-    if (nt <= 1) {
-        for (size_t i = 0; i < n; i++) f(i);
-        return;
-    }
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (;;) {
-            const size_t i0 = next.fetch_add(16);
-            if (i0 >= n) return;
-            for (size_t i = i0; i < std::min(n, i0 + 16); i++) f(i);
-        }
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &x : th) x.join();
+    size_t hw = host_threads(32);
+    if (const char *e = std::getenv("FHS_CLIENT_THREADS")) hw = (size_t)std::max(1, std::atoi(e));
+    parallel_for(n, std::min(hw, n / 32), 16, f);
 }
 constexpr uint64_t STR_STREAM_BASE = 1ull << 62;   // stream ids of string encryptions: base + (call << 24) + character
 constexpr size_t STR_MAX_CHARS = (size_t)1 << 24;
@@ -288,103 +257,39 @@ int fhs_client_decrypt_str(const fhs_client *ck, const uint64_t *chars, size_t n
     *out_len = k;
     return FHS_OK;
 }
-namespace {
-struct KeyFileHeader {
-    char magic[8];
-    uint64_t kind, lwe_n, poly_n, ks_levels, ks_base_log, pbs_base_log, bsk_quant_bits;
-};
-static_assert(sizeof(KeyFileHeader) == 64, "header is 64 bytes");
-KeyFileHeader make_header(uint64_t kind) {
-    KeyFileHeader h{};
-    std::memcpy(h.magic, "FHSKEY01", 8);
-    h.kind = kind; h.lwe_n = LWE_N; h.poly_n = POLY_N; h.ks_levels = KS_LEVEL; h.ks_base_log = KS_BASE_LOG;
-    h.pbs_base_log = PBS_BASE_LOG; h.bsk_quant_bits = BSK_QUANT_BITS;
-    return h;
-}
-bool header_ok(const KeyFileHeader &h) {
-    const KeyFileHeader w = make_header(h.kind);
-    return std::memcmp(&h, &w, sizeof(h)) == 0 && h.kind >= 1 && h.kind <= 6;
-}
-bool write_all(FILE *f, const void *p, size_t n) { return std::fwrite(p, 1, n, f) == n; }
-bool read_all(FILE *f, void *p, size_t n) { return std::fread(p, 1, n, f) == n; }
-}  // namespace
 
 int fhs_client_save(const fhs_client *ck, const char *path, int server_key_only) {
     if (!ck || !path) return FHS_ERR_ARG;
-    FILE *f = std::fopen(path, "wb");
-    if (!f) return FHS_ERR_STATE;
-    const KeyFileHeader h = make_header(server_key_only ? 2 : 1);
-    bool ok = write_all(f, &h, sizeof(h));
-    if (!server_key_only) {
-        ok = ok && write_all(f, &ck->seed, 8) && write_all(f, ck->lwe_sk.data(), ck->lwe_sk.size() * 8) &&
-             write_all(f, ck->glwe_sk.data(), ck->glwe_sk.size() * 8);
-    }
-    ok = ok && write_all(f, ck->bsk.data(), ck->bsk.size() * 8) && write_all(f, ck->ksk.data(), ck->ksk.size() * 8);
-    ok = (std::fclose(f) == 0) && ok;
-    return ok ? FHS_OK : FHS_ERR_STATE;
+    KeyFileWriter w(path, server_key_only ? 2 : 1);
+    if (!server_key_only)
+        w.put(&ck->seed, 8).put(ck->lwe_sk.data(), ck->lwe_sk.size() * 8).put(ck->glwe_sk.data(), ck->glwe_sk.size() * 8);
+    return w.put(ck->bsk.data(), ck->bsk.size() * 8).put(ck->ksk.data(), ck->ksk.size() * 8).close();
 }
 
 // kind 3: the pair key of the two-key-bits-per-product arithmetics alone (it accompanies a kind 1 / kind 2 file)
 int fhs_client_save_multibit_key(fhs_client *ck, const char *path) {
     if (!ck || !path) return FHS_ERR_ARG;
     const uint64_t *mb = fhs_client_bsk_mb2(ck);
-    FILE *f = std::fopen(path, "wb");
-    if (!f) return FHS_ERR_STATE;
-    const KeyFileHeader h = make_header(3);
-    bool ok = write_all(f, &h, sizeof(h)) && write_all(f, mb, FHS_BSK_MB2_WORDS * 8);
-    ok = (std::fclose(f) == 0) && ok;
-    return ok ? FHS_OK : FHS_ERR_STATE;
-}
-int fhs_read_multibit_key_file(const char *path, std::vector<uint64_t> &mb) {
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return FHS_ERR_STATE;
-    KeyFileHeader h;
-    bool ok = read_all(f, &h, sizeof(h)) && header_ok(h) && h.kind == 3;
-    if (ok) {
-        mb.resize(FHS_BSK_MB2_WORDS);
-        ok = read_all(f, mb.data(), mb.size() * 8) && std::fgetc(f) == EOF;
-    }
-    std::fclose(f);
-    return ok ? FHS_OK : FHS_ERR_STATE;
+    return KeyFileWriter(path, 3).put(mb, FHS_BSK_MB2_WORDS * 8).close();
 }
 
 int fhs_client_load(const char *path, fhs_client **out) {
     if (!path || !out) return FHS_ERR_ARG;
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return FHS_ERR_STATE;
-    KeyFileHeader h;
     fhs_client *ck = new (std::nothrow) fhs_client();
-    bool ok = ck && read_all(f, &h, sizeof(h)) && header_ok(h) && h.kind == 1;
-    if (ok) {
-        ck->lwe_sk.resize(LWE_N); ck->glwe_sk.resize(POLY_N);
-        ck->bsk.resize((size_t)LWE_N * 4 * POLY_N); ck->ksk.resize((size_t)BIG_N * KS_LEVEL * SMALL_CT);
-        ok = read_all(f, &ck->seed, 8) && read_all(f, ck->lwe_sk.data(), LWE_N * 8) &&
-             read_all(f, ck->glwe_sk.data(), POLY_N * 8) && read_all(f, ck->bsk.data(), ck->bsk.size() * 8) &&
-             read_all(f, ck->ksk.data(), ck->ksk.size() * 8);
-        // a loaded client never replays an encryption stream: fresh OS entropy for masks and noise
-        ok = ok && os_entropy(&ck->key, sizeof(ck->key));
-        ck->enc_mask = Rng(ck->key, 7, DOM_MASK);
-        ck->enc_noise = Rng(ck->key, 7, DOM_NOISE);
+    if (!ck) return FHS_ERR_STATE;
+    KeyFileReader r(path, {1});
+    r.get(&ck->seed, 8).get(ck->lwe_sk, LWE_N).get(ck->glwe_sk, POLY_N).get(ck->bsk, (size_t)LWE_N * 4 * POLY_N)
+        .get(ck->ksk, (size_t)BIG_N * KS_LEVEL * SMALL_CT);
+    // like the other reader of kinds 1 and 2, this one accepts trailing bytes (keyfile.h).
+    // A loaded client never replays an encryption stream: fresh OS entropy for masks and noise
+    if (r.finish(false) != FHS_OK || !os_entropy(&ck->key, sizeof(ck->key))) {
+        delete ck;
+        return FHS_ERR_STATE;
     }
-    std::fclose(f);
-    if (!ok) { delete ck; return FHS_ERR_STATE; }
+    ck->enc_mask = Rng(ck->key, 7, DOM_MASK);
+    ck->enc_noise = Rng(ck->key, 7, DOM_NOISE);
     *out = ck;
     return FHS_OK;
-}
-
-// reads only the server-key part of a key file (used by fhs_load_server_key_file in capi_core.cpp)
-int fhs_read_server_key_file(const char *path, std::vector<uint64_t> &bsk, std::vector<uint64_t> &ksk) {
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return FHS_ERR_STATE;
-    KeyFileHeader h;
-    bool ok = read_all(f, &h, sizeof(h)) && header_ok(h) && (h.kind == 1 || h.kind == 2);
-    if (ok && h.kind == 1) ok = std::fseek(f, 8 + (LWE_N + POLY_N) * 8, SEEK_CUR) == 0;
-    if (ok) {
-        bsk.resize((size_t)LWE_N * 4 * POLY_N); ksk.resize((size_t)BIG_N * KS_LEVEL * SMALL_CT);
-        ok = read_all(f, bsk.data(), bsk.size() * 8) && read_all(f, ksk.data(), ksk.size() * 8);
-    }
-    std::fclose(f);
-    return ok ? FHS_OK : FHS_ERR_STATE;
 }
 
 int fhs_client_secret_keys(const fhs_client *ck, uint64_t *lwe_sk, uint64_t *glwe_sk) {
@@ -435,24 +340,18 @@ uint64_t streamed_dot(Rng &mask, const uint64_t *s, int n) {
 void keygen_compressed(fhs_client *ck) {
     ck->cbsk_bodies.assign(FHS_CBSK_BODY_WORDS, 0);
     ck->cksk_bodies.assign(FHS_CKSK_BODY_WORDS, 0);
-    const uint64_t qmask = ~((1ull << BSK_QUANT_BITS) - 1), qhalf = 1ull << (BSK_QUANT_BITS - 1);
     const ChaKey seed = ck->cseed;
-    // BSK: the rows of keygen's GGSW_i(lwe_sk[i]) with seeded masks
+    // BSK: the rows of keygen's GGSW_i(lwe_sk[i]) with seeded masks, one stream per row; only the bodies are kept
     for_each_char(LWE_N, [&](size_t i) {
-        std::vector<uint64_t> mask(POLY_N), prod(POLY_N);
+        std::vector<uint64_t> masks(2 * POLY_N);
         Rng e(ck->key, CBSK_NOISE_BASE + i, DOM_NOISE);
         for (int row = 0; row < 2; row++) {
             Rng g(seed, 2 * i + row, FHS_DOM_SEEDED_BSK);
-            for (int n = 0; n < POLY_N; n++) mask[n] = g.next() & qmask;
-            mul_binary(mask.data(), ck->glwe_sk.data(), prod.data());
-            uint64_t *body = ck->cbsk_bodies.data() + (i * 2 + row) * POLY_N;
-            for (int n = 0; n < POLY_N; n++) {
-                uint64_t m;
-                if (row == 0) m = (uint64_t)0 - ((ck->lwe_sk[i] * ck->glwe_sk[n]) << (64 - PBS_BASE_LOG));
-                else m = n == 0 ? ck->lwe_sk[i] << (64 - PBS_BASE_LOG) : 0;
-                body[n] = (prod[n] + e.noise(GLWE_NOISE) + m + qhalf) & qmask;
-            }
+            for (int n = 0; n < POLY_N; n++) masks[row * POLY_N + n] = g.next() & GRID_MASK;
         }
+        const uint64_t *const m[2] = {masks.data(), masks.data() + POLY_N};
+        uint64_t *const b[2] = {ck->cbsk_bodies.data() + i * 2 * POLY_N, ck->cbsk_bodies.data() + (i * 2 + 1) * POLY_N};
+        ggsw_bodies(ck, ck->lwe_sk[i], e, m, b);
     });
     // KSK: ksk[i][l] = LWE_small(glwe_sk[i] * 2^(64 - 3(l+1))) with seeded masks
     for_each_char(BIG_N, [&](size_t i) {
@@ -526,41 +425,18 @@ int fhs_client_compressed_server_key(fhs_client *ck, uint32_t seed_out[8], uint6
 int fhs_client_save_compressed_server_key(fhs_client *ck, const char *path) {
     if (!ck || !path) return FHS_ERR_ARG;
     if (!compressed_server_key(ck)) return FHS_ERR_STATE;
-    FILE *f = std::fopen(path, "wb");
-    if (!f) return FHS_ERR_STATE;
-    const KeyFileHeader h = make_header(4);
-    bool ok = write_all(f, &h, sizeof(h)) && write_all(f, ck->cseed.w, 32) &&
-              write_all(f, ck->cbsk_bodies.data(), FHS_CBSK_BODY_WORDS * 8) &&
-              write_all(f, ck->cksk_bodies.data(), FHS_CKSK_BODY_WORDS * 8);
-    ok = (std::fclose(f) == 0) && ok;
-    return ok ? FHS_OK : FHS_ERR_STATE;
-}
-// reads a kind 4 file (used by fhs_load_compressed_server_key_file in capi_core.cpp)
-int fhs_read_compressed_server_key_file(const char *path, uint32_t seed[8], std::vector<uint64_t> &bsk_bodies,
-                                        std::vector<uint64_t> &ksk_bodies) {
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return FHS_ERR_STATE;
-    KeyFileHeader h;
-    bool ok = read_all(f, &h, sizeof(h)) && header_ok(h) && h.kind == 4;
-    if (ok) {
-        bsk_bodies.resize(FHS_CBSK_BODY_WORDS);
-        ksk_bodies.resize(FHS_CKSK_BODY_WORDS);
-        ok = read_all(f, seed, 32) && read_all(f, bsk_bodies.data(), bsk_bodies.size() * 8) &&
-             read_all(f, ksk_bodies.data(), ksk_bodies.size() * 8) && std::fgetc(f) == EOF;
-    }
-    std::fclose(f);
-    return ok ? FHS_OK : FHS_ERR_STATE;
+    return KeyFileWriter(path, 4).put(ck->cseed.w, 32).put(ck->cbsk_bodies.data(), FHS_CBSK_BODY_WORDS * 8)
+        .put(ck->cksk_bodies.data(), FHS_CKSK_BODY_WORDS * 8).close();
 }
 
 int fhs_expand_compressed_server_key(const uint32_t seed[8], const uint64_t *bsk_bodies, const uint64_t *ksk_bodies,
                                      uint64_t *bsk, uint64_t *ksk) {
     if (!seed || !bsk_bodies || !ksk_bodies || !bsk || !ksk) return FHS_ERR_ARG;
     const ChaKey k = seed_key(seed);
-    const uint64_t qmask = ~((1ull << BSK_QUANT_BITS) - 1);
     for_each_char((size_t)LWE_N * 2, [&](size_t p) {          // GGSW row p = 2i + r
         uint64_t *mask = bsk + p * 2 * POLY_N;
         Rng g(k, p, FHS_DOM_SEEDED_BSK);
-        for (int n = 0; n < POLY_N; n++) mask[n] = g.next() & qmask;
+        for (int n = 0; n < POLY_N; n++) mask[n] = g.next() & GRID_MASK;
         std::memcpy(mask + POLY_N, bsk_bodies + p * POLY_N, POLY_N * 8);
     });
     for_each_char((size_t)BIG_N * KS_LEVEL, [&](size_t r) {   // row r = 5i + l
@@ -583,29 +459,26 @@ namespace {
 constexpr uint64_t PACK_STREAM_BASE = 6000000;
 void keygen_packing(fhs_client *ck) {
     ck->pack_key.assign(FHS_PACK_KEY_WORDS, 0);
-    const uint64_t qmask = ~((1ull << BSK_QUANT_BITS) - 1), qhalf = 1ull << (BSK_QUANT_BITS - 1);
-    std::vector<std::thread> th;
-    for (int lv = 1; lv <= FHS_PACK_TREE_LEVELS; lv++) {
-        th.emplace_back([=] {
-            const uint32_t g = (1u << lv) + 1;
-            std::vector<uint64_t> sg(POLY_N), prod(POLY_N);
-            for (uint32_t i = 0; i < (uint32_t)POLY_N; i++) {          // S(X^g): coefficient i goes to i g mod 2N
-                const uint32_t r = (i * g) & (2 * POLY_N - 1);
-                sg[r & (POLY_N - 1)] = r >= (uint32_t)POLY_N ? (uint64_t)0 - ck->glwe_sk[i] : ck->glwe_sk[i];
-            }
-            for (int l = 0; l < FHS_PACK_LEVELS; l++) {
-                const uint64_t sid = PACK_STREAM_BASE + (uint64_t)FHS_PACK_LEVELS * (lv - 1) + l;
-                Rng gm(ck->key, sid, DOM_MASK), e(ck->key, sid, DOM_NOISE);
-                uint64_t *mask = ck->pack_key.data() + (((size_t)(lv - 1) * FHS_PACK_LEVELS + l) * 2) * POLY_N;
-                uint64_t *body = mask + POLY_N;
-                for (int n = 0; n < POLY_N; n++) mask[n] = gm.next() & qmask;
-                mul_binary(mask, ck->glwe_sk.data(), prod.data());
-                for (int n = 0; n < POLY_N; n++)
-                    body[n] = (prod[n] + e.noise(GLWE_NOISE) + (sg[n] << (64 - FHS_PACK_BASE_LOG * (l + 1))) + qhalf) & qmask;
-            }
-        });
-    }
-    for (auto &x : th) x.join();
+    parallel_for(FHS_PACK_TREE_LEVELS, FHS_PACK_TREE_LEVELS, 1, [&](size_t k) {   // one thread per tree level
+        const int lv = (int)k + 1;
+        const uint32_t g = (1u << lv) + 1;
+        std::vector<uint64_t> sg(POLY_N), prod(POLY_N);
+        for (uint32_t i = 0; i < (uint32_t)POLY_N; i++) {          // S(X^g): coefficient i goes to i g mod 2N
+            const uint32_t r = (i * g) & (2 * POLY_N - 1);
+            sg[r & (POLY_N - 1)] = r >= (uint32_t)POLY_N ? (uint64_t)0 - ck->glwe_sk[i] : ck->glwe_sk[i];
+        }
+        for (int l = 0; l < FHS_PACK_LEVELS; l++) {
+            const uint64_t sid = PACK_STREAM_BASE + (uint64_t)FHS_PACK_LEVELS * (lv - 1) + l;
+            Rng gm(ck->key, sid, DOM_MASK), e(ck->key, sid, DOM_NOISE);
+            uint64_t *mask = ck->pack_key.data() + (((size_t)(lv - 1) * FHS_PACK_LEVELS + l) * 2) * POLY_N;
+            uint64_t *body = mask + POLY_N;
+            for (int n = 0; n < POLY_N; n++) mask[n] = gm.next() & GRID_MASK;
+            mul_binary(mask, ck->glwe_sk.data(), prod.data());
+            for (int n = 0; n < POLY_N; n++)
+                body[n] = round_to_grid(prod[n] + e.noise(GLWE_NOISE) + (sg[n] << (64 - FHS_PACK_BASE_LOG * (l + 1))),
+                                        BSK_QUANT_BITS);
+        }
+    });
 }
 
 // phases of one packed group: ph[j] = (body16[j] << 48) - ((mask16 << 48) (*) S)[j], j < count
@@ -631,12 +504,7 @@ const uint64_t *fhs_client_packing_key(fhs_client *ck) {
 int fhs_client_save_packing_key(fhs_client *ck, const char *path) {
     if (!ck || !path) return FHS_ERR_ARG;
     const uint64_t *k = fhs_client_packing_key(ck);
-    FILE *f = std::fopen(path, "wb");
-    if (!f) return FHS_ERR_STATE;
-    KeyFileHeader h = make_header(5);
-    bool ok = write_all(f, &h, sizeof(h)) && write_all(f, k, FHS_PACK_KEY_WORDS * 8);
-    ok = (std::fclose(f) == 0) && ok;
-    return ok ? FHS_OK : FHS_ERR_STATE;
+    return KeyFileWriter(path, 5).put(k, FHS_PACK_KEY_WORDS * 8).close();
 }
 
 int fhs_client_encrypt_blocks(fhs_client *ck, const uint8_t *values, size_t n, uint64_t *blocks) {
@@ -677,20 +545,6 @@ int fhs_client_decrypt_packed_str(const fhs_client *ck, const void *mask16, cons
 
 }  // extern "C"
 
-// reads a kind 5 file (used by fhs_load_packing_key_file in capi_ops.cpp)
-int fhs_read_packing_key_file(const char *path, std::vector<uint64_t> &key) {
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return FHS_ERR_STATE;
-    KeyFileHeader h;
-    bool ok = read_all(f, &h, sizeof(h)) && header_ok(h) && h.kind == 5;
-    if (ok) {
-        key.resize(FHS_PACK_KEY_WORDS);
-        ok = read_all(f, key.data(), key.size() * 8) && std::fgetc(f) == EOF;
-    }
-    std::fclose(f);
-    return ok ? FHS_OK : FHS_ERR_STATE;
-}
-
 // ---- public key (pk_host.cpp, pk_kernels.hip): the client's side ---------------------------------------------------------
 namespace {
 
@@ -726,26 +580,7 @@ int fhs_client_public_key(fhs_client *ck, uint32_t seed_out[8], uint64_t *body_o
 int fhs_client_save_public_key(fhs_client *ck, const char *path) {
     if (!ck || !path) return FHS_ERR_ARG;
     if (!public_key(ck)) return FHS_ERR_STATE;
-    FILE *f = std::fopen(path, "wb");
-    if (!f) return FHS_ERR_STATE;
-    const KeyFileHeader h = make_header(6);
-    bool ok = write_all(f, &h, sizeof(h)) && write_all(f, ck->pk_seed.w, 32) && write_all(f, ck->pk_body.data(), POLY_N * 8);
-    ok = (std::fclose(f) == 0) && ok;
-    return ok ? FHS_OK : FHS_ERR_STATE;
+    return KeyFileWriter(path, 6).put(ck->pk_seed.w, 32).put(ck->pk_body.data(), POLY_N * 8).close();
 }
 
 }  // extern "C"
-
-// reads a kind 6 file (used by fhs_public_key_load in pk_host.cpp)
-int fhs_read_public_key_file(const char *path, uint32_t seed[8], std::vector<uint64_t> &body) {
-    FILE *f = std::fopen(path, "rb");
-    if (!f) return FHS_ERR_STATE;
-    KeyFileHeader h;
-    bool ok = read_all(f, &h, sizeof(h)) && header_ok(h) && h.kind == 6;
-    if (ok) {
-        body.resize(POLY_N);
-        ok = read_all(f, seed, 32) && read_all(f, body.data(), body.size() * 8) && std::fgetc(f) == EOF;
-    }
-    std::fclose(f);
-    return ok ? FHS_OK : FHS_ERR_STATE;
-}

@@ -5,7 +5,6 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <thread>
 #include <utility>
 
 namespace fhs {
@@ -176,8 +175,7 @@ int Context::install_server_key(const uint64_t *bsk, const uint64_t *d_ksk) {
     }
     {
         std::vector<double> host(bsk_ntt_doubles);
-        unsigned hc = std::thread::hardware_concurrency();
-        convert_bsk_to_ntt(bsk, host.data(), (int)std::min(32u, std::max(1u, hc)));
+        convert_bsk_to_ntt(bsk, host.data());
         HIP_TRY(hipMemcpy(d_bsk_ntt.ptr, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice),
                 "copy bsk");
     }
@@ -287,8 +285,7 @@ int Context::load_multibit_key(const uint64_t *bsk_mb2) {
         if (!ntt_slot_roots_are_bitreversed()) return fail(-3, "internal: NTT slot order is not bit-reversed");
         const size_t n_d = (size_t)(LWE_N / 2) * 3 * 4 * 2 * POLY_N;
         std::vector<double> host(n_d);
-        unsigned hc = std::thread::hardware_concurrency();
-        convert_bsk_to_ntt(bsk_mb2, host.data(), (int)std::min(32u, std::max(1u, hc)), (LWE_N / 2) * 3, 7);
+        convert_bsk_to_ntt(bsk_mb2, host.data(), (LWE_N / 2) * 3, 7);
         HIP_TRY(d_bsk_ntt_mb.reserve_exact(n_d * sizeof(double)), "hipMalloc pair key (NTT)");
         HIP_TRY(hipMemcpy(d_bsk_ntt_mb.ptr, host.data(), n_d * sizeof(double), hipMemcpyHostToDevice), "copy pair key");
         HIP_TRY(prepare_device_for_ntt_mb2(), "kernel attributes");
@@ -318,7 +315,7 @@ int Context::load_packing_key(const uint64_t *key) {
     if (!ntt_slot_roots_are_bitreversed()) return fail(-3, "internal: NTT slot order is not bit-reversed");
     const size_t n_d = PACK_KEY_POLYS * 2 * POLY_N;
     std::vector<double> host(n_d);
-    convert_polys_to_ntt(key, host.data(), 11, PACK_KEY_POLYS, BSK_QUANT_BITS);
+    convert_polys_to_ntt(key, host.data(), PACK_KEY_POLYS, BSK_QUANT_BITS);
     HIP_TRY(hipStreamSynchronize(stream), "stream sync");     // a queued packing may still read the previous key
     HIP_TRY(d_pack_key_ntt.reserve_exact(n_d * sizeof(double)), "hipMalloc packing key");
     HIP_TRY(hipMemcpy(d_pack_key_ntt.ptr, host.data(), n_d * sizeof(double), hipMemcpyHostToDevice), "copy packing key");

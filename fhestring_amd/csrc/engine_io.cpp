@@ -1,6 +1,7 @@
 // The engine's traffic with the host and with memory at rest: block and whole-string uploads, downloads, packing,
 // the device-resident string store, char handles.  The graph, the planner and the launch groups are engine.cpp.
 #include "engine.h"
+#include "host_parallel.h"
 #include "pack_kernels.h"
 #include "../../include/fhestring_hip.h"
 #include "pk_kernels.h"
@@ -9,7 +10,6 @@
 
 #include <algorithm>
 #include <cstring>
-#include <thread>
 
 namespace fhs {
 
@@ -130,21 +130,14 @@ int Engine::from_host_many(const uint64_t *cts, size_t count, Bid *out) {
             // pageable -> pinned: one thread copies ~10 GB/s, which for the 537 MB of two 4097-character strings is as long
             // as their (threaded) client encryption; large passes are split over a few host threads
             const size_t bytes = n * BIG_CT * 8;
-            const unsigned nt = bytes >= ((size_t)8 << 20) ? std::min(8u, std::max(1u, std::thread::hardware_concurrency())) : 1;
-            if (nt <= 1) {
-                std::memcpy(xfer_.pin(), cts + done * BIG_CT, bytes);
-            } else {
-                const char *src = reinterpret_cast<const char *>(cts + done * BIG_CT);
-                char *dst = reinterpret_cast<char *>(xfer_.pin());
-                const size_t part = (bytes / nt + 4095) & ~(size_t)4095;
-                std::vector<std::thread> th;
-                for (unsigned t = 1; t < nt; t++) {
-                    const size_t lo = std::min(bytes, t * part), hi = std::min(bytes, (t + 1) * part);
-                    if (hi > lo) th.emplace_back([=] { std::memcpy(dst + lo, src + lo, hi - lo); });
-                }
-                std::memcpy(dst, src, std::min(bytes, part));
-                for (auto &x : th) x.join();
-            }
+            const size_t nt = bytes >= ((size_t)8 << 20) ? host_threads(8) : 1;
+            const char *src = reinterpret_cast<const char *>(cts + done * BIG_CT);
+            char *dst = reinterpret_cast<char *>(xfer_.pin());
+            const size_t part = (bytes / nt + 4095) & ~(size_t)4095;
+            parallel_for(nt, nt, 1, [&](size_t t) {
+                const size_t lo = std::min(bytes, t * part), hi = std::min(bytes, (t + 1) * part);
+                std::memcpy(dst + lo, src + lo, hi - lo);
+            });
         }
         uint64_t *const dev = xfer_.dev();
         if (!send_pass(n, out + done, n * BIG_CT, 0, n * BIG_CT + n) ||

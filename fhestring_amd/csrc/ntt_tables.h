@@ -20,9 +20,9 @@ bool ntt_slot_roots_are_bitreversed();
 
 // bsk_std: [n_ggsw][2][2][2048] u64 (rounded to multiples of 2^quant_bits inside).  out: [n_ggsw][2][2][2 primes][32][64]
 // doubles = forward NTT of (signed bsk / 2^quant_bits) mod p, pre-scaled by N^-1, centred, in the device's
-// contiguous-layout order.  Runs on `nthreads` host threads (key loading, not the hot path).
-void convert_bsk_to_ntt(const uint64_t *bsk_std, double *out, int nthreads, int n_ggsw = 742, int quant_bits = 6);
+// contiguous-layout order.  Runs on up to 32 host threads (key loading, not the hot path).
+void convert_bsk_to_ntt(const uint64_t *bsk_std, double *out, int n_ggsw = 742, int quant_bits = 6);
 // the same per polynomial: [n_polys][2048] u64 -> [n_polys][2 primes][32][64] (the packing key has 66 polynomials)
-void convert_polys_to_ntt(const uint64_t *polys, double *out, int nthreads, size_t n_polys, int quant_bits = 6);
+void convert_polys_to_ntt(const uint64_t *polys, double *out, size_t n_polys, int quant_bits = 6);
 
 }  // namespace fhs

@@ -1,105 +1,22 @@
 // Host reference of the packed result download (include/fhestring_hip.h, "packed result download"):
 // ring packing of up to 2048 LWE blocks into one GLWE (Chen, Dai, Kim, Song, Alg. PackLWEs) in exact arithmetic over
 // Z_2^64[X]/(X^2048+1).  Public data only, no GPU: the comparator of pack_kernels.hip and what CPU-only tests decrypt.
-// The negacyclic products run through a host NTT over the device's two primes (any exact method gives the same words).
+// The negacyclic products run through the host NTT over the device's two primes (host_ntt.h; any exact method gives the
+// same words, and tests/test_packed.py checks a node against a schoolbook product that uses no transform).
 #include <algorithm>
-#include <atomic>
 #include <cstring>
-#include <thread>
 #include <vector>
 
 #include "../../include/fhestring_hip.h"
+#include "host_ntt.h"
+#include "host_parallel.h"
 #include "pbs_kernels.h"
 
 namespace {
 
 using namespace fhs;
-typedef unsigned __int128 u128;
 constexpr int N = POLY_N;
 constexpr int L = FHS_PACK_LEVELS, BETA = FHS_PACK_BASE_LOG;
-
-struct Prime {
-    uint64_t p, barrett;                    // barrett = floor(2^94 / p)
-    std::vector<uint64_t> psi_br, ipsi_br;  // psi^bitrev(k), psi^-bitrev(k)
-    uint64_t ninv;
-    // a, b < p < 2^47: a b mod p with one 96-bit quotient estimate (at most three corrections)
-    uint64_t mul(uint64_t a, uint64_t b) const {
-        const u128 x = (u128)a * b;
-        const uint64_t q = (uint64_t)(((u128)(uint64_t)(x >> 46) * barrett) >> 48);
-        uint64_t r = (uint64_t)(x - (u128)q * p);
-        while (r >= p) r -= p;
-        return r;
-    }
-    uint64_t pow(uint64_t b, uint64_t e) const {
-        uint64_t r = 1;
-        for (; e; e >>= 1, b = mul(b, b))
-            if (e & 1) r = mul(r, b);
-        return r;
-    }
-};
-unsigned bitrev11(unsigned x) {
-    unsigned r = 0;
-    for (int i = 0; i < 11; i++) r |= ((x >> i) & 1u) << (10 - i);
-    return r;
-}
-Prime make_prime(uint64_t p, uint64_t psi) {
-    Prime t;
-    t.p = p;
-    t.barrett = (uint64_t)((((u128)1) << 94) / p);
-    t.psi_br.resize(N);
-    t.ipsi_br.resize(N);
-    const uint64_t ipsi = t.pow(psi, p - 2);
-    uint64_t a = 1, b = 1;
-    for (unsigned i = 0; i < (unsigned)N; i++) {
-        t.psi_br[bitrev11(i)] = a;
-        t.ipsi_br[bitrev11(i)] = b;
-        a = t.mul(a, psi);
-        b = t.mul(b, ipsi);
-    }
-    t.ninv = t.pow(N, p - 2);
-    return t;
-}
-const Prime &prime(int q) {
-    static const Prime t0 = make_prime(NTT_P0, NTT_PSI0), t1 = make_prime(NTT_P1, NTT_PSI1);
-    return q ? t1 : t0;
-}
-// negacyclic forward (Cooley-Tukey, natural order in, bit-reversed out) and inverse (Gentleman-Sande, without 1/N)
-void ntt_fwd(uint64_t *a, const Prime &t) {
-    const uint64_t p = t.p;
-    unsigned len = N;
-    for (unsigned m = 1; m < (unsigned)N; m <<= 1) {
-        len >>= 1;
-        for (unsigned i = 0; i < m; i++) {
-            const uint64_t w = t.psi_br[m + i];
-            uint64_t *x = a + 2 * i * len, *y = x + len;
-            for (unsigned k = 0; k < len; k++) {
-                const uint64_t u = x[k], v = t.mul(y[k], w);
-                x[k] = u + v >= p ? u + v - p : u + v;
-                y[k] = u >= v ? u - v : u + p - v;
-            }
-        }
-    }
-}
-void ntt_inv(uint64_t *a, const Prime &t) {
-    const uint64_t p = t.p;
-    unsigned len = 1;
-    for (unsigned m = N / 2; m >= 1; m >>= 1) {
-        for (unsigned i = 0; i < m; i++) {
-            const uint64_t w = t.ipsi_br[m + i];
-            uint64_t *x = a + 2 * i * len, *y = x + len;
-            for (unsigned k = 0; k < len; k++) {
-                const uint64_t u = x[k], v = y[k];
-                x[k] = u + v >= p ? u + v - p : u + v;
-                y[k] = t.mul(u >= v ? u - v : u + p - v, w);
-            }
-        }
-        len <<= 1;
-    }
-}
-inline uint64_t to_residue(int64_t v, uint64_t p) {
-    const int64_t m = v % (int64_t)p;
-    return (uint64_t)(m < 0 ? m + (int64_t)p : m);
-}
 
 // the packing key in the NTT domain: [11][L][mask, body][prime][2048], rounded to the 58-bit grid, 1/N folded in
 struct HostKey {
@@ -111,16 +28,7 @@ struct HostKey {
 void convert_key(const uint64_t *key, HostKey &hk) {
     hk.w.resize((size_t)FHS_PACK_TREE_LEVELS * L * 2 * 2 * N);
     for (size_t pi = 0; pi < (size_t)FHS_PACK_TREE_LEVELS * L * 2; pi++)
-        for (int q = 0; q < 2; q++) {
-            const Prime &pt = prime(q);
-            uint64_t *a = hk.w.data() + (pi * 2 + q) * N;
-            for (int n = 0; n < N; n++) {
-                const uint64_t r = (key[pi * N + n] + (1ull << (BSK_QUANT_BITS - 1))) & ~((1ull << BSK_QUANT_BITS) - 1);
-                a[n] = to_residue((int64_t)r >> BSK_QUANT_BITS, pt.p);
-            }
-            ntt_fwd(a, pt);
-            for (int n = 0; n < N; n++) a[n] = pt.mul(a[n], pt.ninv);
-        }
+        for (int q = 0; q < 2; q++) torus_poly_to_ntt(key + pi * N, BSK_QUANT_BITS, ntt_prime(q), hk.w.data() + (pi * 2 + q) * N);
 }
 
 // signed digits of x, most significant first (l = 0), each in [-2^(BETA-1), 2^(BETA-1))
@@ -158,11 +66,11 @@ void pack_node(const HostKey &hk, int lv, const uint64_t *e, const uint64_t *o, 
         int64_t d[L];
         decompose(A1[n], d);
         for (int l = 0; l < L; l++)
-            for (int q = 0; q < 2; q++) dig[((size_t)q * L + l) * N + n] = to_residue(d[l], prime(q).p);
+            for (int q = 0; q < 2; q++) dig[((size_t)q * L + l) * N + n] = to_residue(d[l], ntt_prime(q).p);
     }
     for (int q = 0; q < 2; q++) {
-        const Prime &pt = prime(q);
-        for (int l = 0; l < L; l++) ntt_fwd(dig + ((size_t)q * L + l) * N, pt);
+        const NttPrime &pt = ntt_prime(q);
+        for (int l = 0; l < L; l++) ntt_forward(dig + ((size_t)q * L + l) * N, pt);
         for (int c = 0; c < 2; c++) {
             uint64_t *a = acc + ((size_t)c * 2 + q) * N;
             for (int n = 0; n < N; n++) {
@@ -170,11 +78,11 @@ void pack_node(const HostKey &hk, int lv, const uint64_t *e, const uint64_t *o, 
                 for (int l = 0; l < L; l++) s += pt.mul(dig[((size_t)q * L + l) * N + n], hk.poly(lv, l, c, q)[n]);
                 a[n] = s % pt.p;
             }
-            ntt_inv(a, pt);
+            ntt_inverse(a, pt);
         }
     }
     // CRT to the centred integer, back to the torus: << 6 (the key was divided by 2^6)
-    const Prime &p1 = prime(1);
+    const NttPrime &p1 = ntt_prime(1);
     static const uint64_t crt = p1.pow(NTT_P0 % NTT_P1, NTT_P1 - 2);   // p0^-1 mod p1
     for (int c = 0; c < 2; c++)
         for (int n = 0; n < N; n++) {
@@ -196,17 +104,6 @@ void leaf_glwe(const uint64_t *blk, uint64_t *out) {
     out[N] = prescale(blk[BIG_N]);
 }
 
-template <class F>
-void parallel_nodes(size_t n, F &&f) {
-    const unsigned nt = (unsigned)std::max<size_t>(1, std::min<size_t>({16, (size_t)std::max(1u, std::thread::hardware_concurrency()), n}));
-    std::atomic<size_t> next{0};
-    auto work = [&] { for (size_t k; (k = next.fetch_add(1)) < n;) f(k); };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &x : th) x.join();
-}
-
 // one group: `count` blocks (1..2048) -> mask[2048], body[2048].  Node k of level lv holds the blocks = k mod (N >> lv);
 // its children at level lv - 1 are nodes k (even) and k + (N >> lv) (odd); a node is live when block k exists.
 void pack_group(const HostKey &hk, const uint64_t *blocks, size_t count, uint64_t *mask, uint64_t *body) {
@@ -215,7 +112,7 @@ void pack_group(const HostKey &hk, const uint64_t *blocks, size_t count, uint64_
         const size_t n_lv = (size_t)N >> lv, live = std::min(count, n_lv);
         prev.swap(cur);
         cur.assign(live * 2 * N, 0);
-        parallel_nodes(live, [&](size_t k) {
+        parallel_for(live, host_threads(16), 1, [&](size_t k) {
             const bool has_o = k + n_lv < count;
             if (lv == 1) {
                 std::vector<uint64_t> leaves(4 * N);

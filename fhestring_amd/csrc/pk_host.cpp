@@ -6,14 +6,13 @@
 #include <atomic>
 #include <cstring>
 #include <new>
-#include <thread>
 #include <vector>
 
 #include "../../include/fhestring_hip.h"
 #include "chacha_rng.h"
+#include "host_parallel.h"
+#include "keyfile.h"
 #include "pbs_kernels.h"
-
-int fhs_read_public_key_file(const char *path, uint32_t seed[8], std::vector<uint64_t> &body);
 
 namespace {
 
@@ -31,25 +30,6 @@ struct PublicKey {
 };
 
 inline uint32_t store32(uint64_t x) { return (uint32_t)((x + (1ull << 31)) >> 32); }
-
-// f(work item) over [0, n) on up to 16 host threads; every item has its own generator streams, so the result does not
-// depend on the thread count
-template <class F>
-void for_each_group(size_t n, F &&f) {
-    const size_t nt = std::min<size_t>({n, 16, std::max(1u, std::thread::hardware_concurrency())});
-    if (nt <= 1) {
-        for (size_t i = 0; i < n; i++) f(i);
-        return;
-    }
-    std::atomic<size_t> next{0};
-    auto work = [&] {
-        for (size_t i; (i = next.fetch_add(1)) < n;) f(i);
-    };
-    std::vector<std::thread> th;
-    for (size_t t = 1; t < nt; t++) th.emplace_back(work);
-    work();
-    for (auto &x : th) x.join();
-}
 
 // one group: mask = A U + E1, body = B U + E2 + messages, U binary -- both negacyclic products as sums of signed shifts
 void encrypt_group(const PublicKey &pk, const ChaKey &key, uint64_t g, const uint8_t *msg, size_t count, uint32_t *mask32,
@@ -145,7 +125,7 @@ int fhs_public_encrypt_str(void *pk_, const char *s, size_t len, size_t padding,
     std::vector<uint8_t> msg(4 * n, 0);
     for (size_t i = 0; i < len; i++)
         for (int d = 0; d < 4; d++) msg[4 * i + d] = ((uint8_t)s[i] >> (2 * d)) & 3;
-    for_each_group((4 * n + GROUP - 1) / GROUP, [&](size_t g) {
+    parallel_for((4 * n + GROUP - 1) / GROUP, host_threads(16), 1, [&](size_t g) {
         encrypt_group(*pk, key, g, msg.data() + g * GROUP, std::min(GROUP, 4 * n - g * GROUP), mask32 + g * N,
                       body32 + g * GROUP);
     });
@@ -157,7 +137,7 @@ int fhs_expand_public_str(const void *mask32_, const void *body32_, size_t n_tot
     const uint32_t *mask32 = static_cast<const uint32_t *>(mask32_), *body32 = static_cast<const uint32_t *>(body32_);
     if (!window_ok(n_total, first_char, count) || (count && (!mask32 || !body32 || !out))) return FHS_ERR_ARG;
     const size_t t0 = 4 * first_char, nb = 4 * count;
-    for_each_group((nb + 63) / 64, [&](size_t w) {
+    parallel_for((nb + 63) / 64, host_threads(16), 1, [&](size_t w) {
         for (size_t k = 64 * w; k < std::min(nb, 64 * w + 64); k++) {
             const size_t t = t0 + k;
             const uint32_t *a = mask32 + t / GROUP * N;

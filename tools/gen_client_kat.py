@@ -1,0 +1,79 @@
+#!/usr/bin/env python3
+"""Known-answer digests of the host-only client code -> tests/golden/client_kat.json.  CPU only, a few seconds.
+
+One insecure seeded client, MyClientKey(0xF5E57121), and everything the library derives from it on the host: the keys of
+every kind, the first string in each of the three ciphertext formats with its host expansion, and the host packing of
+that string.  Per array the file keeps the SHA-256 of its little-endian words, the first and the last word (the style
+of tests/golden/pbs_kat.json).  These are the product's own outputs, frozen: key generation, the generator streams, the
+exact host NTT behind pack_host and the thread fan-outs may be reorganised, but no word may change.  Regenerate only
+when a change of the client's outputs is intended, and say so in the commit:
+
+    python tools/gen_client_kat.py
+"""
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+SEED = 0xF5E57121
+TEXT, PADDING = "Hello, world", 4
+OUT = os.path.join(ROOT, "tests", "golden", "client_kat.json")
+
+
+def digest(a):
+    a = np.ascontiguousarray(a)
+    flat = a.reshape(-1)
+    return {"sha256": hashlib.sha256(a.astype(a.dtype.newbyteorder("<"), copy=False).tobytes()).hexdigest(),
+            "dtype": a.dtype.name, "words": int(flat.size), "first": int(flat[0]), "last": int(flat[-1])}
+
+
+def records():
+    """{name: digest} of a FRESH seeded client, in the order the calls are made (the call counters of the client and of
+    the public key decide the streams of the three encryptions: each is the first of its kind)."""
+    from fhestring_amd import api
+    ck = api.MyClientKey(SEED)
+    rec = {}
+    rec["lwe_sk"], rec["glwe_sk"] = map(digest, ck.secret_keys())
+    rec["bsk"], rec["ksk"], rec["bsk_mb2"] = digest(ck.bsk()), digest(ck.ksk()), digest(ck.bsk_mb2())
+    seed, bb, kb = ck.compressed_server_key()
+    rec["csk_seed"], rec["csk_bsk_bodies"], rec["csk_ksk_bodies"] = digest(seed), digest(bb), digest(kb)
+    ebsk, eksk = api.expand_compressed_server_key(seed, bb, kb)
+    rec["csk_expanded_bsk"], rec["csk_expanded_ksk"] = digest(ebsk), digest(eksk)
+    pack_key = ck.packing_key()
+    rec["packing_key"] = digest(pack_key)
+    pk_seed, pk_body = ck.public_key()
+    rec["pk_seed"], rec["pk_body"] = digest(pk_seed), digest(pk_body)
+    chars = ck.encrypt_str_raw(TEXT, PADDING)
+    rec["str"] = digest(chars)
+    cs = ck.encrypt_compressed(TEXT, PADDING)
+    rec["cstr_seed"], rec["cstr_bodies"], rec["cstr_expanded"] = digest(cs.seed), digest(cs.bodies), digest(cs.expand())
+    pp = ck.get_public_parameters()
+    pp.set_insecure_seed(1)
+    ps = pp.encrypt(TEXT, PADDING)
+    rec["pstr_mask32"], rec["pstr_body32"], rec["pstr_expanded"] = digest(ps.mask32), digest(ps.body32), digest(ps.expand())
+    blocks = chars.reshape(-1, chars.shape[-1])
+    mask64, body64 = api.pack_host(pack_key, blocks)
+    rec["pack_mask64"], rec["pack_body64"] = digest(mask64), digest(body64)
+    p16 = api.pack_switch16(mask64, body64, blocks.shape[0])
+    rec["pack_mask16"], rec["pack_body16"] = digest(p16.mask16), digest(p16.body16)
+    p32 = api.pack_switch32(mask64, body64, blocks.shape[0])
+    rec["pack_mask32"], rec["pack_body32"] = digest(p32.mask32), digest(p32.body32)
+    assert ck.decrypt_str_raw(chars) == TEXT and ck.decrypt_packed(p16) == TEXT
+    return rec
+
+
+def main():
+    rec = {"seed": "0x%X" % SEED, "text": TEXT, "padding": PADDING, "generator": "tools/gen_client_kat.py",
+           "arrays": records()}
+    with open(OUT, "w") as f:
+        json.dump(rec, f, indent=0, separators=(",", ":"))
+        f.write("\n")
+    print("wrote %s (%d bytes)" % (OUT, os.path.getsize(OUT)), file=sys.stderr)
+
+
+if __name__ == "__main__":
+    main()

@@ -1,5 +1,5 @@
 // ASan/UBSan driver of the product's HOST-ONLY code (no device is touched): client keygen / encrypt / decrypt /
-// key files (client.cpp), public-key encryption and its expansion (pk_host.cpp), the twiddle and key transforms (ntt_tables.cpp, fft_tables.cpp), and the whole DAG layer --
+// key files (client.cpp), public-key encryption and its expansion (pk_host.cpp), the exact host NTT (host_ntt.cpp), the twiddle and key transforms (ntt_tables.cpp, fft_tables.cpp), and the whole DAG layer --
 // engine.cpp graph logic, radix.cpp, strings.cpp, capi_*.cpp -- through a planner context (fhs_ctx_create_planner),
 // which records and levelises every string op of the C ABI without executing anything.
 // Built by `make -C fhestring_amd/csrc asan`; run by tests/test_sanitizers.py.  CPU only.
@@ -11,6 +11,8 @@
 
 #include "../../include/fhestring_hip.h"
 #include "../../fhestring_amd/csrc/fft_tables.h"
+#include "../../fhestring_amd/csrc/host_ntt.h"
+#include "../../fhestring_amd/csrc/keyfile.h"
 #include "../../fhestring_amd/csrc/ntt_tables.h"
 
 static int fails = 0;
@@ -72,6 +74,31 @@ int main() {
         fhs_public_key_destroy(pk);
         fhs_public_key_destroy(pk2);
     }
+    {   // the key-file readers (keyfile.h) return what the writers were given; a file that cannot be opened is an error
+        const std::string kf = "/tmp/fhs_asan_kind.bin";
+        std::vector<uint64_t> a, b;
+        uint32_t seed[8], cseed[8];
+        CHECK(fhs_read_server_key_file(path.c_str(), a, b) == FHS_OK && a.size() == FHS_BSK_WORDS && b.size() == FHS_KSK_WORDS);
+        CHECK(!std::memcmp(a.data(), fhs_client_bsk(ck), a.size() * 8) && !std::memcmp(b.data(), fhs_client_ksk(ck), b.size() * 8));
+        CHECK(fhs_client_save(ck, kf.c_str(), 1) == FHS_OK && fhs_read_server_key_file(kf.c_str(), a, b) == FHS_OK);
+        CHECK(!std::memcmp(a.data(), fhs_client_bsk(ck), a.size() * 8) && !std::memcmp(b.data(), fhs_client_ksk(ck), b.size() * 8));
+        CHECK(fhs_client_save_multibit_key(ck, kf.c_str()) == FHS_OK && fhs_read_multibit_key_file(kf.c_str(), a) == FHS_OK);
+        CHECK(a.size() == FHS_BSK_MB2_WORDS && !std::memcmp(a.data(), fhs_client_bsk_mb2(ck), a.size() * 8));
+        std::vector<uint64_t> bb(FHS_CBSK_BODY_WORDS), kb(FHS_CKSK_BODY_WORDS);
+        CHECK(fhs_client_compressed_server_key(ck, cseed, bb.data(), kb.data()) == FHS_OK);
+        CHECK(fhs_client_save_compressed_server_key(ck, kf.c_str()) == FHS_OK &&
+              fhs_read_compressed_server_key_file(kf.c_str(), seed, a, b) == FHS_OK);
+        CHECK(!std::memcmp(seed, cseed, 32) && a == bb && b == kb);
+        CHECK(fhs_client_save_packing_key(ck, kf.c_str()) == FHS_OK && fhs_read_packing_key_file(kf.c_str(), a) == FHS_OK);
+        CHECK(a.size() == FHS_PACK_KEY_WORDS && !std::memcmp(a.data(), fhs_client_packing_key(ck), a.size() * 8));
+        CHECK(fhs_read_multibit_key_file(kf.c_str(), b) == FHS_ERR_STATE);                         // kind 5
+        CHECK(fhs_client_public_key(ck, cseed, bb.data()) == FHS_OK && fhs_client_save_public_key(ck, kf.c_str()) == FHS_OK);
+        CHECK(fhs_read_public_key_file(kf.c_str(), seed, a) == FHS_OK && !std::memcmp(seed, cseed, 32) && a.size() == 2048 &&
+              !std::memcmp(a.data(), bb.data(), 2048 * 8));
+        std::remove(kf.c_str());
+        CHECK(fhs_read_public_key_file(kf.c_str(), seed, a) == FHS_ERR_STATE);
+        CHECK(fhs_client_save(ck, "/nonexistent-directory/key.bin", 0) == FHS_ERR_STATE);
+    }
     std::remove(path.c_str());
 
     // ---- host transforms of the key ---------------------------------------------------------------------------
@@ -87,7 +114,68 @@ int main() {
         std::vector<uint64_t> one(fhs_client_bsk(ck), fhs_client_bsk(ck) + 4 * 2048);
         // convert_bsk_to_ntt walks all 742 GGSWs: give it the real key (reads only)
         std::vector<double> all((size_t)742 * 4 * 2 * 2048);
-        fhs::convert_bsk_to_ntt(fhs_client_bsk(ck), all.data(), 4);
+        fhs::convert_bsk_to_ntt(fhs_client_bsk(ck), all.data());
+    }
+
+    // ---- host NTT (host_ntt.h): chosen inputs, both primes ---------------------------------------------------------
+    for (int q = 0; q < 2; q++) {
+        using namespace fhs;
+        constexpr unsigned N = 2048;
+        const NttPrime &pt = ntt_prime(q);
+        const uint64_t p = pt.p;
+        uint64_t lcg = 0x9E3779B97F4A7C15ull + (uint64_t)q;
+        auto rnd = [&] { lcg = lcg * 6364136223846793005ull + 1442695040888963407ull; return (lcg >> 11) % p; };
+        std::vector<uint64_t> r(N), edge(N, 0);
+        for (auto &x : r) x = rnd();
+        edge[0] = edge[1] = edge[N - 1] = p - 1;
+        // (a) forward, inverse, times 1/N: the identity
+        for (const std::vector<uint64_t> *in : {&r, &edge}) {
+            std::vector<uint64_t> a(*in);
+            ntt_forward(a.data(), pt);
+            ntt_inverse(a.data(), pt);
+            for (auto &x : a) x = pt.mul(x, pt.ninv);
+            CHECK(a == *in);
+        }
+        // (b) the transform product with a 16-term polynomial against the schoolbook negacyclic product mod p
+        const unsigned at[16] = {0, 1, 2, 3, 17, 100, 511, 512, 1023, 1024, 1025, 1500, 1999, 2045, 2046, 2047};
+        std::vector<uint64_t> s16(N, 0), want(N, 0), fa(r), fb;
+        for (unsigned j : at) s16[j] = rnd();
+        for (unsigned j : at)
+            for (unsigned i = 0; i < N; i++) {
+                const uint64_t t = pt.mul(r[i], s16[j]);
+                uint64_t &w = want[(i + j) % N];
+                w = i + j < N ? (w + t) % p : (w + p - t) % p;
+            }
+        fb = s16;
+        ntt_forward(fa.data(), pt);
+        ntt_forward(fb.data(), pt);
+        for (unsigned i = 0; i < N; i++) fa[i] = pt.mul(pt.mul(fa[i], fb[i]), pt.ninv);
+        ntt_inverse(fa.data(), pt);
+        CHECK(fa == want);
+    }
+    {   // (c) convert_polys_to_ntt on monomials: the device layout and the rounding to the key grid
+        using namespace fhs;
+        constexpr unsigned N = 2048;
+        struct Case { uint64_t coeff; unsigned k; int quant_bits; bool zero; };
+        const Case cases[] = {{1ull << 6, 0, 6, false}, {1ull << 6, 1, 6, false}, {1ull << 6, 2047, 6, false},
+                              {1ull << 7, 1, 7, false}, {1ull << 5, 1, 6, false}, {(1ull << 5) - 1, 1, 6, true}};
+        for (const Case &cs : cases) {
+            std::vector<uint64_t> poly(N, 0);
+            std::vector<double> out(2 * N, -1.0);
+            poly[cs.k] = cs.coeff;
+            convert_polys_to_ntt(poly.data(), out.data(), 1, cs.quant_bits);
+            int bad = 0;
+            for (int q = 0; q < 2; q++) {
+                const NttPrime &pt = ntt_prime(q);
+                for (unsigned idx = 0; idx < N; idx++) {
+                    const unsigned lane = idx >> 5, c = idx & 31;
+                    const uint64_t v = pt.mul(pt.pow(pt.psi, (uint64_t)(2 * bitrev11(idx) + 1) * cs.k % 4096), pt.ninv);
+                    const double want = cs.zero ? 0.0 : v > pt.p / 2 ? -(double)(pt.p - v) : (double)v;
+                    bad += out[(size_t)q * N + ((c >> 1) * 64 + lane) * 2 + (c & 1)] != want;
+                }
+            }
+            CHECK(bad == 0);
+        }
     }
 
     // ---- DAG layer through the planner ------------------------------------------------------------------------
