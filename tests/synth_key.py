@@ -91,8 +91,29 @@ def pair_bits(s):
     return np.stack([a * (1 - b), (1 - a) * b, a * b], axis=1).reshape(-1)
 
 
-def _product(desc, g, d):
-    """Sparse external product of the digits d [2][2048] with GGSW g -> [2][2048]."""
+def negacyclic_matrix(d):
+    """[2048][2048], T[n][j] = d[n - j], negated where the index wrapped: T @ k is the negacyclic product d * k.  A
+    strided view of (-d[1:], d), nothing is copied."""
+    ext = np.concatenate([-d[1:], d])
+    return np.lib.stride_tricks.as_strided(ext[N - 1:], (N, N), (ext.strides[0], -ext.strides[0]), writeable=False)
+
+
+def dense_product(key_g, d):
+    """Schoolbook external product of the digits d [2][2048] with a dense GGSW [row 2][col 2][2048] in wrapping uint64."""
+    out = np.zeros((2, N), U)
+    for row in range(2):
+        if d[row].any():
+            out += (negacyclic_matrix(d[row]) @ key_g[row].T).T
+    return [out[0], out[1]]
+
+
+def _product(desc, g, d, dense=None, log=None):
+    """Sparse external product of the digits d [2][2048] with GGSW g -> [2][2048]; GGSWs in `dense` {g: [2][2][2048]}
+    are multiplied out in full, and (g, d) is appended to `log`."""
+    if dense is not None and g in dense:
+        if log is not None:
+            log.append((g, np.stack(d)))
+        return dense_product(dense[g], d)
     out = [np.zeros(N, U), np.zeros(N, U)]
     for col in range(2):
         for row in range(2):
@@ -105,7 +126,7 @@ def _start(ms, lut):
     return [np.zeros(N, U), rot(np.asarray(lut, U), (2 * N - int(ms[LWE_N])) & (2 * N - 1))]
 
 
-def blind_rotate_ref(desc, ms, lut, digit=digit, ties=None):
+def blind_rotate_ref(desc, ms, lut, digit=digit, ties=None, dense=None, log=None):
     """Classic blind rotation, ACC += GGSW_i (.) (X^a ACC - ACC) per mask element a = ms[i] != 0 -> [2, 2048].
     ties: a list that receives, per product, the number of body differences whose low 41 bits equal 2^40."""
     acc = _start(ms, lut)
@@ -116,12 +137,12 @@ def blind_rotate_ref(desc, ms, lut, digit=digit, ties=None):
         diff = [rot(acc[r], a) - acc[r] for r in range(2)]
         if ties is not None:
             ties.append(int(np.count_nonzero((diff[1] & U((1 << 41) - 1)) == U(1 << 40))))
-        p = _product(desc, i, [digit(x) for x in diff])
+        p = _product(desc, i, [digit(x) for x in diff], dense, log)
         acc = [acc[c] + p[c] for c in range(2)]
     return np.stack(acc)
 
 
-def blind_rotate_mb2_ref(desc, ms, lut, digit=digit):
+def blind_rotate_mb2_ref(desc, ms, lut, digit=digit, dense=None, log=None):
     """Two key bits per step: ACC += sum_t (X^e_t - 1) (K_t (.) ACC), t over (e1, e2, e1 + e2) -> [2, 2048]."""
     acc = _start(ms, lut)
     for p in range(LWE_N // 2):
@@ -131,7 +152,7 @@ def blind_rotate_mb2_ref(desc, ms, lut, digit=digit):
         d = [digit(x) for x in acc]
         new = list(acc)
         for t, e in enumerate((e1, e2, (e1 + e2) & (2 * N - 1))):
-            pt = _product(desc, 3 * p + t, d)
+            pt = _product(desc, 3 * p + t, d, dense, log)
             new = [new[c] + rot(pt[c], e) - pt[c] for c in range(2)]
         acc = new
     return np.stack(acc)
@@ -273,3 +294,398 @@ def dense_case():
     m = material()
     rows = rows_of(m, "single", "pair", "sparse")
     return m.ks[rows], m.ms[rows], (m.lut_idx[rows] & np.uint32(1))
+
+
+# ---- keyswitch under a synthetic key ---------------------------------------------------------------------------------
+#
+# ks[j] = b * [j == 742] - sum_{i < 2048, l < 5} d(i, l) * KSK[5 i + l][j] in wrapping uint64, of which the library only
+# ever shows (ks + 2^51) >> 52.  The key below makes all 64 bits decide those 12:
+#   * top part: column j < 742 owns one input coefficient top[j] with KSK[(top[j], l)][j] = -2^(61 - 3 l) and zero in
+#     every other column, so the column's output carries that coefficient's 15-bit rounding v in bits 49..63; v = 4 mod 8
+#     is an odd multiple of 2^51, a modulus-switch edge (column 742: the body is one);
+#   * dense part: the other 1306 coefficients hold full 64-bit words in every column -- one of 32 word rows (balanced bytes
+#     -128 and 127 in every plane, carries that run through all planes, random words), the same in all five levels except
+#     that one level, the twin, holds the word + 1.  Digits that sum to zero over a coefficient's five levels cancel
+#     exactly mod 2^64 and leave minus the twin's digit in every column at once.
+# An "edge" row therefore has all 743 outputs at edge + r, r in {0, -1, +1} its residual: one unit of error of either
+# sign in any byte plane of any key word with a non-zero digit changes a visible value on a row with r = 0 or r = -1.
+KS_N, KS_LEVELS, KS_COLS = 2048, 5, 743
+KS_SEED = 0x4B5EED
+KS_ROWS = 63                      # odd: a row changes its position in a tile of 32 between the repeats of a batch
+KS_WIDTHS = (1, 128, 129, 300, 600, 1281, 2817)
+KS_GROUPS = 32
+KS_SPECIAL = tuple(0x80 << 8 * b for b in range(8)) + tuple(0x7F << 8 * b for b in range(8)) + (
+    0x8080808080808080, 0x7F7F7F7F7F7F7F7F, 0xFFFFFFFFFFFFFFFF, 0x0000000000000080)
+_M64 = (1 << 64) - 1
+
+
+def ks_digits(a, rounding=1 << 48):
+    """[..., 2048] torus words -> [..., 10240] int64 digits at index 5 i + l: 15-bit rounding (the sum wraps: words
+    >= 2^64 - 2^48 round to zero), five balanced base-8 digits, least significant level (l = 4) first with carry, top
+    carry dropped."""
+    v = ((np.asarray(a, U) + U(rounding)) >> U(49)).astype(np.int64)
+    out = np.empty(v.shape + (KS_LEVELS,), np.int64)
+    for l in range(KS_LEVELS - 1, -1, -1):
+        d = v & 7
+        v >>= 3
+        high = d >= 4
+        out[..., l] = d - 8 * high
+        v += high
+    return out.reshape(v.shape[:-1] + (-1,))
+
+
+def keyswitch_ref(ksk, cts, rounding=1 << 48, cols=slice(None)):
+    """cts [R][2049], ksk [10240][743] -> ks [R][743] (or the chosen columns) in wrapping uint64."""
+    d = ks_digits(cts[:, :KS_N], rounding).view(U)
+    out = U(0) - d @ ksk[:, cols]
+    body = np.zeros(KS_COLS, U)
+    body[KS_COLS - 1] = 1
+    return out + cts[:, KS_N:] * body[cols]
+
+
+def balanced_bytes(w):
+    """[...] uint64 -> [..., 8] int8 with w = sum_b s_b 2^(8 b) mod 2^64, s_b in [-128, 127]."""
+    w = np.array(w, U)
+    out = np.empty(w.shape + (8,), np.int8)
+    for b in range(8):
+        s = (w & U(0xFF)).astype(np.uint8).view(np.int8)
+        out[..., b] = s
+        w = (w - s.astype(np.int64).view(U)) >> U(8)
+    return out
+
+
+def ks_word(digits, low=0):
+    """The torus word whose digits are `digits` [5] (most significant level first) and whose distance to the 15-bit grid
+    is low in [-2^48, 2^48)."""
+    v = sum(int(d) << 3 * (KS_LEVELS - 1 - l) for l, d in enumerate(digits)) & 0x7FFF
+    return ((v << 49) + int(low)) & _M64
+
+
+def ks_launch_shape(B, cus=256):
+    """What launch_keyswitch_mfma (ks_kernels.hip) does with B rows on `cus` CUs: ("split-k", workgroups per split,
+    splits) below 129 rows, else ("ring", unsliced tiles, sliced tiles, slices of K per sliced tile)."""
+    if B < 129:
+        tgroups, splits = ((B + 31) // 32 + 3) // 4, 1
+        while splits < 16 and tgroups * 24 * splits < 256:
+            splits *= 2
+        return ("split-k", tgroups * 24, splits)
+    tiles = 24 * ((B + 255) // 256)
+    full = tiles // cus * cus
+    rem, slices = tiles - full, 1
+    if rem:
+        slices = next((c for c in (8, 4, 2) if rem * c <= cus), 1)
+    if slices == 1:
+        full, rem = tiles, 0
+    return ("ring", full, rem, slices)
+
+
+# the launch shapes of KS_WIDTHS on 256 CUs; tests/test_gpu_synth_key.py leaves out a width whose shape differs elsewhere
+KS_SHAPES_256 = {1: ("split-k", 24, 16), 128: ("split-k", 24, 16), 129: ("ring", 0, 24, 8), 300: ("ring", 0, 48, 4),
+                 600: ("ring", 0, 72, 2), 1281: ("ring", 144, 0, 1), 2817: ("ring", 256, 32, 8)}
+
+
+def ks_batch(n):
+    """The row that each of the n ciphertexts of a batch repeats."""
+    return np.arange(n) % KS_ROWS
+
+
+class KsMaterial:
+    """ksk [10240][743]; top [742]: the input coefficient of each column; dense [1306], group, twin: the other
+    coefficients, their word row and twin level; cts [63][2049], kinds, residual (edge and input rows)."""
+
+
+def _zero_sum_digits(rng, twin, rho):
+    """[n][5] digits in [-4, 3] that sum to zero per coefficient, with -rho at the twin level."""
+    n = len(twin)
+    d = np.zeros((n, KS_LEVELS), np.int64)
+    todo = np.arange(n)
+    while len(todo):
+        free = rng.integers(-4, 4, (len(todo), KS_LEVELS))
+        free[np.arange(len(todo)), twin[todo]] = -rho[todo]
+        last = (twin[todo] + 1) % KS_LEVELS                      # the level that closes the sum
+        free[np.arange(len(todo)), last] = 0
+        free[np.arange(len(todo)), last] = -free.sum(axis=1)
+        ok = (free[np.arange(len(todo)), last] >= -4) & (free[np.arange(len(todo)), last] <= 3)
+        d[todo[ok]] = free[ok]
+        todo = todo[~ok]
+    return d
+
+
+@functools.lru_cache(maxsize=None)
+def keyswitch_material():
+    rng = np.random.default_rng(KS_SEED)
+    m = KsMaterial()
+    perm = rng.permutation(KS_N)
+    m.top, m.dense = perm[:KS_COLS - 1], np.sort(perm[KS_COLS - 1:])
+    n_dense = len(m.dense)
+    ksk = np.zeros((KS_N, KS_LEVELS, KS_COLS), U)
+    for l in range(KS_LEVELS):
+        ksk[m.top, l, np.arange(KS_COLS - 1)] = U(-(1 << (61 - 3 * l)) & _M64)
+    words = np.empty((KS_GROUPS, KS_COLS), U)
+    special = np.array(KS_SPECIAL, U)
+    for g in range(len(special)):                                # every column meets every special word
+        words[g] = special[(g + np.arange(KS_COLS)) % len(special)]
+    pool = np.array([0x80, 0x7F, 0xFF, 0x00], U)
+    for g in range(len(special), KS_GROUPS):                     # random words, half of their bytes from the pool
+        b = np.where(rng.integers(0, 2, (KS_COLS, 8)) == 1, pool[rng.integers(0, 4, (KS_COLS, 8))],
+                     rng.integers(0, 256, (KS_COLS, 8)).astype(U))
+        words[g] = (b << (U(8) * np.arange(8, dtype=U))).sum(axis=1, dtype=U)
+    m.group = rng.integers(0, KS_GROUPS, n_dense)
+    m.group[:KS_GROUPS] = np.arange(KS_GROUPS)
+    m.twin = rng.integers(0, KS_LEVELS, n_dense)
+    ksk[m.dense] = words[m.group][:, None, :]
+    ksk[m.dense, m.twin] += U(1)
+    m.ksk = ksk.reshape(KS_N * KS_LEVELS, KS_COLS)
+
+    def dense_part(row, residual):
+        """Digits that sum to zero over the five levels of every dense coefficient, so that the words cancel; the twins'
+        digits are random too and sum to minus the residual over the row.  24 coefficients hold words that round to zero
+        digits instead (wrapping ones among them)."""
+        rho = rng.integers(-3, 4, n_dense)                       # minus the twin's digit
+        quiet = rng.choice(n_dense, 24, replace=False)
+        rho[quiet] = 0
+        busy = np.setdiff1d(np.arange(n_dense), quiet)
+        while rho.sum() != residual:
+            i, step = int(rng.choice(busy)), (1 if rho.sum() < residual else -1)
+            if -3 <= rho[i] + step <= 3:
+                rho[i] += step
+        d = _zero_sum_digits(rng, m.twin, rho)
+        for k, i in enumerate(m.dense):
+            row[i] = ks_word(d[k], int(rng.integers(-(1 << 48), 1 << 48)))
+        wraps = (_M64 - (1 << 48) + 1, _M64, 0, (1 << 48) - 1)   # the first and last word that wrap, and that do not
+        for k, i in enumerate(quiet):
+            row[m.dense[i]] = wraps[k] if k < 4 else (int(rng.integers(-(1 << 48), 1 << 48)) & _M64)
+
+    def top_part(row, r, input_edges):
+        """v = 4 mod 8 on every column: an edge.  Distances to the grid: exact ties (low 49 bits 2^48, rounding up), the
+        last word below a tie, on the grid, random.  input_edges: a quarter of the columns instead hold v = 3 mod 8 with
+        the low 49 bits at 2^48 - 1 (one unit below the tie that would reach the edge) or a word that wraps to zero."""
+        for j, i in enumerate(m.top):
+            v = 8 * int(rng.integers(0, 4096)) + 4
+            low = (-(1 << 48), (1 << 48) - 1, 0, int(rng.integers(-(1 << 48), 1 << 48)))[int(rng.integers(0, 4))]
+            if input_edges and j % 4 == r % 4:
+                if rng.integers(0, 4):
+                    v, low = v - 1, (1 << 48) - 1
+                else:
+                    v, low = 0x7FFF, int(rng.integers(1 << 48, 1 << 49))   # >= 2^64 - 2^48
+            row[i] = ((v << 49) + low) & _M64
+
+    rows, kinds, residual = [], [], []
+    for r in range(KS_ROWS):
+        row = [0] * (KS_N + 1)
+        row[KS_N] = (2 * int(rng.integers(0, 4096)) + 1) << 51   # the body: an edge
+        if r == 0 or r == 32:                                    # every digit -4 / every digit 3
+            kind, d = ("neg4", "pos3")[r // 32], (-4, 3)[r // 32]
+            row[:KS_N] = [ks_word([d] * 5, int(rng.integers(-(1 << 48), 1 << 48))) for _ in range(KS_N)]
+        elif r == 1:
+            kind = "zero"                                        # a trivial ciphertext
+        elif r in (16, 17, 48, 49):
+            kind = "full"
+            row[:] = [int(x) for x in rng.integers(0, 1 << 64, KS_N + 1, dtype=U)]
+        else:
+            kind = ("edge", "input")[r & 1]
+            residual.append((r, (0, -1, 1)[(r // 2) % 3]))
+            dense_part(row, residual[-1][1])
+            top_part(row, r, kind == "input")
+        rows.append(np.array(row, dtype=U))
+        kinds.append(kind)
+    m.cts, m.kinds, m.residual = np.stack(rows), kinds, dict(residual)
+    for a in (m.ksk, m.cts, m.top, m.dense, m.group, m.twin):
+        a.setflags(write=False)
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def keyswitch_reference():
+    """ks [63][743] in all 64 bits (3.5 s of uint64 matmul, once per process)."""
+    m = keyswitch_material()
+    ks = keyswitch_ref(m.ksk, m.cts)
+    ks.setflags(write=False)
+    return ks
+
+
+# ---- the exact kernels near the top of their CRT range ---------------------------------------------------------------
+#
+# A few GGSWs of the classic key and the matching triples of the pair key are dense with every coefficient at full
+# magnitude: the words 2^63 (centred: -2^63) and 2^63 - 2^7 (on the 2^6 grid of the classic key and the 2^7 grid of the
+# pair key), with the signs aligned against the negacyclic wrap so that the terms of one chosen coefficient all add.
+# Under a constant look-up table -- 2^62 for the classic arithmetic, whose digits are those of X^2048 ACC - ACC = -2^63,
+# and 2^63 for the two-bit one, whose digits are those of ACC itself -- every body digit is -2^22.  In the two-step rows
+# a first, monomial step (GGSW 100 / pair 50, whose mask polynomial holds c = odd * 2^40) leaves the mask at an odd
+# multiple of 2^62 (classic) / at 2^63 (two-bit) everywhere, so that both rows of the dense GGSW get the digit -2^22.
+# Largest product coefficient, as a true integer in units of the key grid (tests/test_synth_key.py prints them):
+#     classic kernel, one-step rows   2^90.00   (2048 * 2^22 * 2^57)
+#     classic kernel, two-step rows   2^91.00   the bound stated for blind_rotate_kernel, reached exactly
+#     two-bit kernel, one-pair rows   2^91.00   (2048 * 2^22 * 4 * 2^56: e1 = e2 = 2048 cancels the third key)
+#     two-bit kernel, two-step rows   2^92.00   against the stated 2^92.6 and a CRT range of p0 p1 / 2 = 2^93.0
+# The f64 arithmetics on the same rows, CPU mirrors (bit-identical to the kernels) against the integer references, on the
+# rows whose last step is their one dense product:
+#     mode 3 (f64 FFT)          max |mirror - reference| = 2^45.58
+#     mode 4 (f64 FFT, two-bit) max |mirror - reference| = 2^48.00
+# T3X and T4X are 8 x those, for the reason given at T3 / T4.  Both are ABOVE one digit step of 2^41 (a product of 2^96
+# to 2^99 in torus units has an f64 ulp of 2^44 to 2^47): where another step follows a dense product the digits of that
+# step differ from the integer reference's and the distance is no longer a rounding error (2^52.42 measured); those rows
+# are held to the mirrors bit for bit like all others, and to no distance.
+X_DENSE = (400, 401, 600)          # classic GGSWs; the pair triples are those of the pairs 200 and 300
+X_PAIRS = (200, 300)
+X_FIRST, X_FIRST_PAIR = 100, 50    # the first step of the two-step rows
+X_SEED = 0xE87E3E
+NTT_P0, NTT_P1 = 0x7FFFFFFEC001, 0x7FFFFFFE7001
+K_NEG, K_POS = 1 << 63, (1 << 63) - (1 << 7)
+T3X = 8 * 2 ** 45.58
+T4X = 8 * 2 ** 48.00
+
+
+def _aligned(n_star, sign):
+    """A full-magnitude polynomial whose terms in coefficient n_star of a product with constant digits all add:
+    sign * magnitude up to n_star, the opposite sign beyond (those terms wrap and are negated)."""
+    lo, hi = (K_NEG, K_POS) if sign < 0 else (K_POS, K_NEG)
+    return np.where(_ARANGE <= n_star, U(lo), U(hi))
+
+
+def dense_product_true(key_g, d, grid_bits):
+    """The same product as true integers in units of 2^grid_bits, key words centred -> [2][2048] Python integers.
+    Three 20-bit limbs of the key keep every partial sum below 2^54."""
+    kc = key_g.view(np.int64) >> grid_bits
+    limbs = [kc & ((1 << 20) - 1), (kc >> 20) & ((1 << 20) - 1), kc >> 40]
+    parts = [np.zeros((2, N), np.int64) for _ in limbs]
+    for row in range(2):
+        if d[row].any():
+            t = negacyclic_matrix(d[row].view(np.int64))
+            for part, limb in zip(parts, limbs):
+                part += (t @ limb[row].T).T
+    return sum(part.astype(object) << (20 * k) for k, part in enumerate(parts))
+
+
+def wrap_to_range(x, modulus, grid_bits):
+    """What a CRT of range `modulus` would make of the true integers x: the representative in (-M/2, M/2], then the
+    torus word x * 2^grid_bits mod 2^64."""
+    out = np.empty(x.shape, U)
+    for idx, v in np.ndenumerate(x):
+        v = int(v) % modulus
+        if v > modulus // 2:
+            v -= modulus
+        out[idx] = (v << grid_bits) & _M64
+    return out
+
+
+def _set_mono(key, desc, where, mono):
+    key_poly = key[where[0], where[1], where[2]]
+    key_poly[:] = 0
+    desc[where] = mono
+    for coef, e in mono:
+        w = int(key_poly[e & (N - 1)]) + (coef if e < N else -coef)
+        key_poly[e & (N - 1)] = U(w & _M64)
+
+
+class ExtremeMaterial:
+    """bsk, bsk_mb2 with their descriptions and dense {g: [2][2][2048]} / dense_mb2 {3 p + t: ...}; luts [2][2048]:
+    constant 2^62, constant 2^63; ks [R][743], ms, lut_idx, kinds ("one", "pair", "two"), one_dense, one_dense_mb2."""
+
+
+@functools.lru_cache(maxsize=None)
+def extreme_material():
+    base = material()
+    rng = np.random.default_rng(X_SEED)
+    x = ExtremeMaterial()
+    x.bsk, x.bsk_mb2 = base.bsk.copy(), base.bsk_mb2.copy()
+    x.desc, x.desc_mb2 = dict(base.desc), dict(base.desc_mb2)
+    # dense GGSWs.  400 / pair 200, keys 1 and 2: every coefficient -2^63, all 2048 terms of coefficient 2047 add;
+    # 401, 600 / the other triples: other aligned coefficients and signs per polynomial, and random signs
+    n_stars = (N - 1, 0, 1023, 1024, 2046, 1, 777, N - 1)
+    def ggsw(kind):
+        g = np.empty((2, 2, N), U)
+        for k in range(4):
+            if kind == 0:
+                g[k >> 1, k & 1] = K_NEG
+            elif kind == 1:
+                g[k >> 1, k & 1] = _aligned(n_stars[int(rng.integers(0, 8))], (-1, 1)[int(rng.integers(0, 2))])
+            else:
+                g[k >> 1, k & 1] = np.where(rng.integers(0, 2, N) == 1, U(K_NEG), U(K_POS))
+        return g
+    x.dense = {g: ggsw(k) for k, g in enumerate(X_DENSE)}
+    x.dense_mb2 = {3 * p + t: ggsw((0, 0, 1, 1, 2, 1)[3 * k + t]) for k, p in enumerate(X_PAIRS) for t in range(3)}
+    for g, poly in x.dense.items():
+        x.bsk[g] = poly
+    for g, poly in x.dense_mb2.items():
+        x.bsk_mb2[g] = poly
+    # first steps: c = odd * 2^40 in the polynomial that takes the body digits into the mask
+    for key, desc, g in ((x.bsk, x.desc, X_FIRST), (x.bsk_mb2, x.desc_mb2, 3 * X_FIRST_PAIR)):
+        _set_mono(key, desc, (g, 1, 0), [((2 * int(rng.integers(0, 512)) + 1) << 40, int(rng.integers(0, 2 * N)))])
+
+    x.luts = np.stack([np.full(N, 1 << 62, U), np.full(N, 1 << 63, U)])
+    masks = [("one", {400: 2048}), ("one", {401: 2048}), ("one", {600: 2048}), ("one", {400: 1}), ("one", {401: 1024}),
+             ("one", {600: 4095}), ("one", {400: 2047}), ("one", {601: 2048}),
+             ("pair", {400: 2048, 401: 2048}), ("pair", {400: 2048, 401: 1}), ("pair", {600: 2048, 601: 2048}),
+             ("pair", {600: 2049, 601: 2047}), ("pair", {400: 2048, 401: 4095}),
+             ("two", {100: 2048, 400: 2048}), ("two", {100: 2048, 400: 2048, 401: 2048}), ("two", {100: 2048, 600: 2048}),
+             ("two", {100: 2048, 101: 2048, 600: 2048, 601: 2048})]
+    rows, lut_idx, kinds = [], [], []
+    for k, (kind, mask) in enumerate(masks):
+        for lut in range(2):
+            row = [0] * (LWE_N + 1)
+            for i, e in mask.items():
+                row[i] = _torus(e, (k + lut) % 3)
+            row[LWE_N] = (0, 0xFFF8000000000000, (1 << 51) - 1)[k % 3]       # all three switch to 0
+            rows.append(np.array(row, dtype=U)); lut_idx.append(lut); kinds.append(kind)
+    x.ks = np.stack(rows)
+    x.ms = mod_switch(x.ks)
+    x.lut_idx = np.array(lut_idx, np.uint32)
+    x.kinds = kinds
+    # rows with ONE dense product, in the last step, in the classic / the two-bit arithmetic: where the f64 arithmetics
+    # are bounded (the rounding of a dense product is above a digit step and changes the digits of any step after it)
+    x.one_dense = [r for r in range(len(rows)) if np.count_nonzero(x.ms[r, list(X_DENSE)]) == 1
+                   and int(np.flatnonzero(x.ms[r, :LWE_N])[-1]) in X_DENSE]
+    x.one_dense_mb2 = [r for r in range(len(rows)) if sum(bool(x.ms[r, 2 * p] | x.ms[r, 2 * p + 1]) for p in X_PAIRS) == 1]
+    for a in (x.bsk, x.bsk_mb2, x.luts, x.ks, x.ms, x.lut_idx):
+        a.setflags(write=False)
+    return x
+
+
+class ExtremeReferences:
+    """acc, acc_mb2 [R][2][2048], out, out_mb2 [R][2049] as in References; products, products_mb2: per row the dense
+    products as (true integers in grid units [2][2048], the same product in wrapping uint64 [2][2048])."""
+
+
+@functools.lru_cache(maxsize=None)
+def extreme_references():
+    x = extreme_material()
+    ref = ExtremeReferences()
+    ref.products, ref.products_mb2 = [], []
+    acc, acc_mb2 = [], []
+    for r in range(len(x.ks)):
+        ms, lut = x.ms[r], x.luts[x.lut_idx[r]]
+        log, log_mb2 = [], []
+        acc.append(blind_rotate_ref(x.desc, ms, lut, dense=x.dense, log=log))
+        acc_mb2.append(blind_rotate_mb2_ref(x.desc_mb2, ms, lut, dense=x.dense_mb2, log=log_mb2))
+        ref.products.append([(dense_product_true(x.dense[g], d, 6), np.stack(dense_product(x.dense[g], d))) for g, d in log])
+        found = []
+        for (g, d), _, _ in zip(*[iter(log_mb2)] * 3):                # the three keys of a pair see the same digits
+            p = g // 3
+            e = (int(ms[2 * p]), int(ms[2 * p + 1]))
+            # the combined key K1 (X^e1 - 1) + K2 (X^e2 - 1) + K3 (X^(e1+e2) - 1) of centred words in units of 2^7: below
+            # 6 * 2^56
+            comb = np.zeros((2, 2, N), np.int64)
+            wrapping = np.zeros((2, N), U)
+            for t, et in enumerate(e + ((e[0] + e[1]) & (2 * N - 1),)):
+                k = x.dense_mb2[3 * p + t]
+                kc = k.view(np.int64) >> 7
+                j = (_ARANGE - et) & (2 * N - 1)
+                comb += np.where(j >= N, -kc[..., j & (N - 1)], kc[..., j & (N - 1)]) - kc
+                pt = dense_product(k, d)
+                wrapping += np.stack([rot(pt[c], et) - pt[c] for c in range(2)])
+            found.append((dense_product_true(comb.view(U), d, 0), wrapping))
+        ref.products_mb2.append(found)
+    ref.acc, ref.acc_mb2 = np.stack(acc), np.stack(acc_mb2)
+    ref.out = np.stack([sample_extract(a) for a in ref.acc])
+    ref.out_mb2 = np.stack([sample_extract(a) for a in ref.acc_mb2])
+    for a in (ref.acc, ref.acc_mb2, ref.out, ref.out_mb2):
+        a.setflags(write=False)
+    return ref
+
+
+def true_magnitude(products):
+    """log2 of the largest |coefficient| over a row's dense products (grid units); -inf without one."""
+    import math
+    worst = max((abs(int(v)) for x_true, _ in products for v in x_true.ravel()), default=0)
+    return math.log2(worst) if worst else float("-inf")

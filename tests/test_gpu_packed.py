@@ -49,15 +49,17 @@ def _ascii(rng, n):
 
 
 def test_device_packing_equals_the_host_reference_in_every_word(ck):
-    """1, 512 and 513 characters.  The longer strings hold a folded constant (TRIV), the result of if_then_else in fused
-    mode (LIN: an unmaterialised sum of two bootstrap outputs per block; the packed download materialises it, as the
+    """1, 6, 300, 512 and 513 characters (6 and 300: 24 and 1200 blocks, a tree level at which some nodes have a live odd
+    child and others do not -- level 7 with 16 nodes, 8 of them, and the leaf level with 1024, 176 of them; 6 rather
+    than 3 or 5 characters because the loop body reads chars[4] and needs chars[3] != chars[n - 2]).  The longer strings
+    hold a folded constant (TRIV), the result of if_then_else in fused mode (LIN: an unmaterialised sum of two bootstrap outputs per block; the packed download materialises it, as the
     classic one would) and uploaded blocks (MAT)."""
     from fhestring_amd.api import FheString, pack_host, pack_switch16
     rng = np.random.default_rng(6)
     key = ck.packing_key()
     sk = _server(ck, 0)
     try:
-        for n in (1, 512, 513):
+        for n in (1, 512, 513, 6, 300):                 # the new sizes last: the texts of the first three stay
             text = _ascii(rng, n)
             s = sk.upload_string(ck.encrypt_str_raw(text, 0))
             chars = list(s.chars)

@@ -64,8 +64,9 @@ def _put_code(sk, chars):
 
 
 def test_device_entry_equals_the_host_reference_in_every_word(ck):
-    """1, 512 and 513 characters.  The longer strings hold a folded constant (TRIV), the result of if_then_else in fused
-    mode (LIN: put materialises it, as a download would) and uploaded blocks (MAT).  The exported entry is the host's
+    """1, 6, 300, 512 and 513 characters (6 and 300: 24 and 1200 blocks -- a packing-tree level with mixed liveness of the
+    odd children, and body quarters of 6 and 300 words, which end inside a workgroup of the switch).  The longer strings
+    hold a folded constant (TRIV), the result of if_then_else in fused mode (LIN: put materialises it, as a download would) and uploaded blocks (MAT).  The exported entry is the host's
     packing + switch of the classic download; what get() restores is the host expansion of those words, whole and for
     the windows (510, 3) -- blocks 2040-2051, across the group boundary --, (1, 1) -- first coefficient 4, inside a
     workgroup's eight -- and (512, 1)."""
@@ -74,7 +75,7 @@ def test_device_entry_equals_the_host_reference_in_every_word(ck):
     key = ck.packing_key()
     sk = _server(ck, 0)
     try:
-        for n in (1, 512, 513):
+        for n in (1, 512, 513, 6, 300):                 # the new sizes last: the texts of the first three stay
             text = _ascii(rng, n)
             s = sk.upload_string(ck.encrypt_str_raw(text, 0))
             chars = list(s.chars)

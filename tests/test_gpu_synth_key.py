@@ -1,7 +1,9 @@
 """The six blind-rotation kernels under the synthetic monomial keys of tests/synth_key.py, against integer numpy
 references that use no transform at all (anchored to the oracle's schoolbook product by tests/test_synth_key.py), on a
 row set whose look-up tables put exact decomposition ties into every product: the exact kernels bit for bit, the f64
-kernels bit for bit against their mirrors and within T3 / T4 of the integer reference on one-product rows."""
+kernels bit for bit against their mirrors and within T3 / T4 of the integer reference on one-product rows.  The same
+under keys with dense full-magnitude GGSWs, near the top of the exact kernels' CRT range.  And the keyswitch under a
+synthetic key that brings every byte plane of every key word to a modulus-switch edge, on every launch shape."""
 import numpy as np
 import pytest
 
@@ -27,10 +29,9 @@ def ref():
 @pytest.fixture(scope="module")
 def ctx(mat):
     import fhestring_amd
-    from oracle import core
     c = fhestring_amd.Context(0)
     c.set_arithmetic(c.ARITH_F64_FFT)                 # builds the Fourier-domain key beside the residues
-    c.load_server_key(mat.bsk, np.zeros(core.KSK_WORDS, np.uint64))     # the blind-rotation entry never keyswitches
+    c.load_server_key(mat.bsk, sk.keyswitch_material().ksk)             # the blind-rotation entry never keyswitches
     c.load_multibit_key(mat.bsk_mb2)
     c.set_arithmetic(c.ARITH_EXACT_NTT)
     c.load_multibit_key(mat.bsk_mb2)
@@ -124,5 +125,63 @@ def test_chosen_masks_and_edge_luts_under_the_real_dense_key(mat, oracle_keys, o
         for fft4_max in (0, 1 << 30):
             got, src = _run(c, c.ARITH_F64_FFT, ks, lut_idx, mat.luts, None, fft4_max)
             assert _bad(got, src, want3) == [], fft4_max
+    finally:
+        c.close()
+
+
+def test_keyswitch_under_the_synthetic_key_on_every_launch_shape(ctx):
+    """Every row of every width against the integer reference (== the oracle in all 64 bits, tests/test_synth_key.py).
+    On the edge rows all 743 outputs sit on a modulus-switch edge or one unit beside it, so one wrong unit in any byte
+    plane shows.  The widths are the smallest that reach each launch shape of launch_keyswitch_mfma on 256 CUs; on a
+    part where a width gets another shape it is left out rather than passed off as that shape."""
+    m = sk.keyswitch_material()
+    want = sk.mod_switch(sk.keyswitch_reference())
+    cus = ctx._L.fhs_resident_slots(ctx._h) // 2              # exact arithmetic: 2 workgroups per CU
+    widths = [w for w in sk.KS_WIDTHS if sk.ks_launch_shape(w, cus) == sk.KS_SHAPES_256[w]]
+    assert cus != 256 or widths == list(sk.KS_WIDTHS)
+    for width in widths:
+        src = sk.ks_batch(width)
+        got = ctx.keyswitch_modswitch_batch(m.cts[src])
+        bad = np.flatnonzero((got != want[src]).any(axis=1))
+        assert bad.size == 0, ("width", width, sk.KS_SHAPES_256[width], "first bad (batch row, distinct row, kind)",
+                               [(int(b), int(src[b]), m.kinds[src[b]]) for b in bad[:8]])
+
+
+def test_every_kernel_on_the_extreme_rows_near_the_top_of_the_crt_range():
+    """Keys with dense GGSWs of full-magnitude coefficients, constant look-up tables, digits of -2^22 in every
+    coefficient: product coefficients of 2^90 to 2^91 (classic) and 2^91 to 2^92 (two-bit) in grid units, against a CRT
+    range of 2^93.  The exact kernels against the integer references bit for bit, the f64 kernels against their mirrors
+    bit for bit and within T3X / T4X of the integer references on the rows that end in their one dense product."""
+    import fhestring_amd
+    from oracle import core
+    x, ref = sk.extreme_material(), sk.extreme_references()
+    osk = core.ServerKey(x.bsk, np.zeros(core.KSK_WORDS, np.uint64)).set_mb2(x.bsk_mb2)
+    want3, want4 = _mirror(osk, x.ms, x.luts, x.lut_idx, 3), _mirror(osk, x.ms, x.luts, x.lut_idx, 4)
+    c = fhestring_amd.Context(0)
+    try:
+        c.set_arithmetic(c.ARITH_F64_FFT)
+        c.load_server_key(x.bsk, np.zeros(core.KSK_WORDS, np.uint64))
+        c.load_multibit_key(x.bsk_mb2)
+        c.set_arithmetic(c.ARITH_EXACT_NTT)
+        c.load_multibit_key(x.bsk_mb2)
+        for n in (None, 300):
+            got, src = _run(c, c.ARITH_EXACT_NTT, x.ks, x.lut_idx, x.luts, n)
+            assert _bad(got, src, ref.out) == [], ("exact", n)
+            got, src = _run(c, c.ARITH_EXACT_NTT_MB2, x.ks, x.lut_idx, x.luts, n)
+            assert _bad(got, src, ref.out_mb2) == [], ("exact two-bit", n)
+            got, src = _run(c, c.ARITH_F64_FFT_MB2, x.ks, x.lut_idx, x.luts, n)
+            assert _bad(got, src, want4) == [], ("f64 two-bit", n)
+            worst = max(sk.centred_abs_max(got[r], ref.out_mb2[r]) for r in x.one_dense_mb2)
+            assert worst < sk.T4X, ("f64 two-bit", n, worst)
+        # 2 wavefronts; 4 wavefronts, wide-LDS variant; 4 wavefronts, shared-area variant (see the monomial-key item)
+        c.set_arithmetic(c.ARITH_F64_FFT)
+        slots = c._L.fhs_resident_slots(c._h)
+        c.set_arithmetic(c.ARITH_EXACT_NTT)
+        assert 4 * len(x.ks) <= slots
+        for fft4_max, n in ((0, None), (1 << 30, None), (1 << 30, max(300, slots // 4 + 1))):
+            got, src = _run(c, c.ARITH_F64_FFT, x.ks, x.lut_idx, x.luts, n, fft4_max)
+            assert _bad(got, src, want3) == [], ("f64", fft4_max, n)
+            worst = max(sk.centred_abs_max(got[r], ref.out[r]) for r in x.one_dense)
+            assert worst < sk.T3X, ("f64", fft4_max, n, worst)
     finally:
         c.close()
