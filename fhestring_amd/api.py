@@ -12,6 +12,7 @@ SMALL_CT = _K["FHS_SMALL_CT"]
 POLY_N = _K["FHS_POLY_N"]
 PACK_GROUP = _K["FHS_PACK_GROUP"]             # blocks per packed GLWE
 PACK_KEY_WORDS = _K["FHS_PACK_KEY_WORDS"]
+REKEY_KEY_WORDS = _K["FHS_REKEY_KEY_WORDS"]
 
 
 def _ptr(a):
@@ -122,6 +123,24 @@ class Context:
         key = np.ascontiguousarray(key, np.uint64)
         assert key.size == PACK_KEY_WORDS
         self._check(self._L.fhs_load_packing_key(self._h, _ptr(key)))
+
+    def load_rekey_key(self, key):
+        """fhs_load_rekey_key: the string store's keyswitch key to another client key, after load_server_key; None
+        unloads it."""
+        if key is not None:
+            key = np.ascontiguousarray(key, np.uint64)
+            assert key.size == REKEY_KEY_WORDS
+        self._check(self._L.fhs_load_rekey_key(self._h, None if key is None else _ptr(key)))
+
+    def rekey_device(self, mask32, body32, n_blocks):
+        """fhs_debug_rekey_device: the re-key kernel on raw words of any block count -> (mask32, body32), the arguments
+        and results of rekey_host."""
+        g = (n_blocks + PACK_GROUP - 1) // PACK_GROUP
+        mask32 = np.ascontiguousarray(mask32, np.uint32).reshape(g, POLY_N)
+        body32 = np.ascontiguousarray(body32, np.uint32).reshape(n_blocks)
+        m_out, b_out = np.zeros((g, POLY_N), np.uint32), np.zeros(n_blocks, np.uint32)
+        self._check(self._L.fhs_debug_rekey_device(self._h, _ptr(mask32), _ptr(body32), n_blocks, _ptr(m_out), _ptr(b_out)))
+        return m_out, b_out
 
     def pbs_batch(self, cts, lut_idx, luts):
         cts = np.ascontiguousarray(cts, np.uint64).reshape(-1, BIG_CT)
@@ -331,6 +350,19 @@ class MyClientKey:
         """fhs_client_save_packing_key: kind 5 key file; it travels beside a kind 1 / 2 / 4 file."""
         if self._L.fhs_client_save_packing_key(self._h, str(path).encode()) != 0:
             raise FhsError("cannot write packing key file %s" % path)
+
+    def rekey_key(self, to):
+        """fhs_client_rekey_key: the key that moves parked store entries of THIS client under the key of `to` (another
+        MyClientKey); a fresh key per call, [2][mask, body][2048] words."""
+        key = np.empty(REKEY_KEY_WORDS, np.uint64)
+        if self._L.fhs_client_rekey_key(self._h, to._h, _ptr(key)) != 0:
+            raise FhsError("fhs_client_rekey_key failed")
+        return key
+
+    def save_rekey_key(self, to, path):
+        """fhs_client_save_rekey_key: kind 7 key file with a fresh re-key key from this client to `to`."""
+        if self._L.fhs_client_save_rekey_key(self._h, to._h, str(path).encode()) != 0:
+            raise FhsError("cannot write re-key key file %s" % path)
 
     def encrypt_blocks_raw(self, values):
         """fhs_client_encrypt_blocks (diagnostic): one block per value mod 32, carry bits included: [n][2049]."""
@@ -767,7 +799,25 @@ def pack_switch32(mask64, body64, n_blocks):
     return CompactFheString(n_blocks // 4, mask32, body32) if n_blocks % 4 == 0 else (mask32, body32)
 
 
+def rekey_host(key, mask32, body32=None, n_blocks=None):
+    """fhs_rekey_host: host reference of the store's re-key.  rekey_host(key, compact) -> CompactFheString under the new
+    client key; rekey_host(key, mask32, body32, n_blocks) -> the raw (mask32, body32) of any block count."""
+    key = np.ascontiguousarray(key, np.uint64)
+    assert key.size == REKEY_KEY_WORDS
+    compact = mask32 if isinstance(mask32, CompactFheString) else None
+    if compact is not None:
+        mask32, body32, n_blocks = compact.mask32, compact.body32, 4 * len(compact)
+    g = (n_blocks + PACK_GROUP - 1) // PACK_GROUP
+    mask32 = np.ascontiguousarray(mask32, np.uint32).reshape(g, POLY_N)
+    body32 = np.ascontiguousarray(body32, np.uint32).reshape(n_blocks)
+    m_out, b_out = np.zeros((g, POLY_N), np.uint32), np.zeros(n_blocks, np.uint32)
+    if lib().fhs_rekey_host(_ptr(key), _ptr(mask32), _ptr(body32), n_blocks, _ptr(m_out), _ptr(b_out)) != 0:
+        raise FhsError("fhs_rekey_host failed")
+    return CompactFheString(n_blocks // 4, m_out, b_out) if compact is not None else (m_out, b_out)
+
+
 STORE_MAX_CYCLES = _K["FHS_STORE_MAX_CYCLES"]
+STORE_MAX_REKEYS = _K["FHS_STORE_MAX_REKEYS"]
 STORE_META_MAGIC = b"FHSSMET1"
 
 
@@ -826,6 +876,23 @@ class StoredString:
 
     def drop(self):
         self.sk.ctx._check(self.sk.ctx._L.fhs_store_drop(self.sk.ctx._h, self.id))
+
+    def rekey(self, copy=False):
+        """fhs_store_rekey with the context's re-key key (MyServerKey.load_rekey_key): in place -> self, or copy=True ->
+        a new StoredString under the other client's key while this one stays as it is."""
+        if not copy:
+            self.sk.ctx._check(self.sk.ctx._L.fhs_store_rekey(self.sk.ctx._h, self.id, None))
+            return self
+        eid = C.c_uint64(0)
+        self.sk.ctx._check(self.sk.ctx._L.fhs_store_rekey(self.sk.ctx._h, self.id, C.byref(eid)))
+        return StoredString(self.sk, eid.value)
+
+    @property
+    def rekeys(self):
+        """fhs_store_rekey_count: re-keys inside this entry's noise (0 after an import)."""
+        n = C.c_uint32(0)
+        self.sk.ctx._check(self.sk.ctx._L.fhs_store_rekey_count(self.sk.ctx._h, self.id, C.byref(n)))
+        return int(n.value)
 
     def export(self):
         """fhs_store_export -> (CompactFheString, meta[4n] u64); store_export_to_bytes serialises the pair."""
@@ -973,6 +1040,14 @@ class MyServerKey:
             self.ctx._check(self.ctx._L.fhs_load_packing_key_file(self.ctx._h, str(path).encode()))
         else:
             self.ctx.load_packing_key(key.packing_key() if isinstance(key, MyClientKey) else key)
+
+    def load_rekey_key(self, key=None, path=None):
+        """fhs_load_rekey_key (the words of MyClientKey.rekey_key(to)) / fhs_load_rekey_key_file (a kind 7 file): enables
+        StoredString.rekey.  Neither: unloads the key."""
+        if path is not None:
+            self.ctx._check(self.ctx._L.fhs_load_rekey_key_file(self.ctx._h, str(path).encode()))
+        else:
+            self.ctx.load_rekey_key(key)
 
     def download_packed(self, fhe_string, wide=False):
         """fhs_download_string_packed: the string ring-packed on the GPU, 16 bits per word -> PackedFheString.

@@ -281,6 +281,40 @@ int fhs_load_packing_key_file(fhs_ctx *c, const char *path) {
         return c->eng.ctx.fail(FHS_ERR_STATE, "cannot read packing key file (missing, truncated, not kind 5 or wrong parameters)");
     return fhs_load_packing_key(c, key.data());
 }
+// ---- string store: re-key ----
+int fhs_load_rekey_key(fhs_ctx *c, const uint64_t *key) {
+    if (!c) return FHS_ERR_ARG;
+    if (c->eng.planner) {                                    // a planner converts nothing: it notes whether a key is there
+        c->eng.planner_rekey_key = key != nullptr;
+        return FHS_OK;
+    }
+    return c->eng.ctx.load_rekey_key(key);
+}
+int fhs_load_rekey_key_file(fhs_ctx *c, const char *path) {
+    if (!c || !path) return FHS_ERR_ARG;
+    std::vector<uint64_t> key;
+    if (fhs_read_rekey_key_file(path, key) != FHS_OK)
+        return c->eng.ctx.fail(FHS_ERR_STATE, "cannot read re-key key file (missing, truncated, not kind 7 or wrong parameters)");
+    return fhs_load_rekey_key(c, key.data());
+}
+int fhs_store_rekey(fhs_ctx *c, uint64_t id, uint64_t *id_out) {
+    if (!c) return FHS_ERR_ARG;
+    if (id_out) *id_out = 0;
+    return c->eng.store_rekey(id, id_out);
+}
+int fhs_store_rekey_count(fhs_ctx *c, uint64_t id, uint32_t *n) {
+    if (!c || !n) return bad(c);
+    const Engine::StoreEntry *ent = c->eng.store_entry(id);
+    if (!ent) return c->eng.ctx.fail(FHS_ERR_ARG, "string store: unknown entry id");
+    *n = ent->rekeys;
+    return FHS_OK;
+}
+int fhs_debug_rekey_device(fhs_ctx *c, const void *mask32, const void *body32, size_t n_blocks, void *mask32_out,
+                           void *body32_out) {
+    if (!c || (n_blocks && (!mask32 || !body32 || !mask32_out || !body32_out)) || n_blocks > ((size_t)1 << 26)) return bad(c);
+    return c->eng.debug_rekey(static_cast<const uint32_t *>(mask32), static_cast<const uint32_t *>(body32), n_blocks,
+                              static_cast<uint32_t *>(mask32_out), static_cast<uint32_t *>(body32_out));
+}
 int fhs_export_device(fhs_ctx *c, fhs_char_t a, uint64_t *d_blocks) {
     if (!ok(c, a) || !d_blocks) return bad(c);
     const Bid *b = c->eng.char_blocks(a);

@@ -50,6 +50,7 @@ struct fhs_client {
     ChaKey pk_seed{};
     std::vector<uint64_t> pk_body;
     std::mutex pk_mu;
+    std::atomic<uint64_t> rekey_calls{0};   // re-key keys made INTO this client (fhs_client_rekey_key): one ChaCha key each
 };
 
 namespace {
@@ -581,6 +582,49 @@ int fhs_client_save_public_key(fhs_client *ck, const char *path) {
     if (!ck || !path) return FHS_ERR_ARG;
     if (!public_key(ck)) return FHS_ERR_STATE;
     return KeyFileWriter(path, 6).put(ck->pk_seed.w, 32).put(ck->pk_body.data(), POLY_N * 8).close();
+}
+
+}  // extern "C"
+
+// ---- string store: re-key keys (rekey_host.cpp, rekey_kernels.hip) ---------------------------------------------------
+namespace {
+
+// K[l] = (mask, body = mask (*) S_to + e + S_from 2^(64 - 16 (l + 1))) on the 58-bit grid.  Masks and noise come from a
+// ChaCha key of this call alone, streams l of DOM_MASK / DOM_NOISE: OS entropy, or for an insecure seeded `to` its seed,
+// the tag below and the number of keys made into it so far -- keys from different `from` clients into one `to` differ in
+// their randomness whatever the clients' own generator keys are.
+constexpr uint64_t SEED_TAG_REKEY = 0x5345454452454b31ull;
+bool rekey_key(fhs_client *from, fhs_client *to, uint64_t *out) {
+    ChaKey key;
+    if (!public_seed(to, SEED_TAG_REKEY, to->rekey_calls.fetch_add(1), key)) return false;
+    std::vector<uint64_t> prod(POLY_N);
+    for (int l = 0; l < FHS_REKEY_LEVELS; l++) {
+        Rng gm(key, l, DOM_MASK), e(key, l, DOM_NOISE);
+        uint64_t *mask = out + (size_t)l * 2 * POLY_N, *body = mask + POLY_N;
+        for (int n = 0; n < POLY_N; n++) mask[n] = gm.next() & GRID_MASK;
+        mul_binary(mask, to->glwe_sk.data(), prod.data());
+        for (int n = 0; n < POLY_N; n++)
+            body[n] = round_to_grid(prod[n] + e.noise(GLWE_NOISE) + (from->glwe_sk[n] << (64 - FHS_REKEY_BASE_LOG * (l + 1))),
+                                    BSK_QUANT_BITS);
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fhs_client_rekey_key(fhs_client *from, fhs_client *to, uint64_t *key_out) {
+    if (!from || !to || !key_out) return FHS_ERR_ARG;
+    return rekey_key(from, to, key_out) ? FHS_OK : FHS_ERR_STATE;
+}
+
+// kind 7: the re-key key alone
+int fhs_client_save_rekey_key(fhs_client *from, fhs_client *to, const char *path) {
+    if (!from || !to || !path) return FHS_ERR_ARG;
+    std::vector<uint64_t> k(FHS_REKEY_KEY_WORDS);
+    if (!rekey_key(from, to, k.data())) return FHS_ERR_STATE;
+    return KeyFileWriter(path, 7).put(k.data(), FHS_REKEY_KEY_WORDS * 8).close();
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 #include "context.h"
 #include "pack_kernels.h"
+#include "rekey_kernels.h"
 #include "seeded_kernels.h"
 #include "../../include/fhestring_hip.h"
 
@@ -163,8 +164,8 @@ int Context::load_compressed_server_key(const uint32_t seed[8], const uint64_t *
 int Context::install_server_key(const uint64_t *bsk, const uint64_t *d_ksk) {
     // what was derived from the previous server key, or generated with it, goes with it: the Fourier-domain key (rebuilt
     // below from the new standard-domain key if an f64-FFT arithmetic is selected, otherwise the first time one is), both
-    // pair keys and the packing key
-    for (DevBuf *b : {&d_bsk_fft, &d_bsk_mb, &d_bsk_ntt_mb, &d_pack_key_ntt}) b->release();
+    // pair keys, the packing key and the re-key key (one rule for auxiliary keys)
+    for (DevBuf *b : {&d_bsk_fft, &d_bsk_mb, &d_bsk_ntt_mb, &d_pack_key_ntt, &d_rekey_key_ntt}) b->release();
     const size_t bsk_ntt_doubles = (size_t)LWE_N * 4 * 2 * POLY_N;
     HIP_TRY(d_bsk_ntt.reserve_exact(bsk_ntt_doubles * sizeof(double)), "hipMalloc bsk");
     {   // the KSK is only kept as byte planes in MFMA fragment order (ks_kernels.hip)
@@ -320,6 +321,27 @@ int Context::load_packing_key(const uint64_t *key) {
     HIP_TRY(d_pack_key_ntt.reserve_exact(n_d * sizeof(double)), "hipMalloc packing key");
     HIP_TRY(hipMemcpy(d_pack_key_ntt.ptr, host.data(), n_d * sizeof(double), hipMemcpyHostToDevice), "copy packing key");
     HIP_TRY(prepare_device_for_packing(), "kernel attributes");
+    return 0;
+}
+
+// Re-key key of the string store: the same conversion as the packing key's.  It has nothing to do with the server key
+// but needs the twiddle tables its load uploads, and goes when the server key is replaced, like every auxiliary key.
+int Context::load_rekey_key(const uint64_t *key) {
+    HIP_TRY(hipSetDevice(device), "hipSetDevice");
+    if (!key) {
+        HIP_TRY(hipStreamSynchronize(stream), "stream sync");     // a queued re-key may still read it
+        d_rekey_key_ntt.release();
+        return 0;
+    }
+    if (!key_loaded) return fail(-3, "load the server key before the re-key key");
+    if (!ntt_slot_roots_are_bitreversed()) return fail(-3, "internal: NTT slot order is not bit-reversed");
+    const size_t n_d = REKEY_KEY_POLYS * 2 * POLY_N;
+    std::vector<double> host(n_d);
+    convert_polys_to_ntt(key, host.data(), REKEY_KEY_POLYS, BSK_QUANT_BITS);
+    HIP_TRY(hipStreamSynchronize(stream), "stream sync");
+    HIP_TRY(d_rekey_key_ntt.reserve_exact(n_d * sizeof(double)), "hipMalloc re-key key");
+    HIP_TRY(hipMemcpy(d_rekey_key_ntt.ptr, host.data(), n_d * sizeof(double), hipMemcpyHostToDevice), "copy re-key key");
+    HIP_TRY(prepare_device_for_rekey(), "kernel attributes");
     return 0;
 }
 

@@ -77,6 +77,10 @@ class Context {
     // packed result download (pack_kernels.hip): the 11 automorphism keyswitch keys as residues modulo the two NTT primes
     DevBuf d_pack_key_ntt;           // double: [11][3][2 cols][2 primes][2048]
     int load_packing_key(const uint64_t *key);   // [FHS_PACK_KEY_WORDS] u64 standard domain (fhs_client_packing_key)
+    // string-store re-key (rekey_kernels.hip): the GLWE keyswitch key S_old -> S_new as residues, an auxiliary key like the
+    // packing key (dropped by a server-key reload)
+    DevBuf d_rekey_key_ntt;          // double: [2][2 cols][2 primes][2048]
+    int load_rekey_key(const uint64_t *key);     // [FHS_REKEY_KEY_WORDS] u64 standard domain, or nullptr: unload
     int load_multibit_key(const uint64_t *bsk_mb2);   // [371][K1,K2,K3][4][2048] u64 standard domain (fhs_client_bsk_mb2)
     int fft4_max_batch = 512;                // batches up to this size use the 4-wavefront kernel (lower latency)
     size_t launch_chunk[N_ARITH] = {};       // per arithmetic: ciphertexts per blind-rotation launch (0 = whole batch)

@@ -168,6 +168,7 @@ class Engine {
         std::vector<uint16_t> var;        // BlockNode::var (1 for a trivial block: it comes back as an ordinary ciphertext)
         std::vector<uint8_t> cycles;      // packings inside the block's noise, this entry's included (0: imported fresh)
         std::vector<uint32_t> rot;        // BlockNode::rot, the engine's id verbatim
+        uint8_t rekeys = 0;               // re-keys inside the entry's noise (store_rekey); not exported, 0 after an import
         size_t groups() const { return (n_blocks + 2047) / 2048; }
         size_t bytes() const { return groups() * 2048 * 4 + n_blocks * 4; }
     };
@@ -185,6 +186,13 @@ class Engine {
     int store_export(uint64_t id, uint32_t *mask32, uint32_t *body32, uint64_t *meta);
     // one H2D copy, no kernel; meta == nullptr: every block a fresh upload (var 1, no group, no packing)
     int store_import(const uint32_t *mask32, const uint32_t *body32, const uint64_t *meta, size_t n_blocks, uint64_t *id_out);
+    // Re-keys an entry to another client key with the context's re-key key (rekey_kernels.hip): in place (id_out ==
+    // nullptr), or into a new entry that inherits var / cycles / rot and rekeys + 1.  A planner does the bookkeeping only.
+    static constexpr int STORE_MAX_REKEYS = 255;   // FHS_STORE_MAX_REKEYS
+    bool planner_rekey_key = false;                // planner only: fhs_load_rekey_key was given a key (nothing is converted)
+    int store_rekey(uint64_t id, uint64_t *id_out);
+    // diagnostic: the kernel on host words of any block count; the outputs may be the inputs
+    int debug_rekey(const uint32_t *mask32, const uint32_t *body32, size_t n_blocks, uint32_t *mask_out, uint32_t *body_out);
     // flushes if needed (do_flush = false: the caller has made sure the block's tick is enqueued); wait=false: enqueue only
     int copy_block_to_device(Bid b, uint64_t *d_out, bool wait = true, bool do_flush = true);
     uint64_t blocks_live() const { return pool_.live(); }
@@ -328,6 +336,9 @@ class Engine {
     // What read_packed and store_put share: flush, sums become blocks; then per pass of up to four groups the leaf table
     // and the 11 tree levels, which leave the pass's GLWEs [groups][2][2048] in ctx.pack_ws[0].
     int prepare_packing(const Bid *b, size_t count);
+    // one re-key launch over the groups of n_blocks blocks (device pointers, entry layout; out may be in), on the stream
+    hipError_t rekey_words(const uint32_t *d_mask, const uint32_t *d_body, uint32_t *d_mask_out, uint32_t *d_body_out,
+                           size_t n_blocks);
     hipError_t pack_tree_pass(const Bid *b, size_t n, size_t groups);
     std::map<uint64_t, StoreEntry> store_;
     uint64_t store_ids_ = 0;             // ids handed out: never reused inside a context

@@ -5,6 +5,7 @@
 #include "pack_kernels.h"
 #include "../../include/fhestring_hip.h"
 #include "pk_kernels.h"
+#include "rekey_kernels.h"
 #include "seeded_kernels.h"
 #include "store_kernels.h"
 
@@ -544,6 +545,70 @@ int Engine::store_import(const uint32_t *mask32, const uint32_t *body32, const u
     const uint64_t id = ++store_ids_;
     store_.emplace(id, std::move(ent));
     *id_out = id;
+    return 0;
+}
+
+// Re-key with the context's key: one launch over all groups on the context's stream, behind every queued expansion of
+// the entry.  In place the kernel reads and writes the entry's own allocation (rekey_kernels.hip says why that is safe);
+// a copy goes to a new entry of the same size and the original stays as it is.
+int Engine::store_rekey(uint64_t id, uint64_t *id_out) {
+    auto it = store_.find(id);
+    if (it == store_.end()) return ctx.fail(-1, "string store: unknown entry id");
+    StoreEntry &src = it->second;
+    if (!planner && !ctx.d_rekey_key_ntt) return ctx.fail(-3, "re-key key not loaded (fhs_load_rekey_key)");
+    if (src.rekeys >= STORE_MAX_REKEYS)
+        return ctx.fail(-4, "string store: the entry has been re-keyed FHS_STORE_MAX_REKEYS times");
+    StoreEntry copy;
+    if (id_out) {
+        copy.n_blocks = src.n_blocks;
+        copy.var = src.var; copy.cycles = src.cycles; copy.rot = src.rot;
+        copy.rekeys = src.rekeys;
+    }
+    StoreEntry &dst = id_out ? copy : src;
+    if (!planner) {
+        (void)hipSetDevice(ctx.device);
+        hipError_t e = id_out ? dst.buf.reserve_exact(dst.bytes()) : hipSuccess;
+        if (e == hipSuccess)
+            e = rekey_words(src.buf.as<uint32_t>(), src.buf.as<uint32_t>() + src.groups() * POLY_N, dst.buf.as<uint32_t>(),
+                            dst.buf.as<uint32_t>() + dst.groups() * POLY_N, src.n_blocks);
+        if (e != hipSuccess) return ctx.hip_fail(e, "string store: re-key");
+    }
+    dst.rekeys++;
+    if (id_out) {
+        const uint64_t nid = ++store_ids_;
+        store_.emplace(nid, std::move(copy));
+        *id_out = nid;
+    }
+    return 0;
+}
+
+hipError_t Engine::rekey_words(const uint32_t *d_mask, const uint32_t *d_body, uint32_t *d_mask_out, uint32_t *d_body_out,
+                               size_t n_blocks) {
+    RekeyParams p{};
+    p.src_mask = d_mask; p.src_body = d_body; p.dst_mask = d_mask_out; p.dst_body = d_body_out;
+    p.total = (uint32_t)n_blocks; p.groups = (int)((n_blocks + REKEY_GROUP - 1) / REKEY_GROUP);
+    p.key_ntt = ctx.d_rekey_key_ntt.as<double>(); p.tw = ctx.tw;
+    return launch_rekey_glwe(p, ctx.stream);
+}
+
+// Diagnostic: the kernel on raw host words of any block count, through a scratch allocation of the entry layout.
+int Engine::debug_rekey(const uint32_t *mask32, const uint32_t *body32, size_t n_blocks, uint32_t *mask_out, uint32_t *body_out) {
+    if (planner) return ctx.fail(-3, "planner context: nothing is computed");
+    if (!ctx.d_rekey_key_ntt) return ctx.fail(-3, "re-key key not loaded (fhs_load_rekey_key)");
+    if (n_blocks == 0) return 0;
+    (void)hipSetDevice(ctx.device);
+    const size_t mask_words = (n_blocks + REKEY_GROUP - 1) / REKEY_GROUP * POLY_N;
+    DevBuf buf;
+    hipError_t e = buf.reserve_exact((mask_words + n_blocks) * 4);
+    uint32_t *d_mask = buf.as<uint32_t>(), *d_body = d_mask + mask_words;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_mask, mask32, mask_words * 4, hipMemcpyHostToDevice, ctx.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_body, body32, n_blocks * 4, hipMemcpyHostToDevice, ctx.stream);
+    if (e == hipSuccess) e = rekey_words(d_mask, d_body, d_mask, d_body, n_blocks);
+    if (e == hipSuccess) e = hipMemcpyAsync(mask_out, d_mask, mask_words * 4, hipMemcpyDeviceToHost, ctx.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(body_out, d_body, n_blocks * 4, hipMemcpyDeviceToHost, ctx.stream);
+    hipError_t es = hipStreamSynchronize(ctx.stream);            // before buf goes, on every path
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return ctx.hip_fail(e, "re-key (diagnostic)");
     return 0;
 }
 

@@ -17,7 +17,7 @@ KeyFileHeader make_header(uint64_t kind) {
 }
 bool header_ok(const KeyFileHeader &h) {
     const KeyFileHeader w = make_header(h.kind);
-    return std::memcmp(&h, &w, sizeof(h)) == 0 && h.kind >= 1 && h.kind <= 6;
+    return std::memcmp(&h, &w, sizeof(h)) == 0 && h.kind >= 1 && h.kind <= 7;
 }
 
 KeyFileWriter::KeyFileWriter(const char *path, uint64_t kind) : f_(std::fopen(path, "wb")), ok_(f_ != nullptr) {
@@ -85,4 +85,7 @@ int fhs_read_packing_key_file(const char *path, std::vector<uint64_t> &key) {
 }
 int fhs_read_public_key_file(const char *path, uint32_t seed[8], std::vector<uint64_t> &body) {
     return KeyFileReader(path, {6}).get(seed, 32).get(body, POLY_N).finish(true);
+}
+int fhs_read_rekey_key_file(const char *path, std::vector<uint64_t> &key) {
+    return KeyFileReader(path, {7}).get(key, FHS_REKEY_KEY_WORDS).finish(true);
 }

@@ -1,7 +1,7 @@
 // Key files (include/fhestring_hip.h, "key files"): a 64-byte header that names the kind and the parameter set, then raw
-// little-endian arrays.  One writer and one reader for the six kinds:
+// little-endian arrays.  One writer and one reader for the seven kinds:
 //   1 client key (seed, both secret keys, bsk, ksk)   2 server key (bsk, ksk)   3 pair key   4 compressed server key
-//   5 packing key   6 public key
+//   5 packing key   6 public key   7 re-key key of the string store
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -18,7 +18,7 @@ struct KeyFileHeader {
 };
 static_assert(sizeof(KeyFileHeader) == 64, "header is 64 bytes");
 KeyFileHeader make_header(uint64_t kind);
-bool header_ok(const KeyFileHeader &h);   // magic, this build's parameters, kind 1..6
+bool header_ok(const KeyFileHeader &h);   // magic, this build's parameters, kind 1..7
 
 // Opens `path` and writes the header of `kind`; put() appends; close() is FHS_OK when every step succeeded, FHS_ERR_STATE
 // otherwise (the open included).  The file is closed on every path.
@@ -60,7 +60,7 @@ private:
 }  // namespace fhs
 
 // The readers behind the fhs_*_file entry points: FHS_OK or FHS_ERR_STATE (missing, truncated, another kind, other
-// parameters).  Kinds 3 to 6 must end where their arrays end; the readers of kinds 1 and 2 (this one and
+// parameters).  Kinds 3 to 7 must end where their arrays end; the readers of kinds 1 and 2 (this one and
 // fhs_client_load) accept trailing bytes.  That difference is as found, pinned by tests/test_client_kat.py, not a rule.
 int fhs_read_server_key_file(const char *path, std::vector<uint64_t> &bsk, std::vector<uint64_t> &ksk);   // kinds 1, 2
 int fhs_read_multibit_key_file(const char *path, std::vector<uint64_t> &mb);                               // kind 3
@@ -68,3 +68,4 @@ int fhs_read_compressed_server_key_file(const char *path, uint32_t seed[8], std:
                                         std::vector<uint64_t> &ksk_bodies);                                // kind 4
 int fhs_read_packing_key_file(const char *path, std::vector<uint64_t> &key);                               // kind 5
 int fhs_read_public_key_file(const char *path, uint32_t seed[8], std::vector<uint64_t> &body);             // kind 6
+int fhs_read_rekey_key_file(const char *path, std::vector<uint64_t> &key);                                 // kind 7

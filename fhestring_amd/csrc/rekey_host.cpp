@@ -1,0 +1,84 @@
+// Host reference of the string store's re-key (include/fhestring_hip.h, "re-keying parked entries"; DESIGN.md section
+// 14): one GLWE keyswitch per group of 2048 blocks in exact arithmetic over Z_2^64[X]/(X^2048+1) -- the AutoKS of
+// pack_host.cpp without the automorphism, two digits of 16 bits on words that have 32 significant bits.  Public data
+// only, no GPU: the comparator of rekey_kernels.hip and what CPU-only tests decrypt.
+#include <algorithm>
+#include <vector>
+
+#include "../../include/fhestring_hip.h"
+#include "host_ntt.h"
+#include "host_parallel.h"
+#include "pbs_kernels.h"
+
+namespace {
+
+using namespace fhs;
+constexpr int N = POLY_N;
+constexpr int L = FHS_REKEY_LEVELS;
+static_assert(L == 2 && FHS_REKEY_BASE_LOG == 16, "the digits below are the two 16-bit halves of a 32-bit word");
+
+inline uint32_t store32(uint64_t x) { return (uint32_t)((x + (1ull << 31)) >> 32); }
+
+// one group in place of (or next to) its source: mask[2048], body[count]; key_ntt: [L][mask, body][prime][2048]
+void rekey_group(const uint64_t *key_ntt, const uint32_t *mask, const uint32_t *body, size_t count, uint32_t *mask_out,
+                 uint32_t *body_out) {
+    std::vector<uint64_t> buf((size_t)(2 * L + 4) * N);
+    uint64_t *dig = buf.data() /* [prime][L] */, *acc = dig + (size_t)2 * L * N /* [col][prime] */;
+    for (int n = 0; n < N; n++) {
+        // mask << 32 = d[0] 2^48 + d[1] 2^32 exactly, digits in [-2^15, 2^15); the carry out of d[0] is a multiple of 2^64
+        const uint32_t a = mask[n], lo = a & 0xffff, c = lo >= 0x8000;
+        const int64_t d[L] = {(int16_t)(uint16_t)((a >> 16) + c), (int16_t)(uint16_t)lo};
+        for (int l = 0; l < L; l++)
+            for (int q = 0; q < 2; q++) dig[((size_t)q * L + l) * N + n] = to_residue(d[l], ntt_prime(q).p);
+    }
+    for (int q = 0; q < 2; q++) {
+        const NttPrime &pt = ntt_prime(q);
+        for (int l = 0; l < L; l++) ntt_forward(dig + ((size_t)q * L + l) * N, pt);
+        for (int c = 0; c < 2; c++) {
+            uint64_t *a = acc + ((size_t)c * 2 + q) * N;
+            for (int n = 0; n < N; n++) {
+                uint64_t s = 0;
+                for (int l = 0; l < L; l++)
+                    s += pt.mul(dig[((size_t)q * L + l) * N + n], key_ntt[((((size_t)l * 2 + c) * 2 + q) * N) + n]);
+                a[n] = s % pt.p;
+            }
+            ntt_inverse(a, pt);
+        }
+    }
+    // CRT to the centred integer, back to the torus: << 6 (the key was divided by 2^6), as pack_host.cpp
+    const NttPrime &p1 = ntt_prime(1);
+    static const uint64_t crt = p1.pow(NTT_P0 % NTT_P1, NTT_P1 - 2);   // p0^-1 mod p1
+    auto ks = [&](int c, size_t n) {
+        const uint64_t r0 = acc[((size_t)c * 2 + 0) * N + n], r1 = acc[((size_t)c * 2 + 1) * N + n];
+        const uint64_t r0m = r0 % NTT_P1;
+        const uint64_t k = p1.mul(r1 >= r0m ? r1 - r0m : r1 + NTT_P1 - r0m, crt);
+        const int64_t kc = k > NTT_P1 / 2 ? (int64_t)k - (int64_t)NTT_P1 : (int64_t)k;
+        return (r0 + NTT_P0 * (uint64_t)kc) << BSK_QUANT_BITS;
+    };
+    for (int n = 0; n < N; n++) mask_out[n] = store32((uint64_t)0 - ks(0, n));        // (every mask word was read above)
+    for (size_t j = 0; j < count; j++) body_out[j] = store32(((uint64_t)body[j] << 32) - ks(1, j));
+}
+
+}  // namespace
+
+extern "C" {
+
+int fhs_rekey_host(const uint64_t *key, const void *mask32_, const void *body32_, size_t n_blocks, void *mask32_out_,
+                   void *body32_out_) {
+    const uint32_t *mask32 = static_cast<const uint32_t *>(mask32_), *body32 = static_cast<const uint32_t *>(body32_);
+    uint32_t *mask_out = static_cast<uint32_t *>(mask32_out_), *body_out = static_cast<uint32_t *>(body32_out_);
+    if (!key || (n_blocks && (!mask32 || !body32 || !mask_out || !body_out))) return FHS_ERR_ARG;
+    // the key as residues: [L][mask, body][prime][2048], rounded to the 58-bit grid, 1/N folded in
+    std::vector<uint64_t> key_ntt((size_t)L * 2 * 2 * N);
+    for (size_t pi = 0; pi < (size_t)L * 2; pi++)
+        for (int q = 0; q < 2; q++) torus_poly_to_ntt(key + pi * N, BSK_QUANT_BITS, ntt_prime(q), key_ntt.data() + (pi * 2 + q) * N);
+    const size_t groups = (n_blocks + FHS_PACK_GROUP - 1) / FHS_PACK_GROUP;
+    parallel_for(groups, host_threads(16), 1, [&](size_t g) {          // groups are independent, in place too
+        const size_t count = std::min<size_t>(FHS_PACK_GROUP, n_blocks - g * FHS_PACK_GROUP);
+        rekey_group(key_ntt.data(), mask32 + g * N, body32 + g * FHS_PACK_GROUP, count, mask_out + g * N,
+                    body_out + g * FHS_PACK_GROUP);
+    });
+    return FHS_OK;
+}
+
+}  // extern "C"

@@ -468,7 +468,7 @@ int fhs_client_secret_keys(const fhs_client *ck, uint64_t *lwe_sk /*[742]*/, uin
  * server_key/mod.rs:13 but never calls them).  Little-endian: 64-byte header {magic "FHSKEY01", kind,
  * lwe_n, poly_n, ks_levels, ks_base_log, pbs_base_log, bsk_quant_bits}, then raw u64 arrays.
  * kind 1 = client key (secret keys + server key), kind 2 = server key only (bsk, ksk), kind 4 = compressed server key,
- * kind 5 = packing key, kind 6 = public key (all three below). */
+ * kind 5 = packing key, kind 6 = public key, kind 7 = re-key key of the string store (all four below). */
 int fhs_client_save(const fhs_client *ck, const char *path, int server_key_only);
 int fhs_client_load(const char *path, fhs_client **out);             /* kind 1 files only */
 int fhs_load_server_key_file(fhs_ctx *ctx, const char *path);        /* kind 1 or 2 */
@@ -686,6 +686,63 @@ int fhs_store_import(fhs_ctx *ctx, const void *mask32, const void *body32, const
 /* Host reference of the store's storage switch, next to fhs_pack_switch16: every word -> (x + 2^31) >> 32;
  * mask32[groups][2048], body32[n_blocks]. */
 int fhs_pack_switch32(const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, void *mask32, void *body32);
+
+/* ---- string store: re-keying parked entries to another client key -------------------------------------------
+ * An entry is a plain GLWE ciphertext under its client's GLWE key S_old, 32 bits per word.  One GLWE keyswitch per group
+ * of 2048 blocks -- the AutoKS of the packing tree without the automorphism -- moves it under the key S_new of another
+ * client (a key rotation, or handing a parked string to a second client) without the secret-key holder touching the
+ * data: exact arithmetic in R = Z_2^64[X]/(X^2048 + 1), a 64 KB key, no bootstrap, no pool blocks.
+ * The RE-KEY KEY from S_old to S_new has FHS_REKEY_LEVELS digit levels of FHS_REKEY_BASE_LOG bits:
+ *   key[l] = (mask[2048], body[2048]),  body = mask * S_new + noise + S_old * 2^(64 - FHS_REKEY_BASE_LOG (l + 1)),
+ * on the bootstrapping key's 58-bit grid with the GLWE noise.  Per group (mask32[2048], body32[count]):
+ *   A = mask32 << 32 = d_0 2^48 + d_1 2^32 with balanced digits in [-2^15, 2^15) (a stored mask word has exactly 32
+ *   significant bits: no rounding; a carry out of d_0 is a multiple of 2^64),  Sum_col = sum_l d_l * key[l].col,
+ *   mask' = -Sum_mask,  body'_j = (body32_j << 32) - Sum_body,j for j < count;  every word stored as (x + 2^31) >> 32.
+ * The result is an entry in the same format under S_new: fhs_store_get / fhs_expand_public_str take it unchanged.
+ * Noise: the keyswitch adds sigma 2^32.6 and the second 32-bit rounding 2^35.2, 2^-15 of the packing variance, so a
+ * re-key changes neither the figure, nor the rotation group, nor `cycles` of a block; it is counted per entry, on the
+ * host, and the re-key after the FHS_STORE_MAX_REKEYS-th of one entry is refused with FHS_ERR_LIMIT.  export / import do
+ * not carry the counter (the meta word keeps its layout, bits 24-31 stay zero): an IMPORTED entry starts at 0 again.
+ * A context CANNOT TELL which client key an entry is under: re-keying an entry with a key that starts from another
+ * client's S, re-keying it twice, or mixing entries of two clients in one operation gives garbage without any error.
+ * Keeping track is the caller's business.
+ * Randomness of a re-key key: its masks and noise come from a ChaCha20 key drawn from getrandom(2) for that call alone
+ * (streams l, domains 2 = masks / 3 = noise of that key), like the encryptor of fhs_public_encrypt_str: two keys into
+ * the same `to`, from whatever `from`, never share a mask or noise (their difference would show (S_a - S_b) 2^k in the
+ * clear).  When `to` is an insecure seeded client the ChaCha key is derived from `to`'s 64-bit seed, a tag of its own and
+ * the number of re-key keys `to` has received so far (tests only). */
+#define FHS_REKEY_BASE_LOG 16
+#define FHS_REKEY_LEVELS 2
+#define FHS_REKEY_KEY_WORDS ((size_t)2 * 2 * 2048)           /* [FHS_REKEY_LEVELS][mask, body][2048] */
+#define FHS_REKEY_KEY_FILE_BYTES ((size_t)64 + 2 * 2 * 2048 * 8)   /* kind 7 key file */
+#define FHS_STORE_MAX_REKEYS 255
+/* The key that moves entries of `from` under the key of `to`.  Both secret keys are needed: the two clients are one
+ * party, or `from` hands its client key to `to`.  A fresh key per call. */
+int fhs_client_rekey_key(fhs_client *from, fhs_client *to, uint64_t *key_out /*[FHS_REKEY_KEY_WORDS]*/);
+/* kind 7 key file: header + a fresh re-key key.  Every other loader refuses it. */
+int fhs_client_save_rekey_key(fhs_client *from, fhs_client *to, const char *path);
+/* The key is independent of the server key but needs its transform tables, so it is loaded after fhs_load_server_key and
+ * dropped by a server-key reload exactly as the packing key is: one rule for auxiliary keys.  key == NULL unloads it.
+ * A planner context records that a key is present and converts nothing. */
+int fhs_load_rekey_key(fhs_ctx *ctx, const uint64_t *key /*[FHS_REKEY_KEY_WORDS], or NULL*/);
+int fhs_load_rekey_key_file(fhs_ctx *ctx, const char *path);     /* kind 7 only */
+/* Re-keys entry `id` with the loaded key: one kernel launch over all its groups on the context's stream, behind every
+ * queued fhs_store_get.  id_out == NULL: in place -- id, size and allocation stay.  Otherwise a NEW entry in a new
+ * allocation of its exact size receives the result (*id_out) and the original is untouched: the copy for a second
+ * client.  It inherits figure / cycles / rotation groups verbatim and the original's re-key count + 1.
+ * FHS_ERR_ARG: unknown id.  FHS_ERR_STATE: no re-key key on a device context.  FHS_ERR_LIMIT: see above.  A planner
+ * context does the bookkeeping only and needs no key. */
+int fhs_store_rekey(fhs_ctx *ctx, uint64_t id, uint64_t *id_out /*may be NULL*/);
+int fhs_store_rekey_count(fhs_ctx *ctx, uint64_t id, uint32_t *n);
+/* Host reference (public data only, no GPU): the same words as the device.  mask32 / body32 as in fhs_store_export
+ * (uint32_t arrays sized for n_blocks blocks: ceil(n_blocks / 2048) x 2048 mask words, n_blocks bodies); the output
+ * arrays may be the input arrays. */
+int fhs_rekey_host(const uint64_t *key, const void *mask32, const void *body32, size_t n_blocks, void *mask32_out,
+                   void *body32_out);
+/* Diagnostic: the device kernel on raw words of ANY block count (an entry holds whole characters, 4 blocks each), same
+ * arguments and aliasing rule as fhs_rekey_host.  FHS_ERR_STATE without a re-key key or on a planner context. */
+int fhs_debug_rekey_device(fhs_ctx *ctx, const void *mask32, const void *body32, size_t n_blocks, void *mask32_out,
+                           void *body32_out);
 
 #ifdef __cplusplus
 }

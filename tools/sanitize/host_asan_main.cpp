@@ -71,6 +71,20 @@ int main() {
         char pbuf[16];
         size_t pn = 0;
         CHECK(fhs_client_decrypt_str(ck, win.data(), 10, pbuf, &pn) == FHS_OK && pn == 8 && !std::memcmp(pbuf, "ssssssss", 8));
+        {   // that compact string re-keyed to a second client, in place (rekey_host.cpp); the re-key key and its kind 7 file
+            fhs_client *to = nullptr;
+            CHECK(fhs_client_create_insecure_seeded(43, &to) == FHS_OK);
+            std::vector<uint64_t> rk(FHS_REKEY_KEY_WORDS), rk2;
+            CHECK(fhs_client_rekey_key(ck, to, rk.data()) == FHS_OK && fhs_client_rekey_key(ck, nullptr, rk.data()) == FHS_ERR_ARG);
+            CHECK(fhs_rekey_host(rk.data(), m32.data(), b32.data(), bw, m32.data(), b32.data()) == FHS_OK);
+            CHECK(fhs_expand_public_str(m32.data(), b32.data(), 517, 507, 10, win.data()) == FHS_OK);
+            CHECK(fhs_client_decrypt_str(to, win.data(), 10, pbuf, &pn) == FHS_OK && pn == 8 && !std::memcmp(pbuf, "ssssssss", 8));
+            CHECK(fhs_client_save_rekey_key(ck, to, pub.c_str()) == FHS_OK && fhs_read_rekey_key_file(pub.c_str(), rk2) == FHS_OK &&
+                  rk2.size() == FHS_REKEY_KEY_WORDS);
+            CHECK(fhs_read_packing_key_file(pub.c_str(), rk2) == FHS_ERR_STATE);                     // kind 7
+            std::remove(pub.c_str());
+            fhs_client_destroy(to);
+        }
         fhs_public_key_destroy(pk);
         fhs_public_key_destroy(pk2);
     }
@@ -234,6 +248,17 @@ int main() {
         CHECK(fhs_flush(c) == FHS_OK);
         uint64_t blocks[FHS_CHAR_WORDS];
         CHECK(fhs_download(c, r, blocks) == FHS_ERR_STATE);      // a planner computes nothing
+    }
+    {   // string store on the planner: put, re-key in place and as a copy (bookkeeping only), get
+        auto s = dummy(c, 3);
+        uint64_t id = 0, id2 = 0, none = 7;
+        uint32_t nk = 9;
+        std::vector<fhs_char_t> back(3);
+        CHECK(fhs_store_put(c, s.data(), s.size(), &id) == FHS_OK && fhs_store_rekey(c, id, nullptr) == FHS_OK);
+        CHECK(fhs_store_rekey(c, id, &id2) == FHS_OK && id2 != 0 && id2 != id && fhs_store_rekey(c, id + 100, &none) == FHS_ERR_ARG && none == 0);
+        CHECK(fhs_store_rekey_count(c, id, &nk) == FHS_OK && nk == 1);
+        CHECK(fhs_store_get(c, id2, 0, 3, back.data()) == FHS_OK && fhs_store_drop(c, id) == FHS_OK && fhs_store_drop(c, id2) == FHS_OK);
+        CHECK(fhs_load_rekey_key(c, nullptr) == FHS_OK && fhs_load_rekey_key_file(c, "/nonexistent-directory/key.bin") == FHS_ERR_STATE);
     }
     {   // level-skewed batching: jobs on ticks, dependent jobs, handles released while their levels are still scheduled
         CHECK(fhs_set_mode(c, 1) == FHS_OK);
