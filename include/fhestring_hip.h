@@ -209,6 +209,13 @@ int fhs_export_device(fhs_ctx *ctx, fhs_char_t a, uint64_t *d_blocks /*[4][2049]
  * under torch.cuda.ExternalStream) after the export and before a following fhs_import_device. */
 int fhs_export_device_async(fhs_ctx *ctx, fhs_char_t a, uint64_t *d_blocks /*[4][2049] device*/);
 void *fhs_stream_handle(fhs_ctx *ctx);
+/* One char from device memory, d_blocks[4][2049] in the layout of fhs_export_device; the handle enters the noise
+ * bookkeeping at figure 1 like an upload (fhs_char_set_noise declares more).  The four copies are only ENQUEUED on the
+ * context's stream (fhs_stream_handle) when the call returns:
+ *  - the source must be complete before the call: the caller orders its producer in front of the copy, e.g. records an
+ *    event behind the producer and makes the stream of fhs_stream_handle wait on it, or waits on the host;
+ *  - the source must stay unchanged until that stream has passed the copy: after fhs_stream_sync (or any call that
+ *    waits for the stream, such as a download of the handle), or behind an event recorded on that stream after the call. */
 fhs_char_t fhs_import_device(fhs_ctx *ctx, const uint64_t *d_blocks);
 
 /* ---- MyServerKey string methods (src/server_key/mod.rs, trim.rs) --------------

@@ -380,3 +380,66 @@ def test_c_host_builds_as_c99_and_fails_loudly_without_a_gpu():
         assert out.returncode == 0, out.stdout + out.stderr
     else:
         assert out.returncode == 2 and "no CPU fallback" in out.stderr and "Test Passed" not in out.stdout
+
+
+def test_device_pointer_entries_refuse_on_the_host():
+    """fhs_export_device(_async), fhs_import_device and fhs_stream_handle where the library answers before it touches a
+    GPU: a planner context computes nothing and exports nothing; null pointers and released handles are argument errors.
+    (What the entries do with valid device pointers is tests/test_gpu_device_boundary.py.)"""
+    import ctypes as C
+    from fhestring_amd.api import MyServerKey
+    FHS_ERR_ARG, FHS_ERR_STATE = -1, -3
+    sk = MyServerKey.planner()
+    try:
+        L, h = sk.ctx._L, sk.ctx._h
+        last = lambda: L.fhs_last_error(h).decode()
+        room = np.zeros(4 * 2049, np.uint64)                  # a valid destination, should an entry ever write
+        dst = room.ctypes.data_as(C.c_void_p)
+        t = sk.trivial(0x41)
+        for entry in (L.fhs_export_device, L.fhs_export_device_async):
+            assert entry(h, t.h, dst) == FHS_ERR_STATE and "planner context" in last()
+            assert entry(h, t.h, None) == FHS_ERR_ARG and "null argument" in last()
+            assert entry(h, 0, dst) == FHS_ERR_ARG
+            assert entry(None, t.h, dst) == FHS_ERR_ARG
+        assert not room.any()
+        gone = sk.trivial(0x42)
+        released, gone.h = gone.h, 0                          # (the Python object must not release it a second time)
+        assert L.fhs_release(h, released) == 0
+        for entry in (L.fhs_export_device, L.fhs_export_device_async):
+            assert entry(h, released, dst) == FHS_ERR_ARG and "invalid handle" in last()
+        assert L.fhs_import_device(h, None) == 0 and "null argument" in last()
+        assert L.fhs_import_device(None, dst) == 0
+        assert L.fhs_stream_handle(None) is None
+        assert L.fhs_stream_handle(h) is None                 # a planner has no stream
+    finally:
+        sk.close()
+
+
+def test_import_device_on_a_planner_context_books_a_block_and_copies_nothing():
+    """Pinned as it is today: on a planner fhs_import_device is an upload for the bookkeeping -- four fresh blocks at
+    figure 1, usable as operands -- and the source is never read."""
+    import ctypes as C
+    from fhestring_amd import FhsError
+    from fhestring_amd.api import FheAsciiChar, MyServerKey
+    from test_gpu_packed import _kinds                        # block kinds through fhs_debug_char_terms; needs no GPU
+    sk = MyServerKey.planner()
+    try:
+        src = np.full(4 * 2049, 0xA5A5A5A5A5A5A5A5, np.uint64)
+        before = sk.stats()["blocks_live"]
+        ch = FheAsciiChar(sk, sk.ctx._L.fhs_import_device(sk.ctx._h, src.ctypes.data_as(C.c_void_p)))
+        assert sk.stats()["blocks_live"] == before + 4
+        assert ch.sum_c2() == 1 and _kinds(sk, ch) == [1] * 4 and ch.trivial_value() is None
+        assert ch.set_noise(3).sum_c2() == 3
+        with pytest.raises(FhsError) as e:
+            ch.set_noise(0)
+        assert e.value.code == -1 and ch.sum_c2() == 3
+        sk.set_mode(0)
+        r = ch.bitand(sk.upload_char(np.zeros((4, 2049), np.uint64)))
+        sk.flush()
+        assert sk.stats()["pbs_executed"] == 4 and r.sum_c2() == 1
+        with pytest.raises(FhsError, match="planner context") as e:
+            ch.download()
+        assert e.value.code == -3
+        assert (src == 0xA5A5A5A5A5A5A5A5).all()
+    finally:
+        sk.close()
