@@ -208,6 +208,8 @@ class Context:
 CHAR_WORDS = _K["FHS_CHAR_WORDS"]
 MAX_FIND_LENGTH = _K["FHS_MAX_FIND_LENGTH"]
 MAX_REPETITIONS = _K["FHS_MAX_REPETITIONS"]
+MAX_FIND_LENGTH_WIDE = _K["FHS_MAX_FIND_LENGTH_WIDE"]
+WIDE_ABSENT = _K["FHS_WIDE_ABSENT"]
 STRING_PADDING = 1
 MODE_AS_WRITTEN = _K["FHS_MODE_AS_WRITTEN"]
 MODE_FUSED = _K["FHS_MODE_FUSED"]
@@ -433,6 +435,10 @@ class MyClientKey:
     def decrypt(self, fhe_string):                                                 # :89-106
         return self.decrypt_str_raw(fhe_string.download())
 
+    def decrypt_u16(self, wide):
+        """The integer of an FheU16 (find_wide, rfind_wide, len_wide, count_flags_wide)."""
+        return self.decrypt_char(wide.lo) + 256 * self.decrypt_char(wide.hi)
+
 
 class FheAsciiChar:
     """Handle of one lazily evaluated encrypted char (fheasciichar.rs:8-10)."""
@@ -506,6 +512,20 @@ class FheAsciiChar:
         self.sk.flush()                      # (collective in level-parallel mode)
         self.sk.ctx._check(self.sk.ctx._L.fhs_download(self.sk.ctx._h, self.h, _ptr(out)))
         return out
+
+
+class FheU16:
+    """A 16-bit unsigned result as two ordinary chars: value = lo + 256 * hi (the _wide entry points of the C ABI)."""
+    __slots__ = ("lo", "hi")
+
+    def __init__(self, lo, hi):
+        self.lo = lo
+        self.hi = hi
+
+    def trivial_value(self):
+        """The integer if both halves folded to constants, else None."""
+        lo, hi = self.lo.trivial_value(), self.hi.trivial_value()
+        return None if lo is None or hi is None else lo + 256 * hi
 
 
 class FheString:
@@ -1278,6 +1298,36 @@ class MyServerKey:
         out = C.c_uint64()
         self.ctx._check(self.ctx._L.fhs_str_len(self.ctx._h, _harr(s), len(s), C.byref(out)))
         return FheAsciiChar(self, out.value)
+
+    # ---- 16-bit positions and counts (the reference's are u8: src/main.rs:20) ----
+    def _wide(self, name, *args):
+        lo, hi = C.c_uint64(), C.c_uint64()
+        rc = getattr(self.ctx._L, name)(self.ctx._h, *args, C.byref(lo), C.byref(hi))
+        if rc == -4:
+            raise OverflowError(self.ctx._L.fhs_last_error(self.ctx._h).decode())
+        self.ctx._check(rc)
+        return FheU16(FheAsciiChar(self, lo.value), FheAsciiChar(self, hi.value))
+
+    def find_wide(self, string, pattern):                                # mod.rs:1010, absent = WIDE_ABSENT
+        s, pat = self._chars(string), self._chars(pattern)
+        return self._wide("fhs_str_find_wide", _harr(s), len(s), _harr(pat), len(pat))
+
+    def find_clear_wide(self, string, clear_pattern):                    # mod.rs:1075
+        s, data = self._chars(string), clear_pattern.encode("ascii")
+        return self._wide("fhs_str_find_clear_wide", _harr(s), len(s), data, len(data))
+
+    def rfind_wide(self, string, pattern):                               # mod.rs:727
+        s, pat = self._chars(string), self._chars(pattern)
+        return self._wide("fhs_str_rfind_wide", _harr(s), len(s), _harr(pat), len(pat))
+
+    def len_wide(self, string):                                          # mod.rs:478, no wrap at 256
+        s = self._chars(string)
+        return self._wide("fhs_str_len_wide", _harr(s), len(s))
+
+    def count_flags_wide(self, flags):
+        """The number of set flags among 0/1 flag chars (fhs_flags_count_wide)."""
+        f = self._chars(flags)
+        return self._wide("fhs_flags_count_wide", _harr(f), len(f))
 
     def eq(self, string, other, public_parameters=None):                 # mod.rs:1122
         return self._flag_op("eq", string, other)

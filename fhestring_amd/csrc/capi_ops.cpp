@@ -389,6 +389,58 @@ int fhs_str_len(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t *out) {
     *out = store(c->eng, r);
     return FHS_OK;
 }
+// ---- wide positions and counts: (lo, hi) chars, value lo + 256 hi ----
+namespace {
+int store_wide(fhs_ctx *c, Strings &S, FWide &r, fhs_char_t *lo, fhs_char_t *hi) {
+    if (int rc = finish(c, S)) return rc;
+    *lo = store(c->eng, r.lo);
+    *hi = store(c->eng, r.hi);
+    return FHS_OK;
+}
+// the limit is tested before the operands are loaded: loading refreshes noisy operands, which records bootstraps
+int wide_limit(fhs_ctx *c, size_t n, size_t m) {
+    if (!Strings::wide_limit_reached(n, m)) return FHS_OK;
+    return c->eng.ctx.fail(FHS_ERR_LIMIT, "Maximum supported size for find reached");
+}
+}  // namespace
+
+int fhs_str_find_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const fhs_char_t *pat, size_t m, fhs_char_t *lo,
+                      fhs_char_t *hi) {                      // mod.rs:1010-1053 with the u8 of :1023-1027, :1044 widened
+    if (!ok_all(c, s, n) || !ok_all(c, pat, m) || !lo || !hi) return bad(c);
+    if (int rc = wide_limit(c, n, m)) return rc;
+    Strings S(&c->eng);
+    FWide r = S.find_wide(load_str(c->eng, s, n), load_str(c->eng, pat, m));
+    return store_wide(c, S, r, lo, hi);
+}
+int fhs_str_find_clear_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, fhs_char_t *lo,
+                            fhs_char_t *hi) {                // mod.rs:1075, the same
+    if (!ok_all(c, s, n) || (m && !pat) || !lo || !hi) return bad(c);
+    if (int rc = wide_limit(c, n, m)) return rc;
+    Strings S(&c->eng);
+    FWide r = S.find_wide(load_str(c->eng, s, n), S.clear(pat, m));
+    return store_wide(c, S, r, lo, hi);
+}
+int fhs_str_rfind_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const fhs_char_t *pat, size_t m, fhs_char_t *lo,
+                       fhs_char_t *hi) {                     // mod.rs:727-790 with the u8 of :739-744, :753, :783 widened
+    if (!ok_all(c, s, n) || !ok_all(c, pat, m) || !lo || !hi) return bad(c);
+    if (int rc = wide_limit(c, n + 1, m)) return rc;        // the NUL pushed at :737 counts
+    Strings S(&c->eng);
+    FWide r = S.rfind_wide(load_str(c->eng, s, n), load_str(c->eng, pat, m));
+    return store_wide(c, S, r, lo, hi);
+}
+int fhs_str_len_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t *lo, fhs_char_t *hi) {   // mod.rs:478-493, no wrap
+    if (!ok_all(c, s, n) || !lo || !hi) return bad(c);
+    Strings S(&c->eng);
+    FWide r = S.len_wide(load_str(c->eng, s, n));
+    return store_wide(c, S, r, lo, hi);
+}
+int fhs_flags_count_wide(fhs_ctx *c, const fhs_char_t *flags, size_t n, fhs_char_t *lo, fhs_char_t *hi) {
+    if (!ok_all(c, flags, n) || !lo || !hi) return bad(c);
+    Strings S(&c->eng);
+    FWide r = S.count_flags_wide(load_str(c->eng, flags, n));
+    return store_wide(c, S, r, lo, hi);
+}
+
 int fhs_str_compare(fhs_ctx *c, const fhs_char_t *a, size_t na, const fhs_char_t *b, size_t nb, int cmp, fhs_char_t *out) {
     if (!ok_all(c, a, na) || !ok_all(c, b, nb) || !out || cmp < 0 || cmp > 3) return bad(c);
     Strings S(&c->eng);

@@ -282,6 +282,101 @@ FChar Strings::find(const FStr &s, const FStr &pat) {        // mod.rs:1010-1053
     return pos;
 }
 
+// ---------------------------------------------------------------------------------------------
+// wide positions and counts: the loops above with the u8 position / counter as two chars (lo, hi), value lo + 256 hi.
+// The reference stops at 255 (src/main.rs:20, mod.rs:742-744, :1025-1027, :1044); everything else is kept, quirks included.
+// ---------------------------------------------------------------------------------------------
+bool Strings::wide_limit_reached(size_t n, size_t m) { return n >= (size_t)FHS_MAX_FIND_LENGTH_WIDE + m; }
+
+FWide Strings::wide_trivial(unsigned v) const { return {t((uint8_t)(v & 255)), t((uint8_t)((v >> 8) & 255))}; }
+
+FChar Strings::num_char(const Num &v, size_t first) {
+    FChar c;
+    for (int k = 0; k < 4; k++) c.b[k] = v[first + k];
+    return c;
+}
+FWide Strings::num_wide(const Num &v) { return {num_char(v, 0), num_char(v, 4)}; }
+
+void Strings::wide_add_flag(FWide &counter, const FChar &flag) {
+    FChar lo = ch_add(counter.lo, flag);
+    counter.hi = ch_add(counter.hi, ch_lt(lo, counter.lo));  // the low char wrapped: carry
+    counter.lo = lo;
+}
+
+FWide Strings::find_wide(const FStr &s, const FStr &pat) {   // mod.rs:1010-1053 with a 16-bit position
+    if (s.empty() && pat.empty()) return wide_trivial(0);
+    if (wide_limit_reached(s.size(), pat.size())) {          // :1025-1027
+        err = {FHS_ERR_LIMIT, "Maximum supported size for find reached"};
+        return wide_trivial(0);
+    }
+    if (pat.size() > s.size()) return wide_trivial(FHS_WIDE_ABSENT);
+    if (fused()) return num_wide(f_find_digits(f_find_window_flags(s, pat), 8));
+    const FChar one = t(1);
+    FWide pos = wide_trivial(FHS_WIDE_ABSENT);
+    for (size_t i = s.size() - pat.size() + 1; i-- > 0;) {
+        FChar flag = one;
+        for (size_t j = pat.size(); j-- > 0;) flag = ch_bitand(flag, ch_eq(pat[j], s[i + j]));
+        pos.lo = ch_ite(flag, t((uint8_t)(i & 255)), pos.lo);
+        pos.hi = ch_ite(flag, t((uint8_t)(i >> 8)), pos.hi);
+    }
+    return pos;
+}
+
+FWide Strings::rfind_wide(const FStr &s_in, const FStr &pat) {   // mod.rs:727-790 with a 16-bit position
+    const FChar one = t(1), zero = t(0);
+    FStr s = s_in;
+    s.push_back(zero);                                       // :737
+    if (wide_limit_reached(s.size(), pat.size())) {          // :742-744
+        err = {FHS_ERR_LIMIT, "Maximum supported size for find reached"};
+        return wide_trivial(0);
+    }
+    if (fused()) return num_wide(f_rfind_digits(s, pat, 8));
+    if (pat.empty()) {                                       // :747-760
+        FWide last = wide_trivial(0);
+        for (size_t i = 0; i < s.size(); i++) {
+            FChar nz = ch_ne(s[i], zero);
+            last.lo = ch_ite(nz, t((uint8_t)((i + 1) & 255)), last.lo);
+            last.hi = ch_ite(nz, t((uint8_t)((i + 1) >> 8)), last.hi);
+        }
+        return last;
+    }
+    if (pat.size() > s.size()) return wide_trivial(FHS_WIDE_ABSENT);
+    FWide pos = wide_trivial(FHS_WIDE_ABSENT);
+    const size_t end = adjust_end_of_pattern(s.size() - pat.size());
+    for (size_t i = 0; i < end; i++) {
+        FChar flag = one;
+        for (size_t j = 0; j < pat.size(); j++) flag = ch_bitand(flag, ch_eq(pat[j], s[i + j]));
+        pos.lo = ch_ite(flag, t((uint8_t)(i & 255)), pos.lo);
+        pos.hi = ch_ite(flag, t((uint8_t)(i >> 8)), pos.hi);
+    }
+    return pos;
+}
+
+FWide Strings::len_wide(const FStr &s) {                     // mod.rs:478-493 with a 16-bit counter
+    if (s.empty()) return wide_trivial(0);
+    if (fused()) {
+        std::vector<Ref> nz;
+        for (const FChar &c : s) nz.push_back(char_zero_test(c, false));
+        return num_wide(count_flags(nz, 8));
+    }
+    const FChar zero = t(0);
+    FWide result = wide_trivial(0);
+    for (const FChar &c : s) wide_add_flag(result, ch_ne(c, zero));
+    return result;
+}
+
+FWide Strings::count_flags_wide(const FStr &flags) {
+    if (flags.empty()) return wide_trivial(0);
+    if (fused()) {
+        std::vector<Ref> f;
+        for (const FChar &c : flags) f.push_back(c.b[0]);
+        return num_wide(count_flags(f, 8));
+    }
+    FWide result = wide_trivial(0);
+    for (const FChar &c : flags) wide_add_flag(result, c);
+    return result;
+}
+
 FChar Strings::eq(const FStr &a, const FStr &b) {            // mod.rs:1122-1149
     if (fused()) return f_eq(a, b);
     const FChar zero = t(0), one = t(1);
@@ -1015,11 +1110,18 @@ std::vector<Ref> Strings::f_find_window_flags(const FStr &s, const FStr &pat) {
 
 // ... and the rest of find on ALL window flags in string order: index of the first one set, 255 if none.  The sharded
 // find exchanges the flags and runs this part on every rank (fhs_dist_str_find).
-FChar Strings::f_find_from_flags(const std::vector<Ref> &f) {
-    const size_t W = f.size();
+// The wide form (8 digits, W <= 65536) is the thermometer route at every length.
+Strings::Num Strings::f_find_digits(const std::vector<Ref> &f, size_t digits) {
     std::vector<Ref> p = prefix_or(f);
     Ref found = or_tree(f);
-    if (W <= 256) return first_index(p, found);              // 255 = 3,3,3,3 when absent (:1023)
+    return first_index(p, found, digits);
+}
+
+FChar Strings::f_find_from_flags(const std::vector<Ref> &f) {
+    const size_t W = f.size();
+    if (W <= 256) return num_char(f_find_digits(f, 4));      // 255 = 3,3,3,3 when absent (:1023)
+    std::vector<Ref> p = prefix_or(f);
+    Ref found = or_tree(f);
     std::vector<Ref> first(W);
     for (size_t i = 0; i < W; i++) first[i] = pbs(lin(e_, {{2, &f[i]}, {1, &p[i]}}), LUT_IS2);
     Ref one = trivial_block(e_, 1);
@@ -1034,8 +1136,10 @@ FChar Strings::f_find_from_flags(const std::vector<Ref> &f) {
 // with at most one block q non-zero (`found` cancels inside a block).  The two high digits are used as they are, the
 // low ones refresh their blocks first (noise budget); 255 when nothing is set.  ~90 bootstraps in 1-3 levels instead of
 // the one-hot route (first = f & !before, weighted sums: ~560 in 6) -- find on 256 characters: 8 levels instead of 11.
-FChar Strings::first_index(const std::vector<Ref> &before, const Ref &found) {
-    const size_t W = before.size();                          // index in [0, W), W <= 256
+// With `digits` = 8 the same formulas give a 16-bit index (S up to 4^7, W <= 65536, absent 3 x 8 = 65535): a digit whose
+// S exceeds W has no block and is 3 nf alone, so a short string pays nothing for the four high digits.
+Strings::Num Strings::first_index(const std::vector<Ref> &before, const Ref &found, size_t digits) {
+    const size_t W = before.size();                          // index in [0, W), W <= 4^digits
     Ref one = trivial_block(e_, 1);
     Ref nf = lin(e_, {{1, &one}, {-1, &found}});
     auto g_terms = [&](size_t j, int64_t coef, std::vector<Term> &tt) {       // coef * g[j], j >= 1
@@ -1043,8 +1147,8 @@ FChar Strings::first_index(const std::vector<Ref> &before, const Ref &found) {
         tt.push_back({coef, found.id()});
         tt.push_back({-coef, j == W ? found.id() : before[j].id()});
     };
-    FChar r;
-    for (int d = 0; d < 4; d++) {
+    Num r(digits);
+    for (size_t d = 0; d < digits; d++) {
         const size_t S = (size_t)1 << (2 * d);
         std::vector<Ref> blocks;                             // L_q, values 0..3, at most one non-zero
         for (size_t q = 0; (4 * q + 1) * S <= W; q++) {
@@ -1091,7 +1195,7 @@ FChar Strings::first_index(const std::vector<Ref> &before, const Ref &found) {
         // one more bootstrap, and its value never leaves 0..3 (found: nf = 0; absent: every block is 0): it is handed back
         // as it is -- like a comparison's verdict -- instead of paying one more dependency level for a refresh; consumers
         // that weigh their operands refresh them by the engine's bookkeeping.
-        r.b[d] = lin(e_, {{1, &digit}, {3, &nf}});
+        r[d] = lin(e_, {{1, &digit}, {3, &nf}});
     }
     return r;
 }
@@ -1225,9 +1329,15 @@ Ref Strings::char_significant(const FChar &c) {
 // the weighted picks are grouped by WEIGHT (sum of digit^2 <= FHS_NOISE_BUDGET_SUM_C2, not by count), every group is
 // refreshed with LUT_MSG before groups are added up, and the digits handed back to the caller are refreshed too:
 // like every op of the reference (fheasciichar.rs:35-104) the result is a fresh, clean-carry ciphertext.
+// `digits` = 8: a 16-bit position, absent_value up to 65535.
 FChar Strings::position_of(const std::vector<Ref> &pick, size_t off, const Ref *absent_flag, int absent_value) {
+    return num_char(position_of(pick, off, absent_flag, absent_value, 4));
+}
+
+Strings::Num Strings::position_of(const std::vector<Ref> &pick, size_t off, const Ref *absent_flag, int absent_value,
+                                  size_t digits) {
     const size_t W = pick.size();
-    FChar r;
+    Num r(digits);
     // At most one pick is set.  A block that serves as the pick of TWO positions (mostly plaintext strings: one shared
     // bootstrap) can therefore never be set and is left out -- summed, its digits would add up to one large coefficient.
     std::vector<bool> twice(W, false);
@@ -1240,7 +1350,7 @@ FChar Strings::position_of(const std::vector<Ref> &pick, size_t off, const Ref *
         for (size_t a = 0; a + 1 < ids.size(); a++)
             if (ids[a].first == ids[a + 1].first) twice[ids[a].second] = twice[ids[a + 1].second] = true;
     }
-    for (int blk = 0; blk < 4; blk++) {
+    for (size_t blk = 0; blk < digits; blk++) {
         std::vector<Ref> cur;
         {
             Term tt[64];
@@ -1281,23 +1391,26 @@ FChar Strings::position_of(const std::vector<Ref> &pick, size_t off, const Ref *
         }
         Ref digit = cur.empty() ? trivial_block(e_, 0) : cur[0];
         if (absent_flag) digit = lin(e_, {{1, &digit}, {(absent_value >> (2 * blk)) & 3, absent_flag}});
-        r.b[blk] = pbs(digit, LUT_MSG);                      // folds when everything was trivial
+        r[blk] = pbs(digit, LUT_MSG);                        // folds when everything was trivial
     }
     return r;
 }
 
 // rfind (mod.rs:727-790) re-associated: the LAST matching window wins (the loop ascends and overwrites);
 // `s` already carries the NUL pushed at :737
-FChar Strings::f_rfind(const FStr &s, const FStr &pat) {
+FChar Strings::f_rfind(const FStr &s, const FStr &pat) { return num_char(f_rfind_digits(s, pat, 4)); }
+
+Strings::Num Strings::f_rfind_digits(const FStr &s, const FStr &pat, size_t digits) {
+    const int absent = digits == 4 ? FHS_MAX_FIND_LENGTH : FHS_WIDE_ABSENT;
     if (pat.empty()) {                                      // :747-760: index after the last non-NUL char
         std::vector<Ref> nz(s.size());
         for (size_t i = 0; i < s.size(); i++) nz[i] = char_nonzero(s[i]);
         std::vector<Ref> after = suffix_or(nz);
         std::vector<Ref> last(s.size());
         for (size_t i = 0; i < s.size(); i++) last[i] = pbs(lin(e_, {{2, &nz[i]}, {1, &after[i]}}), LUT_IS2);
-        return position_of(last, 1, nullptr, 0);
+        return position_of(last, 1, nullptr, 0, digits);
     }
-    if (pat.size() > s.size()) return t(255);
+    if (pat.size() > s.size()) return Num(digits, trivial_block(e_, 3));
     const size_t E = std::max<size_t>(1, s.size() - pat.size());   // adjust_end_of_pattern, exclusive bound (:768-771)
     std::vector<Ref> f(E);
     for (size_t i = 0; i < E; i++) f[i] = window_match(s, i, pat);
@@ -1307,7 +1420,7 @@ FChar Strings::f_rfind(const FStr &s, const FStr &pat) {
     Ref found = or_tree(f);
     Ref one = trivial_block(e_, 1);
     Ref nf = lin(e_, {{1, &one}, {-1, &found}});
-    return position_of(last, 0, &nf, 255);
+    return position_of(last, 0, &nf, absent, digits);
 }
 
 // ends_with (mod.rs:241-288) re-associated: the result is the match flag of the LAST window that
@@ -1575,44 +1688,57 @@ FStr Strings::f_compact(const FStr &s) {
 }
 
 // sum of 0/1 flags mod 256: groups of 15 -> (low, high) digit pair, then 4-operand radix adds
-FChar Strings::count_flags(std::vector<Ref> flags) {
-    std::vector<FChar> nums;
+FChar Strings::count_flags(std::vector<Ref> flags) { return num_char(count_flags(flags, 4)); }
+
+// ... mod 4^digits: with 8 digits the carry runs on through digits 4 to 7 (a carry out of digit 7 needs 65536 flags), but
+// only as far as a partial sum can reach: a digit above the largest possible value stays a trivial 0 instead of two
+// bootstraps on a carry that is always 0.  The four low digits are always computed, as the u8 form has them.
+Strings::Num Strings::count_flags(const std::vector<Ref> &flags, size_t digits) {
+    std::vector<Num> nums;
+    std::vector<size_t> most;                                // the largest value each partial sum can take
     for (size_t i = 0; i < flags.size(); i += 15) {
         const size_t n = std::min<size_t>(15, flags.size() - i);
         Ref s = sum_refs(e_, &flags[i], n);
-        FChar c;
+        Num c(digits);
         if (e_->sum_c2(s.id()) > FHS_NOISE_BUDGET_SUM_C2) {  // the same flag many times over (`repeat`): count in halves
             Num v = count_digits(&flags[i], n, 2);
-            c.b[0] = v[0];
-            c.b[1] = v[1];
+            c[0] = v[0];
+            c[1] = v[1];
         } else {
-            c.b[0] = pbs(s, LUT_MSG);
-            c.b[1] = n >= 4 ? pbs(s, LUT_CARRY) : trivial_block(e_, 0);
+            c[0] = pbs(s, LUT_MSG);
+            c[1] = n >= 4 ? pbs(s, LUT_CARRY) : trivial_block(e_, 0);
         }
-        c.b[2] = trivial_block(e_, 0);
-        c.b[3] = trivial_block(e_, 0);
+        for (size_t d = 2; d < digits; d++) c[d] = trivial_block(e_, 0);
         nums.push_back(c);
+        most.push_back(n);
     }
-    if (nums.empty()) return t(0);
+    if (nums.empty()) return Num(digits, trivial_block(e_, 0));
     while (nums.size() > 1) {
-        std::vector<FChar> nxt;
+        std::vector<Num> nxt;
+        std::vector<size_t> nxt_most;
         for (size_t i = 0; i < nums.size(); i += 4) {
             const size_t n = std::min<size_t>(4, nums.size() - i);
+            size_t top = 0;
+            for (size_t u = 0; u < n; u++) top += most[i + u];
+            nxt_most.push_back(top);
             if (n == 1) { nxt.push_back(nums[i]); continue; }
-            FChar r;
+            size_t live = 4;
+            while (live < digits && (top >> (2 * live)) != 0) live++;
+            Num r(digits, trivial_block(e_, 0));
             Ref carry;
-            for (int blk = 0; blk < 4; blk++) {
+            for (size_t blk = 0; blk < std::min(live, digits); blk++) {
                 Term tt[8];
                 size_t k = 0;
-                for (size_t u = 0; u < n; u++) tt[k++] = {1, nums[i + u].b[blk].id()};
+                for (size_t u = 0; u < n; u++) tt[k++] = {1, nums[i + u][blk].id()};
                 if (carry) tt[k++] = {1, carry.id()};
                 Ref sm(e_, e_->lin(tt, k, 0));   // <= 4*3 + 3 = 15
-                r.b[blk] = pbs(sm, LUT_MSG);
-                if (blk < 3) carry = pbs(sm, LUT_CARRY);
+                r[blk] = pbs(sm, LUT_MSG);
+                if (blk + 1 < std::min(live, digits)) carry = pbs(sm, LUT_CARRY);
             }
             nxt.push_back(r);
         }
         nums.swap(nxt);
+        most.swap(nxt_most);
     }
     return nums[0];
 }

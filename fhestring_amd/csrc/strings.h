@@ -9,6 +9,11 @@ namespace fhs {
 
 using FStr = std::vector<FChar>;   // FheString.bytes (fhestring.rs:6-9); cst = trivial 32 (:24)
 
+// A 16-bit unsigned result as two ordinary chars: value = lo + 256 * hi, eight little-endian base-4 digits in all.
+struct FWide {
+    FChar lo, hi;
+};
+
 struct StrError {
     int code = 0;   // FHS_ERR_LIMIT for the reference's panic!()
     const char *msg = "";
@@ -27,6 +32,13 @@ class Strings {
     FChar rfind(const FStr &s, const FStr &pat);
     FChar is_empty(const FStr &s);
     FChar len(const FStr &s);
+    // find / rfind / len with 16-bit positions and counts (the reference's are u8: src/main.rs:20, mod.rs:742-744,
+    // :1025-1027, :1044): same loops and quirks, absent = 65535, strings below 65535 + |pattern| characters
+    static bool wide_limit_reached(size_t n, size_t m);     // n counts the NUL that rfind pushes
+    FWide find_wide(const FStr &s, const FStr &pat);
+    FWide rfind_wide(const FStr &s, const FStr &pat);
+    FWide len_wide(const FStr &s);
+    FWide count_flags_wide(const FStr &flags);              // number of set 0/1 flags
     FChar eq(const FStr &a, const FStr &b);
     FChar ne(const FStr &a, const FStr &b);
     FChar eq_ignore_case(const FStr &a, const FStr &b);
@@ -86,13 +98,14 @@ class Strings {
     Ref onehot_or(std::vector<Ref> flags);   // OR of flags of which at most one is set: noise-budget-wide groups
     std::vector<Ref> block_eq_flags(const FChar &a, const FChar &b);
     Ref window_match(const FStr &s, size_t at, const FStr &pat);
+    typedef std::vector<Ref> Num;   // little-endian base-4 digits, clean (<= 3)
     FChar count_flags(std::vector<Ref> flags);   // sum of 0/1 flags mod 256 as a 4-block char
+    Num count_flags(const std::vector<Ref> &flags, size_t digits);   // ... mod 4^digits
     Ref is_upper_flag(const FChar &c, bool lower);
     std::vector<Ref> prefix_or(const std::vector<Ref> &f);
     FChar f_find(const FStr &s, const FStr &pat);
     FChar f_comparison(const FStr &a, const FStr &b, int cmp);
     // oblivious compaction: replaces the O(n^2) bubble of utils.rs:28-46 in fused mode
-    typedef std::vector<Ref> Num;   // little-endian base-4 digits, clean (<= 3)
     std::vector<Num> flag_prefix_counts(const std::vector<Ref> &flags, size_t digits);   // exclusive
     Num num_add(const std::vector<const Num *> &ops, size_t digits);
     Num count_digits(const Ref *flags, size_t k, size_t digits);   // sum of <= 15 flags as a base-4 number, within the noise budget
@@ -104,7 +117,16 @@ class Strings {
     Ref char_zero_test(const FChar &c, bool want_zero);               // 1 block, 1 bootstrap: c == 0 / c != 0
     Ref char_significant(const FChar &c);                             // 1 block: c is neither NUL nor whitespace
     FChar position_of(const std::vector<Ref> &pick, size_t index_offset, const Ref *absent_flag, int absent_value);
-    FChar first_index(const std::vector<Ref> &before, const Ref &found);
+    Num position_of(const std::vector<Ref> &pick, size_t index_offset, const Ref *absent_flag, int absent_value, size_t digits);
+    Num first_index(const std::vector<Ref> &before, const Ref &found, size_t digits);
+    static FChar num_char(const Num &v, size_t first_digit = 0);       // four digits of a number as a char
+    static FWide num_wide(const Num &v);                               // eight digits as (lo, hi)
+    FWide wide_trivial(unsigned v) const;
+    // the fused forms split where the u8 and the wide results part: flags first, digits (4 or 8) after
+    Num f_find_digits(const std::vector<Ref> &flags, size_t digits);
+    Num f_rfind_digits(const FStr &s, const FStr &pat, size_t digits);
+    // as written: counter += flag on two chars, the carry is the wrap of the low one
+    void wide_add_flag(FWide &counter, const FChar &flag);
     FChar f_eq_ignore_case(const FStr &a, const FStr &b);
     // lexicographic order as a tree of three-state values s = sign(a - b) in {-1, 0, 1}, most significant first
     std::vector<Ref> cmp_leaves(const FStr &a, const FStr &b);          // one per nibble pair, missing characters are 0

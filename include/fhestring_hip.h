@@ -37,6 +37,8 @@ extern "C" {
 #define FHS_KSK_WORDS ((size_t)2048 * 5 * 743)
 #define FHS_MAX_FIND_LENGTH 255  /* src/main.rs:20 */
 #define FHS_MAX_REPETITIONS 16   /* src/main.rs:17 */
+#define FHS_MAX_FIND_LENGTH_WIDE 65535  /* the limit of the _wide forms, where the reference has 255 (src/main.rs:20) */
+#define FHS_WIDE_ABSENT 65535           /* "not found" of the _wide forms, where the reference has 255 (mod.rs:1023) */
 
 #define FHS_OK 0
 #define FHS_ERR_ARG (-1)
@@ -277,6 +279,21 @@ int fhs_flags_and(fhs_ctx *c, const fhs_char_t *flags, size_t n, fhs_char_t *out
  * differs decides; `tie` (0 or 1) if none differs. */
 int fhs_flags_first_decides(fhs_ctx *c, const fhs_char_t *any_diff, const fhs_char_t *verdict, size_t n, int tie,
                             fhs_char_t *out);
+
+/* ---- wide positions and counts -------------------------------------------------------------------------------
+ * The reference's positions and lengths are u8 (MAX_FIND_LENGTH, src/main.rs:20): find / rfind panic from 255 + m
+ * characters on, len wraps modulo 256.  The _wide forms return a 16-bit unsigned value as TWO ordinary chars,
+ * value = *lo + 256 * *hi (eight little-endian base-4 digits; download, packed download, store, fhs_char_sum_c2,
+ * fhs_trivial_value and the char operators take either half like any char).  Same loops, same quirks, both modes;
+ * "not found" is FHS_WIDE_ABSENT; FHS_ERR_LIMIT once the string (with the NUL that rfind pushes) has
+ * FHS_MAX_FIND_LENGTH_WIDE + m characters, checked before anything is recorded.  The u8 entry points are unchanged. */
+int fhs_str_find_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const fhs_char_t *pat, size_t m, fhs_char_t *lo, fhs_char_t *hi);       /* mod.rs:1010-1053, widens :1023-1027 and :1044 */
+int fhs_str_find_clear_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, fhs_char_t *lo, fhs_char_t *hi);       /* mod.rs:1075, widens :1023-1027 and :1044 */
+int fhs_str_rfind_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const fhs_char_t *pat, size_t m, fhs_char_t *lo, fhs_char_t *hi);      /* mod.rs:727-790, widens :739-744, :753 and :783 */
+int fhs_str_len_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t *lo, fhs_char_t *hi);                                         /* mod.rs:478-493, widens the u8 counter of :485-490 */
+/* The number of set flags among n 0/1 flag chars -- the rows of a scanned table that matched, say: 256 of them already
+ * overflow a char (the u8 adds of fheasciichar.rs:88-91 chained as in mod.rs:485-490, with a carry into *hi). */
+int fhs_flags_count_wide(fhs_ctx *c, const fhs_char_t *flags, size_t n, fhs_char_t *lo, fhs_char_t *hi);
 
 /* ---- multi-GPU inside the library (one process per GPU, RCCL over xGMI) ---------------------------------
  * north_star: "characters of an FheString are independent PBS batches, so long strings shard across the GPUs of one

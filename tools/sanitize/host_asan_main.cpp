@@ -219,6 +219,23 @@ int main() {
         CHECK(fhs_str_rfind(c, s.data(), s.size(), p.data(), p.size(), &r) == FHS_OK);
         CHECK(fhs_str_is_empty(c, s.data(), s.size(), &r) == FHS_OK);
         CHECK(fhs_str_len(c, s.data(), s.size(), &r) == FHS_OK);
+        {   // the 16-bit forms: (lo, hi) handles, the same strings and a flag vector
+            fhs_char_t lo = 0, hi = 0;
+            CHECK(fhs_str_find_wide(c, s.data(), s.size(), p.data(), p.size(), &lo, &hi) == FHS_OK && lo && hi);
+            CHECK(fhs_str_find_clear_wide(c, s.data(), s.size(), "abc", 3, &lo, &hi) == FHS_OK);
+            CHECK(fhs_str_rfind_wide(c, s.data(), s.size(), p.data(), p.size(), &lo, &hi) == FHS_OK);
+            CHECK(fhs_str_rfind_wide(c, s.data(), s.size(), nullptr, 0, &lo, &hi) == FHS_OK);
+            CHECK(fhs_str_len_wide(c, s.data(), s.size(), &lo, &hi) == FHS_OK);
+            CHECK(fhs_flags_count_wide(c, s.data(), s.size(), &lo, &hi) == FHS_OK);
+            if (mode == 1 && variant == 4) {                      // past the u8 limit: digits 4 to 7 get blocks
+                auto big = mixed(1030, 40);
+                CHECK(fhs_str_find_wide(c, big.data(), big.size(), p.data(), p.size(), &lo, &hi) == FHS_OK);
+                CHECK(fhs_str_rfind_wide(c, big.data(), big.size(), p.data(), p.size(), &lo, &hi) == FHS_OK);
+                CHECK(fhs_str_len_wide(c, big.data(), big.size(), &lo, &hi) == FHS_OK);
+                CHECK(fhs_str_find(c, big.data(), big.size(), p.data(), p.size(), &r) == FHS_ERR_LIMIT);
+            }
+            CHECK(fhs_str_find_wide(c, s.data(), s.size(), p.data(), p.size(), nullptr, &hi) == FHS_ERR_ARG);
+        }
         CHECK(fhs_str_eq(c, s.data(), s.size(), o.data(), o.size(), &r) == FHS_OK);
         CHECK(fhs_str_ne(c, s.data(), s.size(), o.data(), o.size(), &r) == FHS_OK);
         CHECK(fhs_str_eq_ignore_case(c, s.data(), s.size(), o.data(), o.size(), &r) == FHS_OK);
