@@ -142,6 +142,16 @@ class Context:
         self._check(self._L.fhs_debug_rekey_device(self._h, _ptr(mask32), _ptr(body32), n_blocks, _ptr(m_out), _ptr(b_out)))
         return m_out, b_out
 
+    def rekey_packed_device(self, mask64, body64, n_blocks):
+        """fhs_debug_rekey_packed_device: the recipient download's kernel on raw 64-bit GLWEs of any block count ->
+        (mask16, body16), the arguments and results of rekey_packed_host."""
+        g = (n_blocks + PACK_GROUP - 1) // PACK_GROUP
+        mask64 = np.ascontiguousarray(mask64, np.uint64).reshape(g, POLY_N)
+        body64 = np.ascontiguousarray(body64, np.uint64).reshape(g, POLY_N)
+        m_out, b_out = np.zeros((g, POLY_N), np.uint16), np.zeros(n_blocks, np.uint16)
+        self._check(self._L.fhs_debug_rekey_packed_device(self._h, _ptr(mask64), _ptr(body64), n_blocks, _ptr(m_out), _ptr(b_out)))
+        return m_out, b_out
+
     def pbs_batch(self, cts, lut_idx, luts):
         cts = np.ascontiguousarray(cts, np.uint64).reshape(-1, BIG_CT)
         luts = np.ascontiguousarray(luts, np.uint64).reshape(-1, POLY_N)
@@ -836,6 +846,21 @@ def rekey_host(key, mask32, body32=None, n_blocks=None):
     return CompactFheString(n_blocks // 4, m_out, b_out) if compact is not None else (m_out, b_out)
 
 
+def rekey_packed_host(key, mask64, body64, n_blocks):
+    """fhs_rekey_packed_host: host reference of the packed download for a recipient.  The 64-bit GLWEs of pack_host (or of
+    download_packed(wide=True)) -> PackedFheString under the recipient's key (n_blocks a multiple of 4) or, for any other
+    block count, the raw (mask16, body16)."""
+    key = np.ascontiguousarray(key, np.uint64)
+    assert key.size == REKEY_KEY_WORDS
+    g = (n_blocks + PACK_GROUP - 1) // PACK_GROUP
+    mask64 = np.ascontiguousarray(mask64, np.uint64).reshape(g, POLY_N)
+    body64 = np.ascontiguousarray(body64, np.uint64).reshape(g, POLY_N)
+    mask16, body16 = np.zeros((g, POLY_N), np.uint16), np.zeros(n_blocks, np.uint16)
+    if lib().fhs_rekey_packed_host(_ptr(key), _ptr(mask64), _ptr(body64), n_blocks, _ptr(mask16), _ptr(body16)) != 0:
+        raise FhsError("fhs_rekey_packed_host failed")
+    return PackedFheString(n_blocks // 4, mask16, body16) if n_blocks % 4 == 0 else (mask16, body16)
+
+
 STORE_MAX_CYCLES = _K["FHS_STORE_MAX_CYCLES"]
 STORE_MAX_REKEYS = _K["FHS_STORE_MAX_REKEYS"]
 STORE_META_MAGIC = b"FHSSMET1"
@@ -1063,17 +1088,30 @@ class MyServerKey:
 
     def load_rekey_key(self, key=None, path=None):
         """fhs_load_rekey_key (the words of MyClientKey.rekey_key(to)) / fhs_load_rekey_key_file (a kind 7 file): enables
-        StoredString.rekey.  Neither: unloads the key."""
+        StoredString.rekey and download_packed(recipient=True).  Neither: unloads the key."""
         if path is not None:
             self.ctx._check(self.ctx._L.fhs_load_rekey_key_file(self.ctx._h, str(path).encode()))
         else:
             self.ctx.load_rekey_key(key)
 
-    def download_packed(self, fhe_string, wide=False):
+    def download_packed(self, fhe_string, wide=False, recipient=False):
         """fhs_download_string_packed: the string ring-packed on the GPU, 16 bits per word -> PackedFheString.
-        wide=True (diagnostic) also returns the 64-bit packed GLWEs (mask64, body64) before the storage switch."""
+        wide=True (diagnostic) also returns the 64-bit packed GLWEs (mask64, body64) before the storage switch.
+        recipient=True: fhs_download_string_packed_for, the words leave under the client key the loaded re-key key leads
+        to (load_rekey_key); the 64-bit GLWEs of wide=True stay under this context's client key.  An FheU16 goes as its
+        two chars, lo then hi."""
+        if isinstance(fhe_string, FheU16):
+            fhe_string = [fhe_string.lo, fhe_string.hi]
         chars = list(fhe_string.chars if isinstance(fhe_string, FheString) else fhe_string)
         p = PackedFheString.empty(len(chars))
+        if recipient:
+            mask64 = body64 = None
+            if wide:
+                mask64, body64 = np.zeros(p.mask16.shape, np.uint64), np.zeros(p.mask16.shape, np.uint64)
+            self.ctx._check(self.ctx._L.fhs_download_string_packed_for(
+                self.ctx._h, _harr(chars), len(chars), _ptr(p.mask16), _ptr(p.body16),
+                None if mask64 is None else _ptr(mask64), None if body64 is None else _ptr(body64)))
+            return (p, mask64, body64) if wide else p
         if not wide:
             self.ctx._check(self.ctx._L.fhs_download_string_packed(self.ctx._h, _harr(chars), len(chars), _ptr(p.mask16),
                                                                    _ptr(p.body16)))

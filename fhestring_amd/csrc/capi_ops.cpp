@@ -315,6 +315,25 @@ int fhs_debug_rekey_device(fhs_ctx *c, const void *mask32, const void *body32, s
     return c->eng.debug_rekey(static_cast<const uint32_t *>(mask32), static_cast<const uint32_t *>(body32), n_blocks,
                               static_cast<uint32_t *>(mask32_out), static_cast<uint32_t *>(body32_out));
 }
+// ---- packed result download under a recipient's key ----
+int fhs_download_string_packed_for(fhs_ctx *c, const fhs_char_t *chars, size_t n, void *mask16, void *body16, uint64_t *mask64,
+                                   uint64_t *body64) {
+    if (!c || (n && (!chars || !mask16 || !body16)) || !mask64 != !body64) return bad(c);
+    if (n == 0) return FHS_OK;
+    std::vector<Bid> b(4 * n);
+    for (size_t i = 0; i < n; i++) {
+        if (!c->eng.valid_char(chars[i])) return bad(c);
+        const Bid *cb = c->eng.char_blocks(chars[i]);
+        for (int k = 0; k < 4; k++) b[4 * i + k] = cb[k];
+    }
+    return c->eng.read_packed(b.data(), b.size(), static_cast<uint16_t *>(mask16), static_cast<uint16_t *>(body16), mask64,
+                              body64, true);
+}
+int fhs_debug_rekey_packed_device(fhs_ctx *c, const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, void *mask16,
+                                  void *body16) {
+    if (!c || (n_blocks && (!mask64 || !body64 || !mask16 || !body16)) || n_blocks > ((size_t)1 << 26)) return bad(c);
+    return c->eng.debug_rekey_packed(mask64, body64, n_blocks, static_cast<uint16_t *>(mask16), static_cast<uint16_t *>(body16));
+}
 int fhs_export_device(fhs_ctx *c, fhs_char_t a, uint64_t *d_blocks) {
     if (!ok(c, a) || !d_blocks) return bad(c);
     const Bid *b = c->eng.char_blocks(a);

@@ -158,7 +158,10 @@ class Engine {
     int read_many(const Bid *b, size_t count, uint64_t *host_out);
     // packed download (pack_kernels.hip): ring-packs the blocks in groups of 2048 and stores them at 16 bits; mask16
     // [groups][2048], body16 [count].  mask64 / body64 (diagnostic, may be null): the 64-bit GLWEs [groups][2048].
-    int read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *body16, uint64_t *mask64, uint64_t *body64);
+    // recipient: the 16-bit words leave under the client key the context's re-key key leads to (rekey_packed_kernel in
+    // place of the storage switch, one launch per pass); mask64 / body64 stay the tree's output under the sender's key.
+    int read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *body16, uint64_t *mask64, uint64_t *body64,
+                    bool recipient = false);
     // ---- device-resident string store (store_kernels.hip; include/fhestring_hip.h, "device-resident string store") ----
     // An entry is one block sequence parked in the compact-string format: mask32[ceil(n / 2048)][2048] | body32[n] in ONE
     // device allocation of its exact size, plus what the bookkeeping knew about every block at store_put (host side).
@@ -193,6 +196,8 @@ class Engine {
     int store_rekey(uint64_t id, uint64_t *id_out);
     // diagnostic: the kernel on host words of any block count; the outputs may be the inputs
     int debug_rekey(const uint32_t *mask32, const uint32_t *body32, size_t n_blocks, uint32_t *mask_out, uint32_t *body_out);
+    // diagnostic: the recipient download's kernel alone on host words, mask64 / body64 [ceil(n_blocks / 2048)][2048]
+    int debug_rekey_packed(const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, uint16_t *mask16, uint16_t *body16);
     // flushes if needed (do_flush = false: the caller has made sure the block's tick is enqueued); wait=false: enqueue only
     int copy_block_to_device(Bid b, uint64_t *d_out, bool wait = true, bool do_flush = true);
     uint64_t blocks_live() const { return pool_.live(); }
@@ -339,6 +344,8 @@ class Engine {
     // one re-key launch over the groups of n_blocks blocks (device pointers, entry layout; out may be in), on the stream
     hipError_t rekey_words(const uint32_t *d_mask, const uint32_t *d_body, uint32_t *d_mask_out, uint32_t *d_body_out,
                            size_t n_blocks);
+    // one launch of the recipient download's kernel: level-11 GLWEs [groups][2][2048] -> 16-bit words under the new key
+    hipError_t rekey_packed_words(const uint64_t *d_glwe, uint16_t *d_mask16, uint16_t *d_body16, size_t n_blocks);
     hipError_t pack_tree_pass(const Bid *b, size_t n, size_t groups);
     std::map<uint64_t, StoreEntry> store_;
     uint64_t store_ids_ = 0;             // ids handed out: never reused inside a context

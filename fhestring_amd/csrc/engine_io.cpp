@@ -350,9 +350,11 @@ hipError_t Engine::pack_tree_pass(const Bid *b, size_t n, size_t groups) {
     return e;
 }
 
-int Engine::read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *body16, uint64_t *mask64, uint64_t *body64) {
+int Engine::read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *body16, uint64_t *mask64, uint64_t *body64,
+                        bool recipient) {
     if (planner) return ctx.fail(-3, "planner context: nothing is computed, there is nothing to download");
     if (!ctx.d_pack_key_ntt) return ctx.fail(-3, "packing key not loaded (fhs_load_packing_key)");
+    if (recipient && !ctx.d_rekey_key_ntt) return ctx.fail(-3, "re-key key not loaded (fhs_load_rekey_key)");
     if (count == 0) return 0;
     if (int rc = prepare_packing(b, count)) return rc;
     constexpr size_t MAX_GROUPS = 4, GLWE_BYTES = 2 * POLY_N * 8;
@@ -363,7 +365,9 @@ int Engine::read_packed(const Bid *b, size_t count, uint16_t *mask16, uint16_t *
         hipError_t e = ctx.pack_out.reserve(groups * 2 * PACK_GROUP * sizeof(uint16_t));
         if (e == hipSuccess) e = pack_tree_pass(b + done, n, groups);
         uint16_t *d_mask = ctx.pack_out.as<uint16_t>(), *d_body = d_mask + groups * PACK_GROUP;
-        if (e == hipSuccess) e = launch_pack_switch16(ctx.pack_ws[0].as<uint64_t>(), d_mask, d_body, (int)groups, (uint32_t)n, ctx.stream);
+        if (e == hipSuccess && !recipient)
+            e = launch_pack_switch16(ctx.pack_ws[0].as<uint64_t>(), d_mask, d_body, (int)groups, (uint32_t)n, ctx.stream);
+        if (e == hipSuccess && recipient) e = rekey_packed_words(ctx.pack_ws[0].as<uint64_t>(), d_mask, d_body, n);
         if (e == hipSuccess)
             e = hipMemcpyAsync(mask16 + done, d_mask, groups * PACK_GROUP * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx.stream);
         if (e == hipSuccess) e = hipMemcpyAsync(body16 + done, d_body, n * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx.stream);
@@ -589,6 +593,42 @@ hipError_t Engine::rekey_words(const uint32_t *d_mask, const uint32_t *d_body, u
     p.total = (uint32_t)n_blocks; p.groups = (int)((n_blocks + REKEY_GROUP - 1) / REKEY_GROUP);
     p.key_ntt = ctx.d_rekey_key_ntt.as<double>(); p.tw = ctx.tw;
     return launch_rekey_glwe(p, ctx.stream);
+}
+
+// The recipient download's kernel over `n_blocks` blocks of level-11 GLWEs [groups][mask, body][2048]: one launch.
+hipError_t Engine::rekey_packed_words(const uint64_t *d_glwe, uint16_t *d_mask16, uint16_t *d_body16, size_t n_blocks) {
+    RekeyPackedParams p{};
+    p.src = d_glwe; p.dst_mask = d_mask16; p.dst_body = d_body16;
+    p.total = (uint32_t)n_blocks; p.groups = (int)((n_blocks + REKEY_GROUP - 1) / REKEY_GROUP);
+    p.key_ntt = ctx.d_rekey_key_ntt.as<double>(); p.tw = ctx.tw;
+    return launch_rekey_packed(p, ctx.stream);
+}
+
+// Diagnostic: that kernel on raw host words of any block count.  The host arrays are [groups][2048] each; the device
+// layout interleaves them per group, as the packing tree leaves them.
+int Engine::debug_rekey_packed(const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, uint16_t *mask16, uint16_t *body16) {
+    if (planner) return ctx.fail(-3, "planner context: nothing is computed");
+    if (!ctx.d_rekey_key_ntt) return ctx.fail(-3, "re-key key not loaded (fhs_load_rekey_key)");
+    if (n_blocks == 0) return 0;
+    (void)hipSetDevice(ctx.device);
+    const size_t groups = (n_blocks + REKEY_GROUP - 1) / REKEY_GROUP, words = groups * POLY_N;
+    std::vector<uint64_t> glwe(2 * words);
+    for (size_t g = 0; g < groups; g++) {
+        std::memcpy(glwe.data() + g * 2 * POLY_N, mask64 + g * POLY_N, POLY_N * 8);
+        std::memcpy(glwe.data() + (g * 2 + 1) * POLY_N, body64 + g * POLY_N, POLY_N * 8);
+    }
+    DevBuf buf;
+    hipError_t e = buf.reserve_exact(2 * words * 8 + (words + n_blocks) * 2);
+    uint64_t *d_glwe = buf.as<uint64_t>();
+    uint16_t *d_mask = reinterpret_cast<uint16_t *>(d_glwe + 2 * words), *d_body = d_mask + words;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_glwe, glwe.data(), 2 * words * 8, hipMemcpyHostToDevice, ctx.stream);
+    if (e == hipSuccess) e = rekey_packed_words(d_glwe, d_mask, d_body, n_blocks);
+    if (e == hipSuccess) e = hipMemcpyAsync(mask16, d_mask, words * 2, hipMemcpyDeviceToHost, ctx.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(body16, d_body, n_blocks * 2, hipMemcpyDeviceToHost, ctx.stream);
+    hipError_t es = hipStreamSynchronize(ctx.stream);            // before buf and glwe go, on every path
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return ctx.hip_fail(e, "recipient re-key (diagnostic)");
+    return 0;
 }
 
 // Diagnostic: the kernel on raw host words of any block count, through a scratch allocation of the entry layout.

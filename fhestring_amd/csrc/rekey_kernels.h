@@ -1,4 +1,4 @@
-// Device side of the string store's re-key (rekey_kernels.hip; host reference: rekey_host.cpp).
+// Device side of the string store's re-key (rekey_kernels.hip; host reference: rekey_host.cpp; DESIGN.md sections 14, 16).
 #pragma once
 #include "pbs_kernels.h"
 
@@ -20,7 +20,19 @@ struct RekeyParams {
     NttTables tw;
 };
 
+// The packed download for a recipient: `groups` level-11 GLWEs of the packing tree, src[groups][mask, body][2048] u64, to
+// the packed format under the new key: dst_mask[groups][2048], dst_body[total] (group g's bodies start at 2048 g).
+struct RekeyPackedParams {
+    const uint64_t *src;
+    uint16_t *dst_mask, *dst_body;
+    uint32_t total;
+    int groups;
+    const double *key_ntt;   // as RekeyParams
+    NttTables tw;
+};
+
 hipError_t prepare_device_for_rekey();   // dynamic LDS above 64 KB, per device
 hipError_t launch_rekey_glwe(const RekeyParams &p, hipStream_t s);
+hipError_t launch_rekey_packed(const RekeyPackedParams &p, hipStream_t s);
 
 }  // namespace fhs

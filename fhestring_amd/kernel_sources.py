@@ -19,6 +19,7 @@ KERNEL_SOURCES = {
     "blind_rotate_ntt_mb2_kernel": ["nttmb_kernels.hip"] + _NTT,
     "pack_level_kernel": ["pack_kernels.hip", "pack_kernels.h"] + _NTT,
     "rekey_glwe_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _NTT,
+    "rekey_packed_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _NTT,
     "pack_switch16_kernel": ["pack_kernels.hip", "pack_kernels.h", FLAGS],
     "keyswitch_mfma_kernel": ["ks_kernels.hip", FLAGS],
     "keyswitch_mfma2_kernel": ["ks_kernels.hip", FLAGS],

@@ -768,6 +768,40 @@ int fhs_rekey_host(const uint64_t *key, const void *mask32, const void *body32, 
 int fhs_debug_rekey_device(fhs_ctx *ctx, const void *mask32, const void *body32, size_t n_blocks, void *mask32_out,
                            void *body32_out);
 
+/* ---- packed result download under a recipient's key ----------------------------------------------------------
+ * A result computed under client a's server key can leave the server under client b's key: the packing tree runs as for
+ * fhs_download_string_packed (a's packing key), and the re-key key a -> b of the section above -- the same key, the same
+ * format, kind 7 file -- switches its level-11 GLWE (M64[2048], B64[2048]) of every group of up to 2048 blocks to S_b in
+ * place of the storage switch.  Exact, wrapping 64-bit words in R = Z_2^64[X]/(X^2048 + 1):
+ *   a = (M64 + 2^31) >> 32 (fhs_pack_switch32's word; a carry out of the top wraps to 0),
+ *   a << 32 = d_0 2^48 + d_1 2^32 with the balanced digits above,  Sum_col = sum_l d_l * key[l].col,
+ *   mask16 = ((-Sum_mask + 2^47) >> 48) & 0xffff,   body16_j = ((B64_j - Sum_body,j + 2^47) >> 48) & 0xffff for j < count.
+ * The body is not rounded on the way in: one rounding, fhs_pack_switch16's, at the end.  The output has the layout of
+ * fhs_download_string_packed and b decrypts it with the unchanged fhs_client_decrypt_packed_str / _blocks.
+ * Noise: packing 2^43.1, the mask's 32-bit rounding 2^35.2 and the keyswitch 2^32.6 all disappear under the final 16-bit
+ * rounding, 2^48 sqrt((1 + |S_b|^2) / 12) ~ 2^51.2, the term that dominates an own-key download too: the decode margin
+ * against 2^58 is the one of the packed download.  Handles and their figures are left as they are.
+ * A context CANNOT TELL which client key its blocks are under, nor which key the loaded re-key key starts from or leads
+ * to: a recipient download of blocks that are not under the `from` key of the loaded key (after a server-key switch, or
+ * of a string restored from an entry that was re-keyed) gives garbage without any error.  Keeping track is the caller's
+ * business. */
+/* fhs_download_string_packed for the recipient of the loaded re-key key; takes what it takes and leaves the handles
+ * unchanged.  mask64 / body64 (both or neither, may be NULL): the level-11 GLWEs under the SENDER's key, as
+ * fhs_debug_download_string_packed64 gives them, so that a caller can check the device words against
+ * fhs_rekey_packed_host.  n = 0 returns 0 in every state.  FHS_ERR_STATE: a planner context, no packing key, or no
+ * re-key key (fhs_last_error says which). */
+int fhs_download_string_packed_for(fhs_ctx *ctx, const fhs_char_t *chars, size_t n, void *mask16, void *body16,
+                                   uint64_t *mask64 /*may be NULL*/, uint64_t *body64 /*may be NULL*/);
+/* Host reference (public data only, no GPU): the same words as the device.  mask64 / body64 [ceil(n_blocks / 2048)][2048]
+ * as fhs_pack_host produces them; mask16[ceil(n_blocks / 2048)][2048], body16[n_blocks] as fhs_pack_switch16 writes
+ * them (bodies beyond n_blocks are not written). */
+int fhs_rekey_packed_host(const uint64_t *key, const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, void *mask16,
+                          void *body16);
+/* Diagnostic: the device kernel alone on raw words of ANY block count, one launch over all groups, arguments of
+ * fhs_rekey_packed_host.  FHS_ERR_STATE without a re-key key or on a planner context. */
+int fhs_debug_rekey_packed_device(fhs_ctx *ctx, const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, void *mask16,
+                                  void *body16);
+
 #ifdef __cplusplus
 }
 #endif

@@ -76,6 +76,17 @@ int main() {
             CHECK(fhs_client_create_insecure_seeded(43, &to) == FHS_OK);
             std::vector<uint64_t> rk(FHS_REKEY_KEY_WORDS), rk2;
             CHECK(fhs_client_rekey_key(ck, to, rk.data()) == FHS_OK && fhs_client_rekey_key(ck, nullptr, rk.data()) == FHS_ERR_ARG);
+            {   // ... and widened to 64-bit GLWEs, as a packed download for that client (fhs_rekey_packed_host)
+                std::vector<uint64_t> m64(mw), b64(mw, 0);
+                for (size_t i = 0; i < mw; i++) m64[i] = (uint64_t)m32[i] << 32;
+                for (size_t i = 0; i < bw; i++) b64[i] = (uint64_t)b32[i] << 32;
+                std::vector<uint16_t> m16(mw), b16(bw);
+                std::vector<char> all(518);
+                CHECK(fhs_rekey_packed_host(rk.data(), m64.data(), b64.data(), bw, m16.data(), b16.data()) == FHS_OK);
+                CHECK(fhs_client_decrypt_packed_str(to, m16.data(), b16.data(), 517, all.data(), &pn) == FHS_OK && pn == 515 &&
+                      !std::memcmp(all.data(), text.data(), 515));
+                CHECK(fhs_rekey_packed_host(rk.data(), nullptr, nullptr, 4, nullptr, nullptr) == FHS_ERR_ARG);
+            }
             CHECK(fhs_rekey_host(rk.data(), m32.data(), b32.data(), bw, m32.data(), b32.data()) == FHS_OK);
             CHECK(fhs_expand_public_str(m32.data(), b32.data(), 517, 507, 10, win.data()) == FHS_OK);
             CHECK(fhs_client_decrypt_str(to, win.data(), 10, pbuf, &pn) == FHS_OK && pn == 8 && !std::memcmp(pbuf, "ssssssss", 8));
@@ -276,6 +287,9 @@ int main() {
         CHECK(fhs_store_rekey_count(c, id, &nk) == FHS_OK && nk == 1);
         CHECK(fhs_store_get(c, id2, 0, 3, back.data()) == FHS_OK && fhs_store_drop(c, id) == FHS_OK && fhs_store_drop(c, id2) == FHS_OK);
         CHECK(fhs_load_rekey_key(c, nullptr) == FHS_OK && fhs_load_rekey_key_file(c, "/nonexistent-directory/key.bin") == FHS_ERR_STATE);
+        uint16_t w16[4];
+        CHECK(fhs_download_string_packed_for(c, s.data(), 0, nullptr, nullptr, nullptr, nullptr) == FHS_OK &&
+              fhs_download_string_packed_for(c, s.data(), 1, w16, w16, nullptr, nullptr) == FHS_ERR_STATE);   // a planner
     }
     {   // level-skewed batching: jobs on ticks, dependent jobs, handles released while their levels are still scheduled
         CHECK(fhs_set_mode(c, 1) == FHS_OK);
