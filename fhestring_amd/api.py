@@ -387,16 +387,19 @@ class MyClientKey:
     def decrypt_packed_blocks(self, p):
         """Every block of a PackedFheString mod 32 (message, carry and padding bits): [4 n] u8."""
         out = np.zeros(4 * len(p), np.uint8)
-        if self._L.fhs_client_decrypt_packed_blocks(self._h, _ptr(p.mask16), _ptr(p.body16), 4 * len(p), _ptr(out)) != 0:
-            raise FhsError("fhs_client_decrypt_packed_blocks failed")
+        if self._L.fhs_client_decrypt_packed_blocks_at(self._h, _ptr(p.mask16), _ptr(p.body16), p.first_coef, 4 * len(p),
+                                                       _ptr(out)) != 0:
+            raise FhsError("fhs_client_decrypt_packed_blocks_at failed")
         return out
 
     def decrypt_packed(self, p):
-        """fhs_client_decrypt_packed_str: MyClientKey.decrypt on a PackedFheString (truncates at the first NUL)."""
+        """fhs_client_decrypt_packed_str_at: MyClientKey.decrypt on a PackedFheString, whole or a window of a parked
+        entry (truncates at the first NUL)."""
         buf = C.create_string_buffer(len(p) + 1)
         n = C.c_size_t()
-        if self._L.fhs_client_decrypt_packed_str(self._h, _ptr(p.mask16), _ptr(p.body16), len(p), buf, C.byref(n)) != 0:
-            raise FhsError("fhs_client_decrypt_packed_str failed")
+        if self._L.fhs_client_decrypt_packed_str_at(self._h, _ptr(p.mask16), _ptr(p.body16), p.first_coef, len(p), buf,
+                                                    C.byref(n)) != 0:
+            raise FhsError("fhs_client_decrypt_packed_str_at failed")
         return buf.raw[:n.value].decode("ascii")
 
     def public_key(self):
@@ -746,48 +749,67 @@ class CompactFheString:
 class PackedFheString:
     """A result string as it leaves the server packed: one 2048 x u16 GLWE mask per group of 512 characters and one u16
     body per block (include/fhestring_hip.h, "packed result download").  Serialised form: magic FHSPSTR1, n (u64), masks,
-    bodies: 16 + 4096 * ceil(4 n / 2048) + 8 n bytes."""
+    bodies: 16 + 4096 * ceil(4 n / 2048) + 8 n bytes.
+    A window of a parked entry (StoredString.download_packed) starts at coefficient first_coef of its first mask instead
+    of 0: block i is coefficient (first_coef + i) % 2048 of mask (first_coef + i) // 2048, and the masks are those of
+    the ceil((first_coef + 4 n) / 2048) covering groups.  With first_coef = 0 nothing changes, the bytes included; any
+    other serialises as magic FHSPSTW1, n (u64), first_coef (u64), masks, bodies."""
 
     MAGIC = b"FHSPSTR1"
+    MAGIC_WINDOW = b"FHSPSTW1"
 
-    def __init__(self, n_chars, mask16, body16):
-        self.n_chars = int(n_chars)
+    def __init__(self, n_chars, mask16, body16, first_coef=0):
+        self.n_chars, self.first_coef = int(n_chars), int(first_coef)
+        if self.first_coef % 4 or not 0 <= self.first_coef < PACK_GROUP:
+            raise ValueError("first_coef is a multiple of 4 below %d, not %d" % (PACK_GROUP, self.first_coef))
         mask16, body16 = np.ascontiguousarray(mask16, np.uint16), np.ascontiguousarray(body16, np.uint16)
-        if mask16.size != self.groups(self.n_chars) * POLY_N or body16.size != 4 * self.n_chars:
-            raise ValueError("packed FheString of %d characters needs %d groups and %d bodies" %
-                             (self.n_chars, self.groups(self.n_chars), 4 * self.n_chars))
-        self.mask16 = mask16.reshape(self.groups(self.n_chars), POLY_N)
+        g = self.groups(self.n_chars, self.first_coef)
+        if mask16.size != g * POLY_N or body16.size != 4 * self.n_chars:
+            raise ValueError("packed FheString of %d characters needs %d groups and %d bodies" % (self.n_chars, g, 4 * self.n_chars))
+        self.mask16 = mask16.reshape(g, POLY_N)
         self.body16 = body16.reshape(4 * self.n_chars)
 
     @staticmethod
-    def groups(n_chars):
-        return (4 * n_chars + PACK_GROUP - 1) // PACK_GROUP
+    def groups(n_chars, first_coef=0):
+        return (first_coef + 4 * n_chars + PACK_GROUP - 1) // PACK_GROUP if n_chars else 0
 
     @classmethod
-    def empty(cls, n_chars):
-        return cls(n_chars, np.zeros((cls.groups(n_chars), POLY_N), np.uint16), np.zeros(4 * n_chars, np.uint16))
+    def empty(cls, n_chars, first_coef=0):
+        return cls(n_chars, np.zeros((cls.groups(n_chars, first_coef), POLY_N), np.uint16), np.zeros(4 * n_chars, np.uint16),
+                   first_coef)
 
     def __len__(self):
         return self.n_chars
 
     @property
     def nbytes(self):
-        return 16 + self.mask16.nbytes + self.body16.nbytes
+        return (24 if self.first_coef else 16) + self.mask16.nbytes + self.body16.nbytes
 
     def to_bytes(self):
-        return self.MAGIC + np.uint64(self.n_chars).tobytes() + self.mask16.tobytes() + self.body16.tobytes()
+        head = self.MAGIC + np.uint64(self.n_chars).tobytes()
+        if self.first_coef:
+            head = self.MAGIC_WINDOW + np.uint64(self.n_chars).tobytes() + np.uint64(self.first_coef).tobytes()
+        return head + self.mask16.tobytes() + self.body16.tobytes()
 
     @classmethod
     def from_bytes(cls, data):
         data = bytes(data)
-        if data[:8] != cls.MAGIC or len(data) < 16:
+        window = data[:8] == cls.MAGIC_WINDOW
+        head = 24 if window else 16
+        if (data[:8] != cls.MAGIC and not window) or len(data) < head:
             raise ValueError("not a packed FheString")
         n = int(np.frombuffer(data, np.uint64, 1, 8)[0])
-        g = cls.groups(n)
-        need = 16 + 2 * POLY_N * g + 8 * n
-        if n > (1 << 24) or len(data) != need:
+        first_coef = int(np.frombuffer(data, np.uint64, 1, 16)[0]) if window else 0
+        if window and (first_coef % 4 or not 0 < first_coef < PACK_GROUP):
+            raise ValueError("packed window: first_coef %d is not a non-zero multiple of 4 below %d" % (first_coef, PACK_GROUP))
+        if n > (1 << 24):
+            raise ValueError("packed FheString of %d characters" % n)
+        g = cls.groups(n, first_coef)
+        need = head + 2 * POLY_N * g + 8 * n
+        if len(data) != need:
             raise ValueError("packed FheString of %d characters needs %d bytes, got %d" % (n, need, len(data)))
-        return cls(n, np.frombuffer(data, np.uint16, POLY_N * g, 16), np.frombuffer(data, np.uint16, 4 * n, 16 + 2 * POLY_N * g))
+        return cls(n, np.frombuffer(data, np.uint16, POLY_N * g, head), np.frombuffer(data, np.uint16, 4 * n, head + 2 * POLY_N * g),
+                   first_coef)
 
 
 def pack_host(key, blocks):
@@ -859,6 +881,28 @@ def rekey_packed_host(key, mask64, body64, n_blocks):
     if lib().fhs_rekey_packed_host(_ptr(key), _ptr(mask64), _ptr(body64), n_blocks, _ptr(mask16), _ptr(body16)) != 0:
         raise FhsError("fhs_rekey_packed_host failed")
     return PackedFheString(n_blocks // 4, mask16, body16) if n_blocks % 4 == 0 else (mask16, body16)
+
+
+def store_packed_words(first_char, count):
+    """fhs_store_packed_words -> (mask_words, body_words, first_coef) of the windowed packed form."""
+    m, b, f = C.c_size_t(), C.c_size_t(), C.c_uint32()
+    lib().fhs_store_packed_words(int(first_char), int(count), C.byref(m), C.byref(b), C.byref(f))
+    return int(m.value), int(b.value), int(f.value)
+
+
+def store_packed_host(key, compact, first_char=0, count=None):
+    """fhs_store_packed_host: host reference of StoredString.download_packed.  `compact`: the whole entry as export()
+    gives it (a CompactFheString); key: the re-key key of a recipient download, None for the entry's own key ->
+    PackedFheString of characters [first_char, first_char + count)."""
+    first_char, count = compact._window(first_char, count)
+    if key is not None:
+        key = np.ascontiguousarray(key, np.uint64)
+        assert key.size == REKEY_KEY_WORDS
+    p = PackedFheString.empty(count, store_packed_words(first_char, count)[2])
+    if lib().fhs_store_packed_host(None if key is None else _ptr(key), _ptr(compact.mask32), _ptr(compact.body32), 4 * len(compact),
+                                   first_char, count, _ptr(p.mask16), _ptr(p.body16)) != 0:
+        raise FhsError("fhs_store_packed_host failed")
+    return p
 
 
 STORE_MAX_CYCLES = _K["FHS_STORE_MAX_CYCLES"]
@@ -938,6 +982,17 @@ class StoredString:
         n = C.c_uint32(0)
         self.sk.ctx._check(self.sk.ctx._L.fhs_store_rekey_count(self.sk.ctx._h, self.id, C.byref(n)))
         return int(n.value)
+
+    def download_packed(self, first_char=0, count=None, recipient=False):
+        """fhs_store_download_packed: characters [first_char, first_char + count) straight from the parked entry as a
+        PackedFheString (its first_coef = 4 first_char % 2048), under the entry's key or, recipient=True, under the key the
+        loaded re-key key leads to.  Nothing is expanded; needs no packing key; the entry stays as it is."""
+        if count is None:
+            count = len(self) - first_char
+        p = PackedFheString.empty(max(0, int(count)), store_packed_words(first_char, max(0, int(count)))[2])
+        self.sk.ctx._check(self.sk.ctx._L.fhs_store_download_packed(self.sk.ctx._h, self.id, int(first_char), int(count),
+                                                                    int(bool(recipient)), _ptr(p.mask16), _ptr(p.body16)))
+        return p
 
     def export(self):
         """fhs_store_export -> (CompactFheString, meta[4n] u64); store_export_to_bytes serialises the pair."""

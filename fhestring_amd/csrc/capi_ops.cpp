@@ -334,6 +334,12 @@ int fhs_debug_rekey_packed_device(fhs_ctx *c, const uint64_t *mask64, const uint
     if (!c || (n_blocks && (!mask64 || !body64 || !mask16 || !body16)) || n_blocks > ((size_t)1 << 26)) return bad(c);
     return c->eng.debug_rekey_packed(mask64, body64, n_blocks, static_cast<uint16_t *>(mask16), static_cast<uint16_t *>(body16));
 }
+// ---- string store: packed download of parked entries ----
+int fhs_store_download_packed(fhs_ctx *c, uint64_t id, size_t first_char, size_t count, int recipient, void *mask16, void *body16) {
+    if (!c || (count && (!mask16 || !body16))) return bad(c);
+    return c->eng.store_read_packed(id, first_char, count, recipient != 0, static_cast<uint16_t *>(mask16),
+                                    static_cast<uint16_t *>(body16));
+}
 int fhs_export_device(fhs_ctx *c, fhs_char_t a, uint64_t *d_blocks) {
     if (!ok(c, a) || !d_blocks) return bad(c);
     const Bid *b = c->eng.char_blocks(a);

@@ -482,12 +482,13 @@ void keygen_packing(fhs_client *ck) {
     });
 }
 
-// phases of one packed group: ph[j] = (body16[j] << 48) - ((mask16 << 48) (*) S)[j], j < count
-void packed_phases(const fhs_client *ck, const uint16_t *mask16, const uint16_t *body16, size_t count, uint64_t *ph) {
+// phases of the coefficients [lo, hi) of one packed group: ph[n - lo] = (body16[n - lo] << 48) - ((mask16 << 48) (*) S)[n];
+// body16 points at the body of coefficient lo
+void packed_phases(const fhs_client *ck, const uint16_t *mask16, const uint16_t *body16, size_t lo, size_t hi, uint64_t *ph) {
     std::vector<uint64_t> a(POLY_N), prod(POLY_N);
     for (int i = 0; i < POLY_N; i++) a[i] = (uint64_t)mask16[i] << 48;
     mul_binary(a.data(), ck->glwe_sk.data(), prod.data());
-    for (size_t j = 0; j < count; j++) ph[j] = ((uint64_t)body16[j] << 48) - prod[j];
+    for (size_t n = lo; n < hi; n++) ph[n - lo] = ((uint64_t)body16[n - lo] << 48) - prod[n];
 }
 
 }  // namespace
@@ -514,25 +515,32 @@ int fhs_client_encrypt_blocks(fhs_client *ck, const uint8_t *values, size_t n, u
     return FHS_OK;
 }
 
-int fhs_client_decrypt_packed_blocks(const fhs_client *ck, const void *mask16_, const void *body16_, size_t n_blocks,
-                                     uint8_t *out) {
+int fhs_client_decrypt_packed_blocks_at(const fhs_client *ck, const void *mask16_, const void *body16_, uint32_t first_coef,
+                                        size_t n_blocks, uint8_t *out) {
     const uint16_t *mask16 = static_cast<const uint16_t *>(mask16_), *body16 = static_cast<const uint16_t *>(body16_);
-    if (!ck || (n_blocks && (!mask16 || !body16 || !out))) return FHS_ERR_ARG;
+    if (!ck || (first_coef & 3) || first_coef >= FHS_PACK_GROUP || (n_blocks && (!mask16 || !body16 || !out))) return FHS_ERR_ARG;
     std::vector<uint64_t> ph(FHS_PACK_GROUP);
-    for (size_t g = 0; g * FHS_PACK_GROUP < n_blocks; g++) {
-        const size_t count = std::min<size_t>(FHS_PACK_GROUP, n_blocks - g * FHS_PACK_GROUP);
-        packed_phases(ck, mask16 + g * POLY_N, body16 + g * FHS_PACK_GROUP, count, ph.data());
-        for (size_t j = 0; j < count; j++)
-            out[g * FHS_PACK_GROUP + j] = (uint8_t)(((ph[j] + (1ull << (DELTA_LOG - 1))) >> DELTA_LOG) & 31);
+    // block i is coefficient (first_coef + i) % 2048 of mask (first_coef + i) / 2048
+    const size_t end = first_coef + n_blocks;
+    for (size_t g = 0; g * FHS_PACK_GROUP < end && n_blocks; g++) {
+        const size_t base = g * FHS_PACK_GROUP, lo = g ? 0 : first_coef, hi = std::min<size_t>(FHS_PACK_GROUP, end - base);
+        const size_t i0 = base + lo - first_coef;                    // the window's block at coefficient lo
+        packed_phases(ck, mask16 + g * POLY_N, body16 + i0, lo, hi, ph.data());
+        for (size_t j = 0; j < hi - lo; j++) out[i0 + j] = (uint8_t)(((ph[j] + (1ull << (DELTA_LOG - 1))) >> DELTA_LOG) & 31);
     }
     return FHS_OK;
 }
 
-int fhs_client_decrypt_packed_str(const fhs_client *ck, const void *mask16, const void *body16, size_t n_chars,
-                                  char *out, size_t *out_len) {
+int fhs_client_decrypt_packed_blocks(const fhs_client *ck, const void *mask16, const void *body16, size_t n_blocks,
+                                     uint8_t *out) {
+    return fhs_client_decrypt_packed_blocks_at(ck, mask16, body16, 0, n_blocks, out);
+}
+
+int fhs_client_decrypt_packed_str_at(const fhs_client *ck, const void *mask16, const void *body16, uint32_t first_coef,
+                                     size_t n_chars, char *out, size_t *out_len) {
     if (!ck || !out || !out_len || (n_chars && (!mask16 || !body16))) return FHS_ERR_ARG;
     std::vector<uint8_t> blk(4 * n_chars);
-    if (int rc = fhs_client_decrypt_packed_blocks(ck, mask16, body16, 4 * n_chars, blk.data())) return rc;
+    if (int rc = fhs_client_decrypt_packed_blocks_at(ck, mask16, body16, first_coef, 4 * n_chars, blk.data())) return rc;
     size_t k = 0;
     for (size_t i = 0; i < n_chars; i++) {
         unsigned v = 0;
@@ -542,6 +550,11 @@ int fhs_client_decrypt_packed_str(const fhs_client *ck, const void *mask16, cons
     }
     *out_len = k;
     return FHS_OK;
+}
+
+int fhs_client_decrypt_packed_str(const fhs_client *ck, const void *mask16, const void *body16, size_t n_chars,
+                                  char *out, size_t *out_len) {
+    return fhs_client_decrypt_packed_str_at(ck, mask16, body16, 0, n_chars, out, out_len);
 }
 
 }  // extern "C"

@@ -194,6 +194,11 @@ class Engine {
     static constexpr int STORE_MAX_REKEYS = 255;   // FHS_STORE_MAX_REKEYS
     bool planner_rekey_key = false;                // planner only: fhs_load_rekey_key was given a key (nothing is converted)
     int store_rekey(uint64_t id, uint64_t *id_out);
+    // Characters [first_char, first_char + count) of an entry in the windowed packed form, under the
+    // entry's key or, recipient, under the key the context's re-key key leads to: mask16[covering groups][2048],
+    // body16[4 count].  One launch on the context's stream (store_switch16_kernel / rekey_entry_packed_kernel), two copies,
+    // one sync; no pool block, no node, no packing key, and the entry stays as it is.
+    int store_read_packed(uint64_t id, size_t first_char, size_t count, bool recipient, uint16_t *mask16, uint16_t *body16);
     // diagnostic: the kernel on host words of any block count; the outputs may be the inputs
     int debug_rekey(const uint32_t *mask32, const uint32_t *body32, size_t n_blocks, uint32_t *mask_out, uint32_t *body_out);
     // diagnostic: the recipient download's kernel alone on host words, mask64 / body64 [ceil(n_blocks / 2048)][2048]

@@ -586,6 +586,36 @@ int Engine::store_rekey(uint64_t id, uint64_t *id_out) {
     return 0;
 }
 
+int Engine::store_read_packed(uint64_t id, size_t first_char, size_t count, bool recipient, uint16_t *mask16, uint16_t *body16) {
+    const StoreEntry *ent = store_entry(id);
+    if (!ent) return ctx.fail(-1, "string store: unknown entry id");
+    const size_t n_chars = ent->n_blocks / 4;
+    if (first_char > n_chars || count > n_chars - first_char) return ctx.fail(-1, "string store: window outside the entry");
+    if (count == 0) return 0;
+    if (planner) return ctx.fail(-3, "planner context: nothing is computed, there is nothing to download");
+    if (recipient && !ctx.d_rekey_key_ntt) return ctx.fail(-3, "re-key key not loaded (fhs_load_rekey_key)");
+    (void)hipSetDevice(ctx.device);
+    const size_t t0 = 4 * first_char, body_words = 4 * count, g0 = t0 / PACK_GROUP, first_coef = t0 % PACK_GROUP;
+    const size_t groups = (first_coef + body_words + PACK_GROUP - 1) / PACK_GROUP, mask_words = groups * POLY_N;
+    const uint32_t *mask32 = ent->buf.as<uint32_t>(), *body32 = mask32 + ent->groups() * POLY_N;
+    hipError_t e = ctx.pack_out.reserve((mask_words + body_words) * sizeof(uint16_t));
+    uint16_t *d_mask = ctx.pack_out.as<uint16_t>(), *d_body = d_mask + mask_words;
+    if (e == hipSuccess && !recipient)
+        e = launch_store_switch16(mask32 + g0 * POLY_N, body32 + t0, d_mask, d_body, (int)groups, body_words, ctx.stream);
+    if (e == hipSuccess && recipient) {
+        RekeyEntryPackedParams p{};
+        p.src_mask = mask32 + g0 * POLY_N; p.src_body = body32 + g0 * PACK_GROUP; p.dst_mask = d_mask; p.dst_body = d_body;
+        p.first_coef = (uint32_t)first_coef; p.body_words = (uint32_t)body_words; p.groups = (int)groups;
+        p.key_ntt = ctx.d_rekey_key_ntt.as<double>(); p.tw = ctx.tw;
+        e = launch_rekey_entry_packed(p, ctx.stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(mask16, d_mask, mask_words * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(body16, d_body, body_words * sizeof(uint16_t), hipMemcpyDeviceToHost, ctx.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx.stream);
+    if (e != hipSuccess) return ctx.hip_fail(e, "string store: packed download");
+    return 0;
+}
+
 hipError_t Engine::rekey_words(const uint32_t *d_mask, const uint32_t *d_body, uint32_t *d_mask_out, uint32_t *d_body_out,
                                size_t n_blocks) {
     RekeyParams p{};

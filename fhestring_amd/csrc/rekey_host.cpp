@@ -81,6 +81,22 @@ void rekey_packed_group(const uint64_t *key_ntt, const uint64_t *mask64, const u
     for (size_t j = 0; j < count; j++) body_out[j] = store16(body64[j] - ks[N + j]);
 }
 
+// one covering group of the packed download of a parked entry: the entry's 32-bit words are the
+// keyswitch's input as they are; bodies exist for the window's coefficients [lo, hi) of the group only: body32 points at
+// coefficient 0 of the group and is read inside [lo, hi) alone, body_out at the output word of coefficient lo
+void store_packed_group(const uint64_t *key_ntt, const uint32_t *mask32, const uint32_t *body32, size_t lo, size_t hi,
+                        uint16_t *mask_out, uint16_t *body_out) {
+    if (!key_ntt) {                                                  // own key: the storage switch alone
+        for (int n = 0; n < N; n++) mask_out[n] = store16((uint64_t)mask32[n] << 32);
+        for (size_t n = lo; n < hi; n++) body_out[n - lo] = store16((uint64_t)body32[n] << 32);
+        return;
+    }
+    std::vector<uint64_t> ks((size_t)2 * N);
+    keyswitch_sums(key_ntt, mask32, ks.data(), ks.data() + N);
+    for (int n = 0; n < N; n++) mask_out[n] = store16((uint64_t)0 - ks[n]);
+    for (size_t n = lo; n < hi; n++) body_out[n - lo] = store16(((uint64_t)body32[n] << 32) - ks[N + n]);
+}
+
 // the key as residues: [L][mask, body][prime][2048], rounded to the 58-bit grid, 1/N folded in
 std::vector<uint64_t> key_to_ntt(const uint64_t *key) {
     std::vector<uint64_t> key_ntt((size_t)L * 2 * 2 * N);
@@ -117,6 +133,33 @@ int fhs_rekey_packed_host(const uint64_t *key, const uint64_t *mask64, const uin
     parallel_for(groups, host_threads(16), 1, [&](size_t g) {
         const size_t count = std::min<size_t>(FHS_PACK_GROUP, n_blocks - g * FHS_PACK_GROUP);
         rekey_packed_group(key_ntt.data(), mask64 + g * N, body64 + g * N, count, mask16 + g * N, body16 + g * FHS_PACK_GROUP);
+    });
+    return FHS_OK;
+}
+
+void fhs_store_packed_words(size_t first_char, size_t count, size_t *mask_words, size_t *body_words, uint32_t *first_coef) {
+    const size_t t0 = 4 * first_char;
+    if (mask_words) *mask_words = count ? ((t0 + 4 * count - 1) / FHS_PACK_GROUP - t0 / FHS_PACK_GROUP + 1) * (size_t)N : 0;
+    if (body_words) *body_words = 4 * count;
+    if (first_coef) *first_coef = (uint32_t)(t0 % FHS_PACK_GROUP);
+}
+
+int fhs_store_packed_host(const uint64_t *key, const void *mask32_, const void *body32_, size_t n_blocks_entry, size_t first_char,
+                          size_t count, void *mask16_, void *body16_) {
+    const uint32_t *mask32 = static_cast<const uint32_t *>(mask32_), *body32 = static_cast<const uint32_t *>(body32_);
+    uint16_t *mask16 = static_cast<uint16_t *>(mask16_), *body16 = static_cast<uint16_t *>(body16_);
+    const size_t n_chars = n_blocks_entry / 4;
+    if ((n_blocks_entry & 3) || first_char > n_chars || count > n_chars - first_char) return FHS_ERR_ARG;
+    if (count == 0) return FHS_OK;
+    if (!mask32 || !body32 || !mask16 || !body16) return FHS_ERR_ARG;
+    std::vector<uint64_t> key_ntt;
+    if (key) key_ntt = key_to_ntt(key);
+    const size_t t0 = 4 * first_char, t1 = t0 + 4 * count, g0 = t0 / FHS_PACK_GROUP, g1 = (t1 - 1) / FHS_PACK_GROUP;
+    parallel_for(g1 - g0 + 1, host_threads(16), 1, [&](size_t k) {
+        const size_t base = (g0 + k) * FHS_PACK_GROUP;               // the group's coefficient 0 as a block of the entry
+        const size_t lo = std::max(t0, base) - base, hi = std::min<size_t>(t1 - base, FHS_PACK_GROUP);
+        store_packed_group(key ? key_ntt.data() : nullptr, mask32 + (g0 + k) * N, body32 + base, lo, hi, mask16 + k * N,
+                           body16 + (base + lo - t0));
     });
     return FHS_OK;
 }

@@ -11,7 +11,9 @@
 // In place: every wave has read the whole mask before the workgroup barrier and every store comes after it; a body word is
 // read and written by the same lane; groups touch disjoint words.  So dst may be src.
 // rekey_packed_kernel is the same keyswitch between other formats: 64-bit words in, 16-bit words out (DESIGN.md section
-// 16; host reference fhs_rekey_packed_host).  The arithmetic between load and store exists once, in keyswitch_sums.
+// 16; host reference fhs_rekey_packed_host), and rekey_entry_packed_kernel takes a window of a parked entry, 32-bit words,
+// to 16-bit words (section 17; fhs_store_packed_host).  The arithmetic between load and store exists once, in
+// keyswitch_sums.
 #include "ntt_transform.h"
 #include "rekey_kernels.h"
 
@@ -25,7 +27,7 @@ __device__ __forceinline__ uint32_t switch32(uint64_t x) { return (uint32_t)((x 
 __device__ __forceinline__ uint16_t switch16(uint64_t x) { return (uint16_t)((x + (1ull << 47)) >> 48); }
 static_assert(REKEY_LEVELS == 2 && REKEY_BASE_LOG == 16, "the digits are the two 16-bit halves of a 32-bit word");
 
-// The keyswitch between load and store, shared by both kernels: from the group's mask as 32-bit words in the strided
+// The keyswitch between load and store, shared by all three kernels: from the group's mask as 32-bit words in the strided
 // layout (a[r] = word of coefficient lane + 64 r) to ks[o] = (sum_l d_l (*) K[l][j]) of coefficient lane + 64 (2 o + q),
 // the half of output polynomial j that wave (j, q) owns.  Holds the workgroup's one barrier: every wave's loads of `a`
 // are behind it when it returns, so the caller may store over its source.
@@ -155,14 +157,56 @@ __global__ __launch_bounds__(256) void rekey_packed_kernel(RekeyPackedParams P) 
     }
 }
 
+// The packed download of a parked entry for a recipient: the mask is loaded as rekey_glwe_kernel
+// loads it (the stored word has 32 significant bits: nothing is rounded on the way in), the words are stored as
+// rekey_packed_kernel stores them.  Workgroup g takes covering group g of the window; only the window's coefficients of
+// that group have a body -- [lo, hi) is partial in the first and the last covering group -- and a body word is read after
+// the barrier by the lane that stores it.  Source (the entry) and destination are different buffers; the entry is only read.
+__global__ __launch_bounds__(256) void rekey_entry_packed_kernel(RekeyEntryPackedParams P) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const uint32_t grp = blockIdx.x;
+    // the window's coefficient range inside this group (the launcher checked that the last group holds `end - 1`)
+    const uint32_t base = grp * REKEY_GROUP, end = P.first_coef + P.body_words;
+    const uint32_t lo = P.first_coef > base ? P.first_coef - base : 0u;
+    const uint32_t hi = min((uint32_t)REKEY_GROUP, end - base);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int j = wave >> 1, q = wave & 1;
+
+    const uint32_t *src_mask = P.src_mask + (size_t)grp * POLY_N;
+    uint32_t a[32];
+#pragma unroll
+    for (int r = 0; r < 32; r++) a[r] = src_mask[lane + 64 * r];
+
+    uint64_t ks[16];
+    keyswitch_sums(a, P.key_ntt, P.tw, smem, lane, wave, ks);
+
+    if (j == 0) {
+        uint16_t *out = P.dst_mask + (size_t)grp * POLY_N;
+#pragma unroll
+        for (int o = 0; o < 16; o++) out[lane + 64 * (2 * o + q)] = switch16((uint64_t)0 - ks[o]);
+    } else {
+        const uint32_t *in = P.src_body + (size_t)base;
+        uint16_t *out = P.dst_body;
+#pragma unroll
+        for (int o = 0; o < 16; o++) {
+            const uint32_t n = lane + 64 * (2 * o + q);
+            if (lo <= n && n < hi) out[base + n - P.first_coef] = switch16(((uint64_t)in[n] << 32) - ks[o]);
+        }
+    }
+}
+
 static size_t rekey_lds_bytes() { return (size_t)4 * LDS_WAVE_SLOTS * sizeof(double); }
 
 hipError_t prepare_device_for_rekey() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rekey_glwe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                        (int)rekey_lds_bytes());
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void *>(rekey_packed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)rekey_lds_bytes());
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(rekey_packed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)rekey_lds_bytes());
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void *>(rekey_entry_packed_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)rekey_lds_bytes());
 }
 
 hipError_t launch_rekey_glwe(const RekeyParams &p, hipStream_t s) {
@@ -179,6 +223,16 @@ hipError_t launch_rekey_packed(const RekeyPackedParams &p, hipStream_t s) {
     if ((size_t)p.total > (size_t)p.groups * REKEY_GROUP || (size_t)p.total <= (size_t)(p.groups - 1) * REKEY_GROUP)
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(rekey_packed_kernel, dim3(p.groups), dim3(256), rekey_lds_bytes(), s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_rekey_entry_packed(const RekeyEntryPackedParams &p, hipStream_t s) {
+    if (p.groups <= 0 || p.body_words == 0 || !p.src_mask || !p.src_body || !p.dst_mask || !p.dst_body || !p.key_ntt)
+        return hipErrorInvalidValue;
+    const size_t end = (size_t)p.first_coef + p.body_words;          // the last covering group holds its last coefficient
+    if (p.first_coef >= (uint32_t)REKEY_GROUP || end > (size_t)p.groups * REKEY_GROUP || end <= (size_t)(p.groups - 1) * REKEY_GROUP)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rekey_entry_packed_kernel, dim3(p.groups), dim3(256), rekey_lds_bytes(), s, p);
     return hipGetLastError();
 }
 

@@ -20,6 +20,8 @@ KERNEL_SOURCES = {
     "pack_level_kernel": ["pack_kernels.hip", "pack_kernels.h"] + _NTT,
     "rekey_glwe_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _NTT,
     "rekey_packed_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _NTT,
+    "rekey_entry_packed_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _NTT,
+    "store_switch16_kernel": ["store_kernels.hip", "store_kernels.h", FLAGS],
     "pack_switch16_kernel": ["pack_kernels.hip", "pack_kernels.h", FLAGS],
     "keyswitch_mfma_kernel": ["ks_kernels.hip", FLAGS],
     "keyswitch_mfma2_kernel": ["ks_kernels.hip", FLAGS],

@@ -611,6 +611,14 @@ int fhs_client_decrypt_packed_str(const fhs_client *ck, const void *mask16, cons
 /* ... and every block's value mod 32 (message and carry bits, padding bit included), out[n_blocks]. */
 int fhs_client_decrypt_packed_blocks(const fhs_client *ck, const void *mask16, const void *body16, size_t n_blocks,
                                      uint8_t *out);
+/* The same two on a WINDOWED packed form ("packed download of parked entries" below): block i is coefficient
+ * (first_coef + i) % 2048 of mask (first_coef + i) / 2048, mask16[ceil((first_coef + n_blocks) / 2048)][2048],
+ * body16[n_blocks].  first_coef = 0 is the form above and the two functions above are that case.  FHS_ERR_ARG unless
+ * first_coef is a multiple of 4 below 2048. */
+int fhs_client_decrypt_packed_str_at(const fhs_client *ck, const void *mask16, const void *body16, uint32_t first_coef,
+                                     size_t n_chars, char *out, size_t *out_len);
+int fhs_client_decrypt_packed_blocks_at(const fhs_client *ck, const void *mask16, const void *body16, uint32_t first_coef,
+                                        size_t n_blocks, uint8_t *out);
 
 /* ---- public-key encryption: compact strings expanded on the GPU --------------------------------------------
  * Anyone who holds the client's PUBLIC key can encrypt a string this library computes on (the reference hands one out:
@@ -801,6 +809,41 @@ int fhs_rekey_packed_host(const uint64_t *key, const uint64_t *mask64, const uin
  * fhs_rekey_packed_host.  FHS_ERR_STATE without a re-key key or on a planner context. */
 int fhs_debug_rekey_packed_device(fhs_ctx *ctx, const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, void *mask16,
                                   void *body16);
+
+/* ---- string store: packed download of parked entries, own or recipient key -----------------------------------
+ * An entry already IS the output of the packing tree, one GLWE per 2048 blocks at 32 bits per word, so it leaves the
+ * server without being expanded: its words are rounded to 16 bits -- through the re-key keyswitch on the way when a
+ * recipient is to open it -- and 17 B per character cross the bus.  No pool block, no packing key,
+ * no tree; the entry, its re-key counter and every figure stay as they are.
+ * WINDOWED PACKED FORM of characters [first_char, first_char + count): the blocks are t0 = 4 first_char .. t0 + 4 count - 1;
+ * with g0 = t0 / 2048 and g1 = (t0 + 4 count - 1) / 2048,
+ *   mask16[g1 - g0 + 1][2048]: the masks of the covering groups;   body16[4 count]: the bodies of the window's blocks only;
+ *   first_coef = t0 % 2048 (a multiple of 4): block i of the window is coefficient (first_coef + i) % 2048 of mask
+ *   (first_coef + i) / 2048.
+ * With first_char = 0 this is the layout of fhs_download_string_packed word for word.  A recipient who is handed a window
+ * holds the masks of whole groups but the bodies of the window alone: the other rows of a table parked as one entry stay
+ * closed to them.  Arithmetic, exact in wrapping 64-bit words, on w = the entry's 32-bit word:
+ *   own key:    every word ((w + 2^15) >> 16) & 0xffff = fhs_pack_switch16 of w << 32 (a carry out of the top wraps to 0);
+ *   recipient:  per covering group the keyswitch of fhs_store_rekey (the digits of mask32 are exact),
+ *               mask16 = ((-Sum_mask + 2^47) >> 48) & 0xffff,  body16_j = (((body32_j << 32) - Sum_body,j + 2^47) >> 48) & 0xffff
+ *               for the window's coefficients j of that group = fhs_rekey_packed_host of (mask32 << 32, body32 << 32).
+ * Noise: the 16-bit rounding, sigma ~ 2^51.2, dominates as in every packed download; the entry's own 2^43.1 (after put)
+ * or 2^35.2 (a public-key import) and the keyswitch's 2^32.6 disappear under it.  As everywhere, a context cannot tell
+ * which key an entry is under: a recipient download of an entry that is not under the `from` key of the loaded re-key
+ * key gives garbage without any error. */
+/* u16 words of mask and body of the window and its first_coef (any of the three may be NULL); count = 0: no words. */
+void fhs_store_packed_words(size_t first_char, size_t count, size_t *mask_words, size_t *body_words, uint32_t *first_coef);
+/* One kernel launch on the context's stream, behind every queued fhs_store_get / fhs_store_rekey of the entry, two
+ * device-to-host copies, one stream sync.  recipient != 0: under the key the loaded re-key key leads to.  FHS_ERR_ARG: unknown
+ * id or a window outside the entry.  count = 0 returns 0 and writes nothing.  FHS_ERR_STATE: a planner context (it holds
+ * no ciphertext), or recipient without a re-key key.  A packing key is NOT required. */
+int fhs_store_download_packed(fhs_ctx *ctx, uint64_t id, size_t first_char, size_t count, int recipient, void *mask16,
+                              void *body16);
+/* Host reference (public data only, no GPU): the same words as the device.  mask32 / body32: the WHOLE entry as
+ * fhs_store_export gives it, n_blocks_entry = 4 x its characters; rekey_key == NULL: the entry's own key.  mask16 / body16
+ * sized by fhs_store_packed_words; no word outside them is written.  FHS_ERR_ARG for a window outside the entry. */
+int fhs_store_packed_host(const uint64_t *rekey_key /*[FHS_REKEY_KEY_WORDS], or NULL*/, const void *mask32, const void *body32,
+                          size_t n_blocks_entry, size_t first_char, size_t count, void *mask16, void *body16);
 
 #ifdef __cplusplus
 }

@@ -87,6 +87,23 @@ int main() {
                       !std::memcmp(all.data(), text.data(), 515));
                 CHECK(fhs_rekey_packed_host(rk.data(), nullptr, nullptr, 4, nullptr, nullptr) == FHS_ERR_ARG);
             }
+            {   // ... and a window across its two groups as the packed download of a parked entry, own key and for that
+                // client (fhs_store_packed_host): output arrays of exactly the window's size
+                size_t wmw = 0, wbw = 0;
+                uint32_t fc = 0;
+                fhs_store_packed_words(511, 6, &wmw, &wbw, &fc);
+                CHECK(wmw == 2 * 2048 && wbw == 24 && fc == 2044);
+                std::vector<uint16_t> m16(wmw), b16(wbw);
+                char w[8];
+                CHECK(fhs_store_packed_host(nullptr, m32.data(), b32.data(), bw, 511, 6, m16.data(), b16.data()) == FHS_OK);
+                CHECK(fhs_client_decrypt_packed_str_at(ck, m16.data(), b16.data(), fc, 6, w, &pn) == FHS_OK && pn == 4 &&
+                      !std::memcmp(w, text.data() + 511, 4));
+                CHECK(fhs_store_packed_host(rk.data(), m32.data(), b32.data(), bw, 511, 6, m16.data(), b16.data()) == FHS_OK);
+                CHECK(fhs_client_decrypt_packed_str_at(to, m16.data(), b16.data(), fc, 6, w, &pn) == FHS_OK && pn == 4 &&
+                      !std::memcmp(w, text.data() + 511, 4));
+                CHECK(fhs_store_packed_host(nullptr, m32.data(), b32.data(), bw, 512, 6, m16.data(), b16.data()) == FHS_ERR_ARG);
+                CHECK(fhs_client_decrypt_packed_str_at(ck, m16.data(), b16.data(), 2, 6, w, &pn) == FHS_ERR_ARG);
+            }
             CHECK(fhs_rekey_host(rk.data(), m32.data(), b32.data(), bw, m32.data(), b32.data()) == FHS_OK);
             CHECK(fhs_expand_public_str(m32.data(), b32.data(), 517, 507, 10, win.data()) == FHS_OK);
             CHECK(fhs_client_decrypt_str(to, win.data(), 10, pbuf, &pn) == FHS_OK && pn == 8 && !std::memcmp(pbuf, "ssssssss", 8));
