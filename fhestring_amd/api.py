@@ -19,6 +19,11 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _coded(err, code):
+    err.code = code
+    return err
+
+
 class Context:
     """fhs_ctx: one per GPU.  Replaces the tfhe::integer::ServerKey held by
     MyServerKey (src/server_key/mod.rs:13-16)."""
@@ -53,9 +58,9 @@ class Context:
 
     def _check(self, rc):
         if rc != 0:
-            err = FhsError("fhs error %d: %s" % (rc, self._L.fhs_last_error(self._h).decode()))
-            err.code = rc
-            raise err
+            # raised without a local name for it: a frame that holds its own exception closes a cycle through the
+            # traceback, and the handles the failed call was given would then live until the next garbage collection
+            raise _coded(FhsError("fhs error %d: %s" % (rc, self._L.fhs_last_error(self._h).decode())), rc)
 
     ARITH_EXACT_NTT = _K["FHS_ARITH_EXACT_NTT"]
     ARITH_F64_FFT = _K["FHS_ARITH_F64_FFT"]
@@ -907,6 +912,7 @@ def store_packed_host(key, compact, first_char=0, count=None):
 
 STORE_MAX_CYCLES = _K["FHS_STORE_MAX_CYCLES"]
 STORE_MAX_REKEYS = _K["FHS_STORE_MAX_REKEYS"]
+TRIM_RELEASE, TRIM_COMPACT = _K["FHS_TRIM_RELEASE"], _K["FHS_TRIM_COMPACT"]
 STORE_META_MAGIC = b"FHSSMET1"
 
 
@@ -1210,6 +1216,23 @@ class MyServerKey:
         e, n, b = C.c_size_t(), C.c_size_t(), C.c_size_t()
         self.ctx._check(self.ctx._L.fhs_store_stats(self.ctx._h, C.byref(e), C.byref(n), C.byref(b)))
         return {"entries": int(e.value), "chars": int(n.value), "device_bytes": int(b.value)}
+
+    # ---- block pool ------------------------------------------------------------
+    def pool_stats(self):
+        """fhs_pool_stats -> dict(chunks, blocks_per_chunk, live, free, free_pending, device_bytes)."""
+        out = (C.c_uint64 * 6)()
+        self.ctx._check(self.ctx._L.fhs_pool_stats(self.ctx._h, out))
+        return dict(zip(("chunks", "blocks_per_chunk", "live", "free", "free_pending", "device_bytes"), map(int, out)))
+
+    def pool_trim(self, compact=True, keep_free_blocks=0):
+        """fhs_pool_trim (not `trim`: that is the string operation of trim.rs): flush, then give back the chunks of the
+        block pool that the live blocks and keep_free_blocks more do not need; compact=True first moves the live blocks
+        of the emptiest chunks together on the GPU (FHS_TRIM_COMPACT), compact=False only releases chunks that are
+        already empty (FHS_TRIM_RELEASE).  -> dict(blocks_moved, bytes_released)."""
+        moved, released = C.c_uint64(), C.c_uint64()
+        self.ctx._check(self.ctx._L.fhs_pool_trim(self.ctx._h, TRIM_COMPACT if compact else TRIM_RELEASE,
+                                                  int(keep_free_blocks), C.byref(moved), C.byref(released)))
+        return {"blocks_moved": int(moved.value), "bytes_released": int(released.value)}
 
     def import_device(self, d_ptr):
         return FheAsciiChar(self, self.ctx._L.fhs_import_device(self.ctx._h, C.c_void_p(d_ptr)))

@@ -274,6 +274,24 @@ int fhs_store_import(fhs_ctx *c, const void *mask32, const void *body32, const u
     if (n > ((size_t)1 << 24) || (n && (!mask32 || !body32))) return bad(c);
     return c->eng.store_import(static_cast<const uint32_t *>(mask32), static_cast<const uint32_t *>(body32), meta, 4 * n, id_out);
 }
+// ---- block pool: accounting and trimming ----
+int fhs_pool_stats(fhs_ctx *c, uint64_t out[6]) {
+    if (!c || !out) return bad(c);
+    c->eng.pool_stats(out);
+    return FHS_OK;
+}
+int fhs_pool_trim(fhs_ctx *c, int mode, size_t keep_free_blocks, uint64_t *blocks_moved, uint64_t *bytes_released) {
+    if (!c || (mode != FHS_TRIM_RELEASE && mode != FHS_TRIM_COMPACT)) return bad(c);
+    return c->eng.pool_trim(mode == FHS_TRIM_COMPACT, keep_free_blocks, blocks_moved, bytes_released);
+}
+int fhs_debug_pool_plan(const uint32_t *live_per_chunk, size_t n_chunks, size_t keep_free_blocks, uint8_t *victim_out) {
+    if (n_chunks && (!live_per_chunk || !victim_out)) return FHS_ERR_ARG;
+    if (n_chunks > ((size_t)1 << 24)) return FHS_ERR_ARG;
+    for (size_t i = 0; i < n_chunks; i++)
+        if (live_per_chunk[i] > BlockPool::CHUNK_BLOCKS) return FHS_ERR_ARG;
+    BlockPool::plan_trim(live_per_chunk, n_chunks, keep_free_blocks, victim_out);
+    return FHS_OK;
+}
 int fhs_load_packing_key_file(fhs_ctx *c, const char *path) {
     if (!c || !path) return FHS_ERR_ARG;
     std::vector<uint64_t> key;

@@ -40,6 +40,66 @@ void BlockPool::tick_enqueued(uint64_t tick) {
     }
 }
 
+void BlockPool::stats(uint64_t out[6]) const {
+    uint64_t waiting = 0;
+    for (const auto &kv : free_after_) waiting += kv.second.size();
+    out[0] = chunks_.size();
+    out[1] = CHUNK_BLOCKS;
+    out[2] = live_;
+    out[3] = free_.size();
+    out[4] = waiting;
+    out[5] = chunks_.size() * CHUNK_BYTES;
+}
+
+void BlockPool::plan_trim(const uint32_t *live_per_chunk, size_t n_chunks, size_t keep_free_blocks, uint8_t *victim) {
+    uint64_t live = 0;
+    for (size_t i = 0; i < n_chunks; i++) { live += live_per_chunk[i]; victim[i] = 0; }
+    // (a reserve beyond what the chunks could hold keeps them all: no sum that could wrap)
+    if (keep_free_blocks >= n_chunks * CHUNK_BLOCKS) return;
+    const size_t keep = (size_t)((live + keep_free_blocks + CHUNK_BLOCKS - 1) / CHUNK_BLOCKS);
+    if (keep >= n_chunks) return;
+    std::vector<uint32_t> order(n_chunks);
+    for (size_t i = 0; i < n_chunks; i++) order[i] = (uint32_t)i;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        return live_per_chunk[a] != live_per_chunk[b] ? live_per_chunk[a] < live_per_chunk[b] : a > b;
+    });
+    for (size_t k = 0; k < n_chunks - keep; k++) victim[order[k]] = 1;
+}
+
+bool BlockPool::locate(uint64_t *const *p, size_t n, uint32_t *chunk, uint32_t *slot) const {
+    std::vector<std::pair<uintptr_t, uint32_t>> bases(chunks_.size());   // the chunks by address
+    for (size_t i = 0; i < chunks_.size(); i++) bases[i] = {(uintptr_t)chunks_[i].ptr, (uint32_t)i};
+    std::sort(bases.begin(), bases.end());
+    for (size_t k = 0; k < n; k++) {
+        const uintptr_t a = (uintptr_t)p[k];
+        auto it = std::upper_bound(bases.begin(), bases.end(), std::make_pair(a, ~(uint32_t)0));
+        if (it == bases.begin()) return false;
+        --it;
+        const uintptr_t off = a - it->first;
+        if (off >= CHUNK_BYTES || off % (STRIDE * 8)) return false;
+        chunk[k] = it->second;
+        slot[k] = (uint32_t)(off / (STRIDE * 8));
+    }
+    return true;
+}
+
+uint64_t BlockPool::release(const std::vector<uint8_t> &victim, const std::vector<uint8_t> &used) {
+    std::vector<uint32_t> chunk(free_.size()), slot(free_.size());
+    if (!locate(free_.data(), free_.size(), chunk.data(), slot.data())) return 0;
+    size_t kept = 0;
+    for (size_t k = 0; k < free_.size(); k++)
+        if (!victim[chunk[k]] && !used[chunk[k] * CHUNK_BLOCKS + slot[k]]) free_[kept++] = free_[k];
+    free_.resize(kept);
+    uint64_t bytes = 0;
+    std::vector<DevBuf> rest;
+    for (size_t i = 0; i < chunks_.size(); i++) {
+        if (victim[i]) bytes += CHUNK_BYTES;                  // (its DevBuf dies with the old vector)
+        else rest.push_back(std::move(chunks_[i]));
+    }
+    chunks_.swap(rest);
+    return bytes;
+}
+
 Bid Engine::new_node() {
     Bid id;
     if (!free_nodes_.empty()) {

@@ -206,6 +206,14 @@ class Engine {
     // flushes if needed (do_flush = false: the caller has made sure the block's tick is enqueued); wait=false: enqueue only
     int copy_block_to_device(Bid b, uint64_t *d_out, bool wait = true, bool do_flush = true);
     uint64_t blocks_live() const { return pool_.live(); }
+    // ---- block pool: accounting and trimming ----
+    void pool_stats(uint64_t out[6]) const { pool_.stats(out); }
+    // Flushes, then gives back the chunks the pool does not need for its live blocks and `keep_free_blocks` more
+    // (BlockPool::plan_trim).  compact: the live blocks of the victims first move into free slots of the kept chunks
+    // (pool_move_blocks_kernel, passes of up to POOL_MOVE_MAX_BATCH blocks, only the pointer tables cross the bus) and
+    // their nodes get the new address; otherwise only victims that hold no live block go.  A planner only flushes.
+    static constexpr size_t POOL_MOVE_MAX_BATCH = 2048;   // blocks per launch: one chunk's worth, 33.6 MB
+    int pool_trim(bool compact, size_t keep_free_blocks, uint64_t *blocks_moved, uint64_t *bytes_released);
 
     // ---- debug: capture of PBS inputs (the linear-combination results entering keyswitch) ----
     // Noise-margin tests download a sample of every level's inputs and measure their phase error with the client

@@ -682,6 +682,84 @@ int Engine::debug_rekey(const uint32_t *mask32, const uint32_t *body32, size_t n
     return 0;
 }
 
+// ---- block pool: trim ---------------------------------------------------------------------------------------------------
+// After a flush every scheduled tick is in the stream: sched_ is empty, the ticks' accumulator-body blocks are back in
+// the pool and nothing waits in free_after_, so the ONLY owners of pool pointers are the `dev` of the MAT nodes (checked
+// below: their number is the pool's live count).  Levels waiting in planned_ hold more (out / body / term pointers): the
+// call is refused while they exist, before the flush, which in capture mode would discard them.
+int Engine::pool_trim(bool compact, size_t keep_free_blocks, uint64_t *blocks_moved, uint64_t *bytes_released) {
+    if (blocks_moved) *blocks_moved = 0;
+    if (bytes_released) *bytes_released = 0;
+    if (!planned_.empty())
+        return ctx.fail(-3, "block pool: levels planned by fhs_flush_plan are waiting for fhs_flush_level_commit");
+    if (planner) return flush();
+    (void)hipSetDevice(ctx.device);
+    if (int rc = flush()) return rc;
+    pool_.tick_enqueued(last_sched_tick_);                           // (nothing is scheduled any more)
+    const size_t C = pool_.n_chunks(), CB = BlockPool::CHUNK_BLOCKS;
+    if (C == 0) return 0;
+    std::vector<Bid> owner;
+    std::vector<uint64_t *> ptr;
+    for (Bid id = 1; id < nodes_.size(); id++)
+        if (nodes_[id].kind == BlockNode::MAT && nodes_[id].dev) { owner.push_back(id); ptr.push_back(nodes_[id].dev); }
+    std::vector<uint32_t> chunk(ptr.size()), slot(ptr.size());
+    uint64_t st[6];
+    pool_.stats(st);
+    if (ptr.size() != pool_.live() || st[4] != 0 || !pool_.locate(ptr.data(), ptr.size(), chunk.data(), slot.data()))
+        return ctx.fail(-3, "internal: the node table does not own every live pool block after a flush");
+    std::vector<uint32_t> live_per_chunk(C, 0);
+    std::vector<uint8_t> used(C * CB, 0), victim(C, 0);
+    for (size_t k = 0; k < ptr.size(); k++) { live_per_chunk[chunk[k]]++; used[chunk[k] * CB + slot[k]] = 1; }
+    BlockPool::plan_trim(live_per_chunk.data(), C, keep_free_blocks, victim.data());
+    if (!compact)
+        for (size_t c = 0; c < C; c++)
+            if (live_per_chunk[c]) victim[c] = 0;
+    if (std::find(victim.begin(), victim.end(), 1) == victim.end()) return 0;
+    // The moves.  Sources are live slots of victims, destinations free slots of kept chunks, first fit in chunk and slot
+    // order: the two sets are disjoint and every destination is taken once, so neither the order of the rows inside a
+    // launch nor that of the launches matters.  The kept chunks have room: 2048 K >= live + keep_free_blocks.
+    std::vector<size_t> moving;                                      // indices into owner / ptr
+    for (size_t k = 0; k < ptr.size(); k++)
+        if (victim[chunk[k]]) moving.push_back(k);
+    std::vector<uint64_t *> dest(moving.size());
+    {
+        size_t at = 0;
+        for (size_t m = 0; m < moving.size(); m++) {
+            while (at < C * CB && (victim[at / CB] || used[at])) at++;
+            if (at == C * CB) return ctx.fail(-3, "internal: block pool: no free slot for a moved block");
+            used[at] = 1;
+            dest[m] = pool_.slot_ptr(at / CB, at % CB);
+        }
+    }
+    for (size_t done = 0, n; done < moving.size(); done += n) {
+        n = std::min(POOL_MOVE_MAX_BATCH, moving.size() - done);
+        size_t at = 0;
+        if (!xfer_.begin_table_pass(2 * n, at, ctx.stream)) return ctx.fail(-2, "block pool: no transfer buffer for the move tables");
+        uint64_t *tab = xfer_.pin() + at;
+        for (size_t k = 0; k < n; k++) {
+            tab[k] = (uint64_t)(uintptr_t)ptr[moving[done + k]];
+            tab[n + k] = (uint64_t)(uintptr_t)dest[done + k];
+        }
+        hipError_t e = xfer_.copy_up(at, 2 * n, ctx.stream);
+        if (e == hipSuccess)
+            e = launch_pool_move_blocks(reinterpret_cast<const uint64_t *const *>(xfer_.dev() + at),
+                                        reinterpret_cast<uint64_t *const *>(xfer_.dev() + at + n), (int)n, ctx.stream);
+        if (e != hipSuccess) {                                       // nothing was rewritten: the copies made so far are
+            (void)hipStreamSynchronize(ctx.stream);                  // garbage in free slots
+            return ctx.hip_fail(e, "block pool: move");
+        }
+    }
+    // in this order: the stream has finished (the moves, and every queued reader of a victim), the nodes point at the
+    // copies, the free list forgets the victims' slots and the destinations, the victims' allocations go
+    hipError_t e = hipStreamSynchronize(ctx.stream);
+    if (e != hipSuccess) return ctx.hip_fail(e, "block pool: trim");
+    for (size_t m = 0; m < moving.size(); m++) nodes_[owner[moving[m]]].dev = dest[m];
+    const uint64_t bytes = pool_.release(victim, used);
+    if (blocks_moved) *blocks_moved = moving.size();
+    if (bytes_released) *bytes_released = bytes;
+    return 0;
+}
+
 int Engine::copy_block_to_device(Bid b, uint64_t *d_out, bool wait, bool do_flush) {
     if (planner) return ctx.fail(-3, "planner context: nothing is computed");
     (void)hipSetDevice(ctx.device);

@@ -36,8 +36,25 @@ class BlockPool {
     void tick_enqueued(uint64_t tick);                   // blocks freed while ticks <= `tick` were pending are reusable now
     uint64_t live() const { return live_; }
 
-  private:
     static constexpr size_t STRIDE = 2050, CHUNK_BLOCKS = 2048;   // u64 words per block, blocks per hipMalloc
+    static constexpr size_t CHUNK_BYTES = CHUNK_BLOCKS * STRIDE * 8;
+    // ---- accounting and trimming (fhs_pool_stats / fhs_pool_trim) ----
+    // [chunks, CHUNK_BLOCKS, live, free, freed under a scheduled tick and not reusable yet, device bytes of the chunks];
+    // a planner holds no chunk: [0, CHUNK_BLOCKS, live, 0, 0, 0]
+    void stats(uint64_t out[6]) const;
+    // The victim choice, a pure function of the occupancies: the pool keeps K = ceil((live + keep_free_blocks) / 2048)
+    // chunks, the victims are the n_chunks - K chunks with the fewest live blocks, ties going to the chunk allocated last.
+    static void plan_trim(const uint32_t *live_per_chunk, size_t n_chunks, size_t keep_free_blocks, uint8_t *victim);
+    size_t n_chunks() const { return chunks_.size(); }
+    uint64_t *slot_ptr(size_t chunk, size_t slot) const { return chunks_[chunk].as<uint64_t>() + slot * STRIDE; }
+    // chunk (in allocation order) and slot of every pointer; false: one of them is no block of this pool
+    bool locate(uint64_t *const *p, size_t n, uint32_t *chunk, uint32_t *slot) const;
+    // Gives the victims back: free_ loses their slots and the slots marked in used[chunk * CHUNK_BLOCKS + slot] (the
+    // destinations of a compaction) and keeps its order otherwise; then the victims' allocations are destroyed.  The
+    // caller has waited for the stream and no victim holds a live block any more.  -> bytes given back
+    uint64_t release(const std::vector<uint8_t> &victim, const std::vector<uint8_t> &used);
+
+  private:
     bool grow();
     const bool &planner_;
     std::vector<DevBuf> chunks_;

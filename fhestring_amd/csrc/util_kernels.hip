@@ -19,4 +19,35 @@ hipError_t launch_gather_rows(const uint64_t *const *d_src, uint64_t *d_out, int
     return hipGetLastError();
 }
 
+// Pool compaction (fhs_pool_trim): workgroup g copies pool row src[g] to pool row dst[g].  A pool
+// row is POOL_ROW_WORDS = 2050 words = 1025 pieces of 16 bytes on a 16-byte boundary, so every lane moves whole pieces
+// (global_load_dwordx4 / global_store_dwordx4: 1 KiB contiguous per wavefront instruction): four per lane, all four
+// loads in flight before the first store, and piece 1024 -- the body word, index 2048, with the padding word behind
+// it -- by lane 0.  Sources and destinations are disjoint sets of rows (the caller's invariant): no ordering inside a
+// launch matters.
+static_assert(POOL_ROW_WORDS * 8 == (4 * 256 + 1) * 16, "a pool row is 4 pieces per lane and the tail piece");
+__global__ __launch_bounds__(256) void pool_move_blocks_kernel(const uint64_t *const *__restrict__ src,
+                                                               uint64_t *const *__restrict__ dst) {
+    // (pointers read from a table are generic to the compiler: as global pointers they take global_* instead of flat_*)
+    typedef uint32_t piece_t __attribute__((ext_vector_type(4)));
+    typedef const __attribute__((address_space(1))) piece_t *gsrc_t;
+    typedef __attribute__((address_space(1))) piece_t *gdst_t;
+    const gsrc_t s = (gsrc_t)src[blockIdx.x];
+    const gdst_t d = (gdst_t)dst[blockIdx.x];
+    const int t = threadIdx.x;
+    const piece_t p0 = s[t], p1 = s[t + 256], p2 = s[t + 512], p3 = s[t + 768];
+    piece_t tail = {0, 0, 0, 0};
+    if (t == 0) tail = s[1024];
+    d[t] = p0;
+    d[t + 256] = p1;
+    d[t + 512] = p2;
+    d[t + 768] = p3;
+    if (t == 0) d[1024] = tail;
+}
+hipError_t launch_pool_move_blocks(const uint64_t *const *d_src, uint64_t *const *d_dst, int n, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pool_move_blocks_kernel, dim3(n), dim3(256), 0, s, d_src, d_dst);
+    return hipGetLastError();
+}
+
 }  // namespace fhs

@@ -845,6 +845,36 @@ int fhs_store_download_packed(fhs_ctx *ctx, uint64_t id, size_t first_char, size
 int fhs_store_packed_host(const uint64_t *rekey_key /*[FHS_REKEY_KEY_WORDS], or NULL*/, const void *mask32, const void *body32,
                           size_t n_blocks_entry, size_t first_char, size_t count, void *mask16, void *body16);
 
+/* ---- block pool: what it holds, and giving it back ---------------------------------------------------------
+ * Ciphertext blocks are carved from chunks of 2048 blocks (2048 x 2050 x 8 = 33 587 200 B each).  A released block goes
+ * back to the context's free list, its chunk stays: without a trim a context sits on the high-water mark of its blocks
+ * until it is destroyed, however little of it is live (a parked 4097-character string: 268 MB held for 139 KB in use).
+ * Nothing below happens unless it is called; allocation order and results are otherwise unchanged.
+ * A planner context holds no chunk: stats report the live blocks and zeros for chunks, free blocks and bytes, and a trim
+ * flushes, moves nothing and releases nothing. */
+/* out[0] chunks held, out[1] blocks per chunk (2048), out[2] live blocks, out[3] free blocks (reusable now),
+ * out[4] blocks freed under a scheduled tick and not reusable yet, out[5] device bytes of the chunks */
+int fhs_pool_stats(fhs_ctx *ctx, uint64_t out[6]);
+/* fhs_pool_trim flushes first, as every download does (all scheduled ticks of fhs_submit are drained), and then keeps
+ * K = ceil((live + keep_free_blocks) / 2048) chunks: keep_free_blocks is the room left for the next request without a
+ * new allocation.  FHS_TRIM_RELEASE gives back chunks that hold no live block, as many as exceed K.  FHS_TRIM_COMPACT
+ * takes as victims the (chunks - K) chunks with the fewest live blocks -- ties go to the chunk allocated last -- copies
+ * every live block of a victim into a free slot of a kept chunk on the GPU (one kernel launch per 2048 blocks; only
+ * the pointer tables cross the bus), waits for the stream and gives the victims back.  A moved block is the same block
+ * at another address: handles, figures, rotation groups and packing counts are untouched.  *blocks_moved /
+ * *bytes_released (either may be NULL) receive what was done; a trim with nothing to give back is not an error.
+ * FHS_ERR_ARG: a null context or an unknown mode.  FHS_ERR_STATE: levels planned by fhs_flush_plan are still waiting for
+ * fhs_flush_level_commit (nothing is flushed or changed), or the flush itself failed.  In level-parallel mode the flush
+ * is collective: every rank trims at the same point or none does. */
+#define FHS_TRIM_RELEASE 0   /* give back the chunks that hold no live block; moves nothing */
+#define FHS_TRIM_COMPACT 1   /* first move live blocks out of the emptiest chunks, then release */
+int fhs_pool_trim(fhs_ctx *ctx, int mode, size_t keep_free_blocks, uint64_t *blocks_moved /*may be NULL*/,
+                  uint64_t *bytes_released /*may be NULL*/);
+/* The victim choice of FHS_TRIM_COMPACT alone, a pure host function: live_per_chunk[n_chunks] in allocation order (each
+ * <= 2048, else FHS_ERR_ARG) -> victim_out[i] = 1 for the chunks a compacting trim would give back, 0 for the kept. */
+int fhs_debug_pool_plan(const uint32_t *live_per_chunk, size_t n_chunks, size_t keep_free_blocks,
+                        uint8_t *victim_out /*[n_chunks]*/);
+
 #ifdef __cplusplus
 }
 #endif

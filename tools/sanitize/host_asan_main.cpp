@@ -399,6 +399,7 @@ int main() {
         CHECK(fhs_flush_plan(c, &n_levels, &max_w) == FHS_OK && n_levels > 5 && max_w > 0);
         fhs_stats before, after;
         CHECK(fhs_get_stats(c, &before) == FHS_OK);
+        CHECK(fhs_pool_trim(c, FHS_TRIM_COMPACT, 0, nullptr, nullptr) == FHS_ERR_STATE);   // planned levels are waiting
         for (uint64_t k = 0; k < n_levels; k++) {
             uint64_t width = 0, cap = 0;
             CHECK(fhs_flush_level_exec(c, k, slice, &width, &cap) == FHS_OK && width <= max_w && cap == (width + 1) / 2);
@@ -418,6 +419,18 @@ int main() {
     fhs_dist_plan_windows(257, 4, 8, 7, &w0, &w1, &c0, &c1);
     CHECK(w1 == 254 && c1 == 257);
     CHECK(fhs_str_find(c, nullptr, 3, nullptr, 0, nullptr) != FHS_OK);   // argument errors do not crash
+    {   // block pool: a planner holds no chunk and trims nothing; the victim choice on the host
+        uint64_t ps[6] = {9, 9, 9, 9, 9, 9}, moved = 9, released = 9;
+        CHECK(fhs_pool_stats(c, ps) == FHS_OK && ps[0] == 0 && ps[1] == 2048 && ps[2] == st.blocks_live && ps[3] == 0 &&
+              ps[4] == 0 && ps[5] == 0);
+        CHECK(fhs_pool_trim(c, FHS_TRIM_COMPACT, 0, &moved, &released) == FHS_OK && moved == 0 && released == 0);
+        CHECK(fhs_pool_trim(c, FHS_TRIM_RELEASE, 7, nullptr, nullptr) == FHS_OK && fhs_pool_trim(c, 2, 0, nullptr, nullptr) == FHS_ERR_ARG);
+        const uint32_t live[4] = {2048, 1, 0, 7}, over[1] = {2049};
+        uint8_t victim[4] = {9, 9, 9, 9};
+        CHECK(fhs_debug_pool_plan(live, 4, 0, victim) == FHS_OK && !victim[0] && victim[1] && victim[2] && !victim[3]);
+        CHECK(fhs_debug_pool_plan(live, 4, ~(size_t)0, victim) == FHS_OK && !victim[1] && !victim[2]);
+        CHECK(fhs_debug_pool_plan(over, 1, 0, victim) == FHS_ERR_ARG && fhs_debug_pool_plan(nullptr, 0, 0, nullptr) == FHS_OK);
+    }
     fhs_ctx_destroy(c);
     {   // a planner destroyed with work outstanding: submitted but unpumped jobs, one store entry, live char handles --
         // nothing is released by hand, every owner and container goes with the context (the leak checker watches)
