@@ -1445,6 +1445,57 @@ class MyServerKey:
         f = self._chars(flags)
         return self._wide("fhs_flags_count_wide", _harr(f), len(f))
 
+    # ---- encrypted positions as operands (the reference only decrypts them) ----
+    # `pos` is an FheAsciiChar (find, rfind, len), an FheU16 (their _wide forms) or a Python int.  The buffer is taken as
+    # it is, NULs included; a position past its end -- an absent one among them -- selects nothing.  An int is plain
+    # slicing with trivial NULs: no entry point, no bootstrap.
+    def _pos_op(self, name, s, pos, n_out, count=None):
+        wide = isinstance(pos, FheU16)
+        args = [_harr(s), len(s)] + ([pos.lo.h, pos.hi.h] if wide else [pos.h]) + ([] if count is None else [count])
+        outs = [(C.c_uint64 * max(1, k))() for k in n_out]
+        self.ctx._check(getattr(self.ctx._L, name + ("_wide" if wide else ""))(self.ctx._h, *args, *outs))
+        return [FheString([FheAsciiChar(self, o[i]) for i in range(k)]) for o, k in zip(outs, n_out)]
+
+    def _nuls(self, k):
+        return [self.trivial(0) for _ in range(k)]
+
+    def char_at(self, string, pos):
+        """buf[pos] if pos < len(buf), else NUL."""
+        return self.substr(string, pos, 1)[0] if isinstance(pos, int) else \
+            self._pos_op("fhs_str_char_at", self._chars(string), pos, [1])[0][0]
+
+    def substr(self, string, start, count):
+        """`count` (clear) characters from `start`: buf[start + j] if start + j < len(buf), else NUL."""
+        s = self._chars(string)
+        if isinstance(start, int):
+            part = s[start:start + count] if 0 <= start < len(s) else []
+            return FheString(part + self._nuls(count - len(part)))
+        return self._pos_op("fhs_str_substr", s, start, [count], count)[0]
+
+    def take(self, string, end):
+        """The buffer with everything from `end` on set to NUL (same length)."""
+        s = self._chars(string)
+        if isinstance(end, int):
+            end = max(0, min(end, len(s)))
+            return FheString(s[:end] + self._nuls(len(s) - end))
+        return self._pos_op("fhs_str_take", s, end, [len(s)])[0]
+
+    def skip(self, string, start):
+        """The buffer from `start` on, NULs behind it (same length)."""
+        return self.substr(string, start, len(self._chars(string)))
+
+    def split_at(self, string, pos):
+        """(take(string, pos), skip(string, pos)); the position's bits are taken out once."""
+        s = self._chars(string)
+        if isinstance(pos, int):
+            return self.take(s, pos), self.skip(s, pos)
+        head, tail = self._pos_op("fhs_str_split_at", s, pos, [len(s), len(s)])
+        return head, tail
+
+    def slice(self, string, start, end):
+        """buf[start:end] at the front of a buffer of the same length."""
+        return self.skip(self.take(string, end), start)
+
     def eq(self, string, other, public_parameters=None):                 # mod.rs:1122
         return self._flag_op("eq", string, other)
 

@@ -484,6 +484,96 @@ int fhs_flags_count_wide(fhs_ctx *c, const fhs_char_t *flags, size_t n, fhs_char
     return store_wide(c, S, r, lo, hi);
 }
 
+// ---- encrypted positions as operands: char_at / substr / take / split_at, position a char or a (lo, hi) pair ----
+namespace {
+// an empty operand or an empty request: clear NULs, and the position is not even loaded (loading may record a refresh)
+int store_nuls(fhs_ctx *c, fhs_char_t *out, size_t count) {
+    for (size_t i = 0; i < count; i++) {
+        FChar z = ch_trivial(&c->eng, 0);
+        out[i] = store(c->eng, z);
+    }
+    return FHS_OK;
+}
+}  // namespace
+int fhs_str_char_at(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !ok(c, pos) || !out) return bad(c);
+    if (n == 0) return store_nuls(c, out, 1);
+    Strings S(&c->eng);
+    FChar r = S.char_at(load_str(c->eng, s, n), load(c->eng, pos));
+    if (int rc = finish(c, S)) return rc;
+    *out = store(c->eng, r);
+    return FHS_OK;
+}
+int fhs_str_char_at_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !ok(c, pos_lo) || !ok(c, pos_hi) || !out) return bad(c);
+    if (n == 0) return store_nuls(c, out, 1);
+    Strings S(&c->eng);
+    FChar r = S.char_at(load_str(c->eng, s, n), FWide{load(c->eng, pos_lo), load(c->eng, pos_hi)});
+    if (int rc = finish(c, S)) return rc;
+    *out = store(c->eng, r);
+    return FHS_OK;
+}
+int fhs_str_substr(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, size_t count, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !ok(c, pos) || (count && !out)) return bad(c);
+    if (n == 0 || count == 0) return store_nuls(c, out, count);
+    Strings S(&c->eng);
+    FStr r = S.substr(load_str(c->eng, s, n), load(c->eng, pos), count);
+    if (int rc = finish(c, S)) return rc;
+    store_str(c->eng, r, out);
+    return FHS_OK;
+}
+int fhs_str_substr_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, size_t count,
+                        fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !ok(c, pos_lo) || !ok(c, pos_hi) || (count && !out)) return bad(c);
+    if (n == 0 || count == 0) return store_nuls(c, out, count);
+    Strings S(&c->eng);
+    FStr r = S.substr(load_str(c->eng, s, n), FWide{load(c->eng, pos_lo), load(c->eng, pos_hi)}, count);
+    if (int rc = finish(c, S)) return rc;
+    store_str(c->eng, r, out);
+    return FHS_OK;
+}
+int fhs_str_take(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !ok(c, pos) || (n && !out)) return bad(c);
+    if (n == 0) return FHS_OK;
+    Strings S(&c->eng);
+    FStr r = S.take(load_str(c->eng, s, n), load(c->eng, pos));
+    if (int rc = finish(c, S)) return rc;
+    store_str(c->eng, r, out);
+    return FHS_OK;
+}
+int fhs_str_take_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !ok(c, pos_lo) || !ok(c, pos_hi) || (n && !out)) return bad(c);
+    if (n == 0) return FHS_OK;
+    Strings S(&c->eng);
+    FStr r = S.take(load_str(c->eng, s, n), FWide{load(c->eng, pos_lo), load(c->eng, pos_hi)});
+    if (int rc = finish(c, S)) return rc;
+    store_str(c->eng, r, out);
+    return FHS_OK;
+}
+int fhs_str_split_at(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, fhs_char_t *head, fhs_char_t *tail) {
+    if (!ok_all(c, s, n) || !ok(c, pos) || (n && (!head || !tail))) return bad(c);
+    if (n == 0) return FHS_OK;
+    Strings S(&c->eng);
+    FStr h, t;
+    S.split_at(load_str(c->eng, s, n), load(c->eng, pos), &h, &t);
+    if (int rc = finish(c, S)) return rc;
+    store_str(c->eng, h, head);
+    store_str(c->eng, t, tail);
+    return FHS_OK;
+}
+int fhs_str_split_at_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, fhs_char_t *head,
+                          fhs_char_t *tail) {
+    if (!ok_all(c, s, n) || !ok(c, pos_lo) || !ok(c, pos_hi) || (n && (!head || !tail))) return bad(c);
+    if (n == 0) return FHS_OK;
+    Strings S(&c->eng);
+    FStr h, t;
+    S.split_at(load_str(c->eng, s, n), FWide{load(c->eng, pos_lo), load(c->eng, pos_hi)}, &h, &t);
+    if (int rc = finish(c, S)) return rc;
+    store_str(c->eng, h, head);
+    store_str(c->eng, t, tail);
+    return FHS_OK;
+}
+
 int fhs_str_compare(fhs_ctx *c, const fhs_char_t *a, size_t na, const fhs_char_t *b, size_t nb, int cmp, fhs_char_t *out) {
     if (!ok_all(c, a, na) || !ok_all(c, b, nb) || !out || cmp < 0 || cmp > 3) return bad(c);
     Strings S(&c->eng);

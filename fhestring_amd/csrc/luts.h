@@ -43,6 +43,11 @@ enum LutId : uint16_t {
     LUT_CLS_PICK,      // v = row + 4 flags: row 1 -> flags & 1, row 2 -> flags >> 1, row 0 -> 0
     // root of the three-state comparison tree (Strings::cmp_verdict): v = 8 + 4 s1 + 2 s2 + s3, s in {-1, 0, 1}
     LUT_LT8, LUT_LE8, LUT_GT8, LUT_GE8,
+    // an encrypted position against clear indices, most significant digit first (Strings::f_pos_thermometer):
+    // v = 4 s + digit - c with s the three-state comparison of the higher digits (0 below, 1 equal, 2 above) and c the
+    // clear digit, -3 <= v <= 11 (a negative v comes through the padding bit as -f(v + 16) = 0)
+    LUT_POS_CMP,       // the three-state value one digit further down: 2 for 5 <= v <= 11, 1 for v == 4, else 0
+    LUT_POS_GT,        // 1 for 5 <= v <= 11: position > index, at the last digit
     LUT_COUNT
 };
 
@@ -95,6 +100,8 @@ inline int lut_function(int id, int v) {
         case LUT_LE8: return v <= 8;
         case LUT_GT8: return v > 8;
         case LUT_GE8: return v >= 8;
+        case LUT_POS_CMP: return (v >= 5 && v <= 11) ? 2 : (v == 4 ? 1 : 0);
+        case LUT_POS_GT: return v >= 5 && v <= 11;
         default: break;
     }
     if (id >= LUT_GREEDY_NEXT0 && id <= LUT_GREEDY_NEXT7)

@@ -1784,4 +1784,200 @@ FStr Strings::f_case(const FStr &s, bool to_lower) {
     return r;
 }
 
+// ---------------------------------------------------------------------------------------------
+// encrypted positions as operands: char_at, substr, take, split_at.  The reference has no such
+// method -- its positions are only ever decrypted.  A position is the u8 of find / rfind / len or the (lo, hi) pair of
+// their wide forms; its value is taken literally as an index into the buffer, NULs and all.
+// ---------------------------------------------------------------------------------------------
+FChar Strings::char_at(const FStr &s, const FChar &pos) { return pos_substr(s, Pos{pos}, 1)[0]; }
+FChar Strings::char_at(const FStr &s, const FWide &pos) { return pos_substr(s, Pos{pos.lo, pos.hi}, 1)[0]; }
+FStr Strings::substr(const FStr &s, const FChar &pos, size_t count) { return pos_substr(s, Pos{pos}, count); }
+FStr Strings::substr(const FStr &s, const FWide &pos, size_t count) { return pos_substr(s, Pos{pos.lo, pos.hi}, count); }
+FStr Strings::take(const FStr &s, const FChar &pos) { return pos_take(s, Pos{pos}); }
+FStr Strings::take(const FStr &s, const FWide &pos) { return pos_take(s, Pos{pos.lo, pos.hi}); }
+void Strings::split_at(const FStr &s, const FChar &pos, FStr *head, FStr *tail) {
+    const Pos p{pos};
+    *head = pos_take(s, p);                                  // the bits of the shift are those the thermometer's digits
+    *tail = pos_substr(s, p, s.size());                      // came from: one refresh, found again by the engine
+}
+void Strings::split_at(const FStr &s, const FWide &pos, FStr *head, FStr *tail) {
+    const Pos p{pos.lo, pos.hi};
+    *head = pos_take(s, p);
+    *tail = pos_substr(s, p, s.size());
+}
+
+// as written: the position against a clear index with the char operators, the wide form from its two halves
+FChar Strings::pos_eq(const Pos &pos, size_t i) {
+    FChar r = ch_eq(pos[0], t((uint8_t)(i & 255)));
+    if (pos.size() > 1) r = ch_bitand(r, ch_eq(pos[1], t((uint8_t)(i >> 8))));
+    return r;
+}
+FChar Strings::pos_gt(const Pos &pos, size_t j) {
+    if (pos.size() == 1) return ch_gt(pos[0], t((uint8_t)j));
+    const FChar jl = t((uint8_t)(j & 255)), jh = t((uint8_t)(j >> 8));
+    return ch_bitor(ch_gt(pos[1], jh), ch_bitand(ch_eq(pos[1], jh), ch_gt(pos[0], jl)));
+}
+
+FStr Strings::pos_substr(const FStr &s, const Pos &pos, size_t count) {
+    const size_t n = s.size();
+    FStr out(count, t(0));
+    if (n == 0 || count == 0) return out;
+    if (fused()) return f_pos_shift(s, pos_digits(pos), count);
+    const size_t reach = std::min(n, (size_t)1 << (8 * pos.size()));   // indices the position can name
+    for (size_t i = 0; i < reach; i++) {
+        FChar hit = pos_eq(pos, i);
+        for (size_t j = 0; j < count && i + j < n; j++) out[j] = ch_ite(hit, s[i + j], out[j]);
+    }
+    return out;
+}
+
+FStr Strings::pos_take(const FStr &s, const Pos &pos) {
+    const size_t n = s.size();
+    if (n == 0) return {};
+    if (fused()) return f_pos_take(s, pos_digits(pos));
+    const size_t reach = std::min(n, (size_t)1 << (8 * pos.size()));
+    const FChar zero = t(0);
+    FStr out(n, zero);
+    for (size_t j = 0; j < reach; j++) out[j] = ch_ite(pos_gt(pos, j), s[j], zero);
+    return out;
+}
+
+// The digits of a position, least significant first.  find's index digits are sums of up to 57 bootstrap outputs; they
+// enter the selects below with other blocks beside them, so anything above 4 is refreshed first (what loading an
+// operand over the C ABI does as well).
+Strings::Num Strings::pos_digits(const Pos &pos) {
+    Num dg;
+    for (const FChar &c : pos)
+        for (int k = 0; k < 4; k++) dg.push_back(e_->sum_c2(c.b[k].id()) > 4 ? pbs(c.b[k], LUT_MSG) : c.b[k]);
+    return dg;
+}
+
+// Bit k of the position from digit k / 2 (one bootstrap each), for the K bits a shift on n characters can use
+// (2^K >= n, at most all of them), and ONE flag for everything above: the non-zero test on the sum of the higher digits
+// -- five to a bootstrap, 15 at most -- and on bit K itself where K is odd.  A trivial digit folds.
+Strings::PosBits Strings::f_pos_bits(const Num &dg, size_t n) {
+    PosBits pb;
+    const int B = 2 * (int)dg.size();
+    while (pb.K < B && ((size_t)1 << pb.K) < n) pb.K++;
+    for (int k = 0; k < pb.K; k++) pb.bit.push_back(pbs(dg[k / 2], (k & 1) ? LUT_BIT1_UNLESS : LUT_BIT0_UNLESS));
+    std::vector<Ref> high;
+    if (pb.K & 1) high.push_back(pbs(dg[pb.K / 2], LUT_BIT1_UNLESS));
+    for (size_t q = ((size_t)pb.K + 1) / 2; q < dg.size(); q += 5)
+        high.push_back(pbs(sum_refs(e_, &dg[q], std::min<size_t>(5, dg.size() - q)), LUT_NZ));
+    pb.ovf = or_tree(high);
+    return pb;
+}
+
+// out[j] = s[p + j] (0 past the end), j < count: the shift by an encrypted amount that is the same for every character.
+// A stage moves by 2^k where bit k of p is set, f_compact's rule with one move flag for the whole stage:
+//     m[i] = bit_k ? cur[i] : 0 (one bootstrap per block),    next[i] = cur[i] - m[i] + m[i + 2^k]   (exact, linear).
+// One shift for all has no collisions to avoid, so the stages may run in either order of the bits, and only what an
+// output can still be reached from is computed: stage t works on need[t] = need[t+1] u (need[t+1] + 2^k), pruned
+// backwards from the outputs.  From the highest bit down, what is left to shift by after bit k is below 2^k and only the
+// first 2^k + count - 1 characters matter: n + K count characters in all instead of n K, but up to 3 n for one character
+// of a buffer just above a power of two.  From the lowest bit up the working set halves with every stage: 2 n for one
+// character, about n log2(n / count) + n for `count`.  Both are counted and the cheaper order is recorded, so char_at
+// (count 1) is linear in n.  A stage whose bit is trivial is a static shift.  After t stages a block is a sum of its
+// operand (sum c^2 <= 4) and 2 t bootstrap outputs; the select's input carries 16 + 4 + 2 t <= 50.  The last bootstrap
+// refreshes the result and, with the overflow flag at weight 4, turns it into NUL when the position has a bit the stages
+// did not use.
+FStr Strings::f_pos_shift(const FStr &s, const Num &dg, size_t count) {
+    const size_t n = s.size();
+    const PosBits pb = f_pos_bits(dg, n);
+    const int K = pb.K;
+    const Ref zero = trivial_block(e_, 0);
+    auto is_zero = [&](const Ref &r) { return e_->is_triv(r.id()) && e_->triv_val(r.id()) == 0; };
+    // need[t][i]: character i is still wanted before stage t, which uses bit (down ? K - 1 - t : t); returns the selects
+    std::vector<std::vector<char>> need;
+    auto plan = [&](bool down) {
+        need.assign((size_t)K + 1, std::vector<char>(n, 0));
+        for (size_t j = 0; j < std::min(count, n); j++) need[K][j] = 1;
+        size_t selects = 0;
+        for (int t = K; t-- > 0;) {
+            const size_t d = (size_t)1 << (down ? K - 1 - t : t);
+            for (size_t i = 0; i < n; i++)
+                if (need[t + 1][i]) {
+                    need[t][i] = 1;
+                    if (i + d < n) need[t][i + d] = 1;
+                }
+            for (size_t i = 0; i < n; i++) selects += need[t][i];
+        }
+        return selects;
+    };
+    const size_t cost_up = plan(false);
+    const bool down = plan(true) <= cost_up;
+    if (!down) plan(false);
+    FStr cur = s;
+    for (int t = 0; t < K; t++) {
+        const int k = down ? K - 1 - t : t;
+        const size_t d = (size_t)1 << k;
+        const Ref &bit = pb.bit[k];
+        if (is_zero(bit)) continue;
+        FStr nxt(n);
+        if (e_->is_triv(bit.id())) {                         // a clear 1: everything moves
+            for (size_t i = 0; i < n; i++)
+                if (need[t + 1][i])
+                    for (int blk = 0; blk < 4; blk++) nxt[i].b[blk] = i + d < n ? cur[i + d].b[blk] : zero;
+            cur.swap(nxt);
+            continue;
+        }
+        FStr m(n);
+        for (size_t i = 0; i < n; i++)
+            if (need[t][i])
+                for (int blk = 0; blk < 4; blk++)
+                    m[i].b[blk] = is_zero(cur[i].b[blk]) ? zero : pbs(lin(e_, {{4, &bit}, {1, &cur[i].b[blk]}}), LUT_SEL_T);
+        for (size_t i = 0; i < n; i++)
+            if (need[t + 1][i])
+                for (int blk = 0; blk < 4; blk++)
+                    nxt[i].b[blk] = lin(e_, {{1, &cur[i].b[blk]}, {-1, &m[i].b[blk]}, {1, i + d < n ? &m[i + d].b[blk] : &zero}});
+        cur.swap(nxt);
+    }
+    const bool ovf_clear = e_->is_triv(pb.ovf.id());
+    FStr out(count);
+    for (size_t j = 0; j < count; j++)
+        for (int blk = 0; blk < 4; blk++) {
+            Ref &o = out[j].b[blk];
+            if (j >= n || is_zero(cur[j].b[blk]) || (ovf_clear && !is_zero(pb.ovf))) o = zero;
+            else if (!ovf_clear) o = pbs(lin(e_, {{4, &pb.ovf}, {1, &cur[j].b[blk]}}), LUT_SEL_F);
+            else o = e_->sum_c2(cur[j].b[blk].id()) > 4 ? pbs(cur[j].b[blk], LUT_MSG) : cur[j].b[blk];
+        }
+    return out;
+}
+
+// g[j] = [p > j] for j < limit, from the digits most significant first.  Every clear prefix of q digits carries the
+// three-state comparison s of the position's top q digits with it (0 below, 1 equal, 2 above; the empty prefix: equal),
+// and one bootstrap on 4 s + digit - c takes it one digit further down for the clear digit c (LUT_POS_CMP; LUT_POS_GT
+// at the last digit, where only "above" is asked).  The four children of a prefix differ in the constant c alone: they
+// are extractions of one blind rotation, so the tree of limit + limit / 4 + ... nodes costs about limit / 3 rotations.
+// Prefixes no index below `limit` has are not built.  Inputs carry 16 + 4.
+std::vector<Ref> Strings::f_pos_thermometer(const Num &dg, size_t limit) {
+    std::vector<Ref> state{trivial_block(e_, 1)};
+    for (size_t q = dg.size(); q-- > 0;) {
+        const size_t S = (size_t)1 << (2 * q), count = (limit + S - 1) / S;
+        std::vector<Ref> nxt(count);
+        for (size_t p = 0; p < count; p++)
+            nxt[p] = pbs(lin(e_, {{4, &state[p / 4]}, {1, &dg[q]}}, -(int)(p % 4)), q ? LUT_POS_CMP : LUT_POS_GT);
+        state.swap(nxt);
+    }
+    return state;
+}
+
+// take[j] = g[j] ? s[j] : 0, one select per block (16 + 4).  An index no value of the position exceeds (j >= 4^digits:
+// a u8 position on a long buffer) is a clear NUL.
+FStr Strings::f_pos_take(const FStr &s, const Num &dg) {
+    const size_t n = s.size(), limit = std::min(n, (size_t)1 << (2 * dg.size()));
+    const std::vector<Ref> g = f_pos_thermometer(dg, limit);
+    const Ref zero = trivial_block(e_, 0);
+    FStr out(n);
+    for (size_t j = 0; j < n; j++)
+        for (int blk = 0; blk < 4; blk++) {
+            const Ref &x = s[j].b[blk];
+            Ref &o = out[j].b[blk];
+            if (j >= limit || (e_->is_triv(x.id()) && e_->triv_val(x.id()) == 0)) o = zero;
+            else if (e_->is_triv(g[j].id())) o = e_->triv_val(g[j].id()) ? x : zero;
+            else o = pbs(lin(e_, {{4, &g[j]}, {1, &x}}), LUT_SEL_T);
+        }
+    return out;
+}
+
 }  // namespace fhs

@@ -39,6 +39,17 @@ class Strings {
     FWide rfind_wide(const FStr &s, const FStr &pat);
     FWide len_wide(const FStr &s);
     FWide count_flags_wide(const FStr &flags);              // number of set 0/1 flags
+    // consumers of an encrypted position p (a char, or a wide value) on the n characters of s as they are, NULs included:
+    // char_at = s[p] if p < n else 0; substr[j] = s[p + j] if p + j < n else 0, j < count; take[j] = s[j] if j < p else 0
+    // (n characters); split_at = (take(s, p), substr(s, p, n)).  No length limit; an absent position is past the end.
+    FChar char_at(const FStr &s, const FChar &pos);
+    FChar char_at(const FStr &s, const FWide &pos);
+    FStr substr(const FStr &s, const FChar &pos, size_t count);
+    FStr substr(const FStr &s, const FWide &pos, size_t count);
+    FStr take(const FStr &s, const FChar &pos);
+    FStr take(const FStr &s, const FWide &pos);
+    void split_at(const FStr &s, const FChar &pos, FStr *head, FStr *tail);
+    void split_at(const FStr &s, const FWide &pos, FStr *head, FStr *tail);
     FChar eq(const FStr &a, const FStr &b);
     FChar ne(const FStr &a, const FStr &b);
     FChar eq_ignore_case(const FStr &a, const FStr &b);
@@ -127,6 +138,18 @@ class Strings {
     Num f_rfind_digits(const FStr &s, const FStr &pat, size_t digits);
     // as written: counter += flag on two chars, the carry is the wrap of the low one
     void wide_add_flag(FWide &counter, const FChar &flag);
+    // positions as operands: one implementation over the halves of the position (1: u8, 2: wide = lo, hi)
+    typedef std::vector<FChar> Pos;
+    FChar pos_eq(const Pos &pos, size_t i);                            // as written: pos == i
+    FChar pos_gt(const Pos &pos, size_t j);                            // as written: pos > j
+    FStr pos_substr(const FStr &s, const Pos &pos, size_t count);
+    FStr pos_take(const FStr &s, const Pos &pos);
+    Num pos_digits(const Pos &pos);                                    // 4 or 8 digits, each at sum c^2 <= 4
+    struct PosBits { int K = 0; std::vector<Ref> bit; Ref ovf; };      // bits 0 .. K-1 as 0/1 blocks, ovf = some bit >= K is set
+    PosBits f_pos_bits(const Num &dg, size_t n);
+    FStr f_pos_shift(const FStr &s, const Num &dg, size_t count);      // out[j] = s[p + j]
+    std::vector<Ref> f_pos_thermometer(const Num &dg, size_t limit);   // g[j] = [p > j], j < limit <= 4^digits
+    FStr f_pos_take(const FStr &s, const Num &dg);
     FChar f_eq_ignore_case(const FStr &a, const FStr &b);
     // lexicographic order as a tree of three-state values s = sign(a - b) in {-1, 0, 1}, most significant first
     std::vector<Ref> cmp_leaves(const FStr &a, const FStr &b);          // one per nibble pair, missing characters are 0

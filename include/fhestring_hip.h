@@ -295,6 +295,27 @@ int fhs_str_len_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t *lo, 
  * overflow a char (the u8 adds of fheasciichar.rs:88-91 chained as in mod.rs:485-490, with a carry into *hi). */
 int fhs_flags_count_wide(fhs_ctx *c, const fhs_char_t *flags, size_t n, fhs_char_t *lo, fhs_char_t *hi);
 
+/* ---- encrypted positions as operands -------------------------------------------------------------------------
+ * What find / rfind / len and their _wide forms return can be used on the server (the reference only ever decrypts
+ * it).  With buf the n characters of s as byte values, NULs included (nothing is compacted), and p the value of the
+ * position -- one char, or pos_lo + 256 * pos_hi:
+ *   char_at   *out = buf[p] if p < n, else 0
+ *   substr    out[j] = buf[p + j] if p + j < n, else 0, for j < count (count is clear)
+ *   take      out[j] = buf[j] if j < p, else 0, for j < n
+ *   split_at  head = take(s, p), tail = substr(s, p, n)
+ * p is taken literally: a u8 255 on 300 characters is index 255.  An absent position (255 on n <= 255,
+ * FHS_WIDE_ABSENT) is past the end: substr and char_at give NULs, take the whole buffer, split_at (s, "").  On a string
+ * of text followed by NUL padding these are text[p:p+count], text[:p] and text[p:].  Both modes; no length limit.
+ * n == 0 gives trivial NULs and count == 0 nothing, with nothing recorded. */
+int fhs_str_char_at(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, fhs_char_t *out);
+int fhs_str_char_at_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, fhs_char_t *out);
+int fhs_str_substr(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, size_t count, fhs_char_t *out /*[count]*/);
+int fhs_str_substr_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, size_t count, fhs_char_t *out /*[count]*/);
+int fhs_str_take(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, fhs_char_t *out /*[n]*/);
+int fhs_str_take_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, fhs_char_t *out /*[n]*/);
+int fhs_str_split_at(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, fhs_char_t *head /*[n]*/, fhs_char_t *tail /*[n]*/);
+int fhs_str_split_at_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, fhs_char_t *head /*[n]*/, fhs_char_t *tail /*[n]*/);
+
 /* ---- multi-GPU inside the library (one process per GPU, RCCL over xGMI) ---------------------------------
  * north_star: "characters of an FheString are independent PBS batches, so long strings shard across the GPUs of one
  * node with an RCCL gather".  fhs_dist_init creates this context's communicator (librccl.so.1 is loaded at run time;

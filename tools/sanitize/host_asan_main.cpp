@@ -263,6 +263,22 @@ int main() {
                 CHECK(fhs_str_find(c, big.data(), big.size(), p.data(), p.size(), &r) == FHS_ERR_LIMIT);
             }
             CHECK(fhs_str_find_wide(c, s.data(), s.size(), p.data(), p.size(), nullptr, &hi) == FHS_ERR_ARG);
+            // the positions as operands: find's noisy digits are refreshed on the way in, results of every length
+            CHECK(fhs_str_find_wide(c, s.data(), s.size(), p.data(), p.size(), &lo, &hi) == FHS_OK);
+            CHECK(fhs_str_find(c, s.data(), s.size(), p.data(), p.size(), &r) == FHS_OK);
+            std::vector<fhs_char_t> head(s.size() + 5, 0), tail(s.size() + 5, 0);
+            CHECK(fhs_str_char_at(c, s.data(), s.size(), r, &f) == FHS_OK && f);
+            CHECK(fhs_str_char_at_wide(c, s.data(), s.size(), lo, hi, &f) == FHS_OK && f);
+            CHECK(fhs_str_substr(c, s.data(), s.size(), r, s.size() + 5, head.data()) == FHS_OK && head.back());
+            CHECK(fhs_str_substr_wide(c, s.data(), s.size(), lo, hi, 3, head.data()) == FHS_OK);
+            CHECK(fhs_str_take(c, s.data(), s.size(), r, head.data()) == FHS_OK);
+            CHECK(fhs_str_take_wide(c, s.data(), s.size(), lo, hi, head.data()) == FHS_OK);
+            CHECK(fhs_str_split_at(c, s.data(), s.size(), r, head.data(), tail.data()) == FHS_OK);
+            CHECK(fhs_str_split_at_wide(c, s.data(), s.size(), lo, hi, head.data(), tail.data()) == FHS_OK);
+            CHECK(fhs_str_substr(c, s.data(), s.size(), r, 0, nullptr) == FHS_OK);
+            CHECK(fhs_str_take(c, nullptr, 0, r, nullptr) == FHS_OK);
+            CHECK(fhs_str_substr(c, s.data(), s.size(), r, 3, nullptr) == FHS_ERR_ARG);
+            CHECK(fhs_str_split_at(c, s.data(), s.size(), 0, head.data(), tail.data()) == FHS_ERR_ARG);
         }
         CHECK(fhs_str_eq(c, s.data(), s.size(), o.data(), o.size(), &r) == FHS_OK);
         CHECK(fhs_str_ne(c, s.data(), s.size(), o.data(), o.size(), &r) == FHS_OK);
