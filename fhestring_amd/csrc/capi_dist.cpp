@@ -205,8 +205,8 @@ int fhs_dist_str_contains_clear(fhs_ctx *c, const fhs_char_t *shard, size_t n, c
 static int dist_find(fhs_ctx *c, const fhs_char_t *s, size_t n, const FStr &pat, size_t first_window, size_t total_chars,
                      fhs_char_t *out) {
     Engine &e = c->eng;
-    if (total_chars >= FHS_MAX_FIND_LENGTH + pat.size())          // mod.rs:1025-1027, on the whole string
-        return e.ctx.fail(FHS_ERR_LIMIT, "Maximum supported size for find reached");
+    if (Strings::limit_reached(total_chars, pat.size(), 1))       // mod.rs:1025-1027, on the whole string
+        return e.ctx.fail(FHS_ERR_LIMIT, Strings::LIMIT_MSG);
     FusedScope fs(e);
     Strings S(&e);
     if (pat.empty()) {                                              // mod.rs:1017-1019: "" is found at position 0 (every window matches)

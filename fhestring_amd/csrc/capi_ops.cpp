@@ -38,10 +38,25 @@ FStr load_str(Engine &e, const fhs_char_t *h, size_t n) {
     for (size_t i = 0; i < n; i++) s.push_back(load(e, h[i]));
     return s;
 }
+struct PosArg {                                              // a position operand: {{pos}, 1} or {{lo, hi}, 2}
+    fhs_char_t h[2];
+    size_t halves;
+};
+bool ok_pos(fhs_ctx *c, const PosArg &p) { return ok_all(c, p.h, p.halves); }
+Pos load_pos(fhs_ctx *c, const PosArg &p) { return load_str(c->eng, p.h, p.halves); }
 void store_str(Engine &e, FStr &s, fhs_char_t *out) {
     for (size_t i = 0; i < s.size(); i++) out[i] = store(e, s[i]);
 }
 int bad(fhs_ctx *c) { return c ? c->eng.ctx.fail(FHS_ERR_ARG, "invalid handle or null argument") : FHS_ERR_ARG; }
+// the blocks behind n char handles, in order; fails on the first handle that is not valid
+int gather_blocks(fhs_ctx *c, const fhs_char_t *chars, size_t n, std::vector<Bid> &out) {
+    out.resize(4 * n);
+    for (size_t i = 0; i < n; i++) {
+        if (!c->eng.valid_char(chars[i])) return bad(c);
+        std::copy_n(c->eng.char_blocks(chars[i]), 4, &out[4 * i]);
+    }
+    return FHS_OK;
+}
 
 template <class F> fhs_char_t binop(fhs_ctx *c, fhs_char_t a, fhs_char_t b, F f) {
     if (!ok(c, a) || !ok(c, b)) { bad(c); return 0; }
@@ -192,12 +207,8 @@ int fhs_download(fhs_ctx *c, fhs_char_t a, uint64_t *blocks) {
 }
 int fhs_download_string(fhs_ctx *c, const fhs_char_t *chars, size_t n, uint64_t *blocks) {
     if (!c || (n && (!chars || !blocks))) return bad(c);
-    std::vector<Bid> b(4 * n);
-    for (size_t i = 0; i < n; i++) {
-        if (!c->eng.valid_char(chars[i])) return bad(c);
-        const Bid *cb = c->eng.char_blocks(chars[i]);
-        for (int k = 0; k < 4; k++) b[4 * i + k] = cb[k];
-    }
+    std::vector<Bid> b;
+    if (int rc = gather_blocks(c, chars, n, b)) return rc;
     return c->eng.read_many(b.data(), b.size(), blocks);
 }
 int fhs_load_packing_key(fhs_ctx *c, const uint64_t *key) {
@@ -206,17 +217,20 @@ int fhs_load_packing_key(fhs_ctx *c, const uint64_t *key) {
     if (int rc = c->eng.flush()) return rc;
     return c->eng.ctx.load_packing_key(key);
 }
+namespace {
+int download_packed(fhs_ctx *c, const fhs_char_t *chars, size_t n, void *mask16, void *body16, uint64_t *mask64,
+                    uint64_t *body64, bool recipient) {
+    if (!c || (n && (!chars || !mask16 || !body16)) || !mask64 != !body64) return bad(c);
+    if (recipient && n == 0) return FHS_OK;
+    std::vector<Bid> b;
+    if (int rc = gather_blocks(c, chars, n, b)) return rc;
+    return c->eng.read_packed(b.data(), b.size(), static_cast<uint16_t *>(mask16), static_cast<uint16_t *>(body16), mask64,
+                              body64, recipient);
+}
+}  // namespace
 int fhs_debug_download_string_packed64(fhs_ctx *c, const fhs_char_t *chars, size_t n, void *mask16, void *body16,
                                        uint64_t *mask64, uint64_t *body64) {
-    if (!c || (n && (!chars || !mask16 || !body16)) || !mask64 != !body64) return bad(c);
-    std::vector<Bid> b(4 * n);
-    for (size_t i = 0; i < n; i++) {
-        if (!c->eng.valid_char(chars[i])) return bad(c);
-        const Bid *cb = c->eng.char_blocks(chars[i]);
-        for (int k = 0; k < 4; k++) b[4 * i + k] = cb[k];
-    }
-    return c->eng.read_packed(b.data(), b.size(), static_cast<uint16_t *>(mask16), static_cast<uint16_t *>(body16), mask64,
-                              body64);
+    return download_packed(c, chars, n, mask16, body16, mask64, body64, false);
 }
 int fhs_download_string_packed(fhs_ctx *c, const fhs_char_t *chars, size_t n, void *mask16, void *body16) {
     return fhs_debug_download_string_packed64(c, chars, n, mask16, body16, nullptr, nullptr);
@@ -226,12 +240,8 @@ int fhs_download_string_packed(fhs_ctx *c, const fhs_char_t *chars, size_t n, vo
 int fhs_store_put(fhs_ctx *c, const fhs_char_t *chars, size_t n, uint64_t *id_out) {
     if (!c || !id_out || (n && !chars)) return bad(c);
     *id_out = 0;
-    std::vector<Bid> b(4 * n);
-    for (size_t i = 0; i < n; i++) {
-        if (!c->eng.valid_char(chars[i])) return bad(c);
-        const Bid *cb = c->eng.char_blocks(chars[i]);
-        for (int k = 0; k < 4; k++) b[4 * i + k] = cb[k];
-    }
+    std::vector<Bid> b;
+    if (int rc = gather_blocks(c, chars, n, b)) return rc;
     return c->eng.store_put(b.data(), b.size(), id_out);
 }
 int fhs_store_get(fhs_ctx *c, uint64_t id, size_t first_char, size_t count, fhs_char_t *out) {
@@ -336,16 +346,7 @@ int fhs_debug_rekey_device(fhs_ctx *c, const void *mask32, const void *body32, s
 // ---- packed result download under a recipient's key ----
 int fhs_download_string_packed_for(fhs_ctx *c, const fhs_char_t *chars, size_t n, void *mask16, void *body16, uint64_t *mask64,
                                    uint64_t *body64) {
-    if (!c || (n && (!chars || !mask16 || !body16)) || !mask64 != !body64) return bad(c);
-    if (n == 0) return FHS_OK;
-    std::vector<Bid> b(4 * n);
-    for (size_t i = 0; i < n; i++) {
-        if (!c->eng.valid_char(chars[i])) return bad(c);
-        const Bid *cb = c->eng.char_blocks(chars[i]);
-        for (int k = 0; k < 4; k++) b[4 * i + k] = cb[k];
-    }
-    return c->eng.read_packed(b.data(), b.size(), static_cast<uint16_t *>(mask16), static_cast<uint16_t *>(body16), mask64,
-                              body64, true);
+    return download_packed(c, chars, n, mask16, body16, mask64, body64, true);
 }
 int fhs_debug_rekey_packed_device(fhs_ctx *c, const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, void *mask16,
                                   void *body16) {
@@ -358,25 +359,19 @@ int fhs_store_download_packed(fhs_ctx *c, uint64_t id, size_t first_char, size_t
     return c->eng.store_read_packed(id, first_char, count, recipient != 0, static_cast<uint16_t *>(mask16),
                                     static_cast<uint16_t *>(body16));
 }
-int fhs_export_device(fhs_ctx *c, fhs_char_t a, uint64_t *d_blocks) {
+namespace {
+int export_device(fhs_ctx *c, fhs_char_t a, uint64_t *d_blocks, bool wait) {
     if (!ok(c, a) || !d_blocks) return bad(c);
     const Bid *b = c->eng.char_blocks(a);
     for (int i = 0; i < 4; i++) {
-        int rc = c->eng.copy_block_to_device(b[i], d_blocks + (size_t)i * FHS_BIG_CT);
+        int rc = c->eng.copy_block_to_device(b[i], d_blocks + (size_t)i * FHS_BIG_CT, wait);
         if (rc) return rc;
     }
     return FHS_OK;
 }
-
-int fhs_export_device_async(fhs_ctx *c, fhs_char_t a, uint64_t *d_blocks) {
-    if (!ok(c, a) || !d_blocks) return bad(c);
-    const Bid *b = c->eng.char_blocks(a);
-    for (int i = 0; i < 4; i++) {
-        int rc = c->eng.copy_block_to_device(b[i], d_blocks + (size_t)i * FHS_BIG_CT, false);
-        if (rc) return rc;
-    }
-    return FHS_OK;
-}
+}  // namespace
+int fhs_export_device(fhs_ctx *c, fhs_char_t a, uint64_t *d_blocks) { return export_device(c, a, d_blocks, true); }
+int fhs_export_device_async(fhs_ctx *c, fhs_char_t a, uint64_t *d_blocks) { return export_device(c, a, d_blocks, false); }
 void *fhs_stream_handle(fhs_ctx *c) { return c ? static_cast<hipStream_t>(c->eng.ctx.stream) : nullptr; }
 
 int fhs_set_mode(fhs_ctx *c, int mode) {
@@ -397,8 +392,6 @@ int fhs_set_mode(fhs_ctx *c, int mode) {
 STR_PAT_OP(fhs_str_contains, contains)
 STR_PAT_OP(fhs_str_starts_with, starts_with)
 STR_PAT_OP(fhs_str_ends_with, ends_with)
-STR_PAT_OP(fhs_str_find, find)
-STR_PAT_OP(fhs_str_rfind, rfind)
 STR_PAT_OP(fhs_str_eq, eq)
 STR_PAT_OP(fhs_str_ne, ne)
 STR_PAT_OP(fhs_str_eq_ignore_case, eq_ignore_case)
@@ -410,14 +403,6 @@ int fhs_str_contains_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char
     *out = store(c->eng, r);
     return FHS_OK;
 }
-int fhs_str_find_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, fhs_char_t *out) {
-    if (!ok_all(c, s, n) || (m && !pat) || !out) return bad(c);
-    Strings S(&c->eng);
-    FChar r = S.find(load_str(c->eng, s, n), S.clear(pat, m));
-    if (int rc = finish(c, S)) return rc;
-    *out = store(c->eng, r);
-    return FHS_OK;
-}
 int fhs_str_is_empty(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t *out) {
     if (!ok_all(c, s, n) || !out) return bad(c);
     Strings S(&c->eng);
@@ -425,63 +410,78 @@ int fhs_str_is_empty(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t *out)
     *out = store(c->eng, r);
     return FHS_OK;
 }
-int fhs_str_len(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t *out) {
-    if (!ok_all(c, s, n) || !out) return bad(c);
-    Strings S(&c->eng);
-    FChar r = S.len(load_str(c->eng, s, n));
-    *out = store(c->eng, r);
-    return FHS_OK;
-}
-// ---- wide positions and counts: (lo, hi) chars, value lo + 256 hi ----
+// ---- positions and counts: one char (the reference's u8) or a (lo, hi) pair, value lo + 256 hi ----
 namespace {
-int store_wide(fhs_ctx *c, Strings &S, FWide &r, fhs_char_t *lo, fhs_char_t *hi) {
+struct PatArg {                                              // a pattern as handles, or as clear text
+    const fhs_char_t *enc;
+    const char *clear;
+    size_t m;
+};
+int store_pos(fhs_ctx *c, Strings &S, Pos &r, fhs_char_t *lo, fhs_char_t *hi) {
     if (int rc = finish(c, S)) return rc;
-    *lo = store(c->eng, r.lo);
-    *hi = store(c->eng, r.hi);
+    *lo = store(c->eng, r[0]);
+    if (hi) *hi = store(c->eng, r[1]);
     return FHS_OK;
 }
-// the limit is tested before the operands are loaded: loading refreshes noisy operands, which records bootstraps
-int wide_limit(fhs_ctx *c, size_t n, size_t m) {
-    if (!Strings::wide_limit_reached(n, m)) return FHS_OK;
-    return c->eng.ctx.fail(FHS_ERR_LIMIT, "Maximum supported size for find reached");
+// find / rfind after the argument checks; hi == nullptr: the u8 form
+int find_op(fhs_ctx *c, bool reverse, const fhs_char_t *s, size_t n, const PatArg &pat, fhs_char_t *lo, fhs_char_t *hi) {
+    const size_t halves = hi ? 2 : 1;
+    // The wide forms test the limit before the operands are loaded: loading refreshes noisy operands, which records
+    // bootstraps.  The u8 forms load first and leave the test to Strings.  (rfind counts the NUL pushed at mod.rs:737.)
+    if (hi && Strings::limit_reached(n + reverse, pat.m, halves)) return c->eng.ctx.fail(FHS_ERR_LIMIT, Strings::LIMIT_MSG);
+    Strings S(&c->eng);
+    const FStr text = load_str(c->eng, s, n);
+    const FStr p = pat.clear ? S.clear(pat.clear, pat.m) : load_str(c->eng, pat.enc, pat.m);
+    Pos r = reverse ? S.rfind(text, p, halves) : S.find(text, p, halves);
+    return store_pos(c, S, r, lo, hi);
+}
+// len, or the number of set flags
+int count_op(fhs_ctx *c, bool are_flags, const fhs_char_t *s, size_t n, fhs_char_t *lo, fhs_char_t *hi) {
+    Strings S(&c->eng);
+    const FStr text = load_str(c->eng, s, n);
+    Pos r = are_flags ? S.count_flags(text, hi ? 2 : 1) : S.len(text, hi ? 2 : 1);
+    return store_pos(c, S, r, lo, hi);
 }
 }  // namespace
 
+int fhs_str_find(fhs_ctx *c, const fhs_char_t *s, size_t n, const fhs_char_t *pat, size_t m, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !ok_all(c, pat, m) || !out) return bad(c);
+    return find_op(c, false, s, n, {pat, nullptr, m}, out, nullptr);
+}
+int fhs_str_find_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || (m && !pat) || !out) return bad(c);
+    return find_op(c, false, s, n, {nullptr, pat, m}, out, nullptr);
+}
+int fhs_str_rfind(fhs_ctx *c, const fhs_char_t *s, size_t n, const fhs_char_t *pat, size_t m, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !ok_all(c, pat, m) || !out) return bad(c);
+    return find_op(c, true, s, n, {pat, nullptr, m}, out, nullptr);
+}
+int fhs_str_len(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !out) return bad(c);
+    return count_op(c, false, s, n, out, nullptr);
+}
 int fhs_str_find_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const fhs_char_t *pat, size_t m, fhs_char_t *lo,
                       fhs_char_t *hi) {                      // mod.rs:1010-1053 with the u8 of :1023-1027, :1044 widened
     if (!ok_all(c, s, n) || !ok_all(c, pat, m) || !lo || !hi) return bad(c);
-    if (int rc = wide_limit(c, n, m)) return rc;
-    Strings S(&c->eng);
-    FWide r = S.find_wide(load_str(c->eng, s, n), load_str(c->eng, pat, m));
-    return store_wide(c, S, r, lo, hi);
+    return find_op(c, false, s, n, {pat, nullptr, m}, lo, hi);
 }
 int fhs_str_find_clear_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, fhs_char_t *lo,
                             fhs_char_t *hi) {                // mod.rs:1075, the same
     if (!ok_all(c, s, n) || (m && !pat) || !lo || !hi) return bad(c);
-    if (int rc = wide_limit(c, n, m)) return rc;
-    Strings S(&c->eng);
-    FWide r = S.find_wide(load_str(c->eng, s, n), S.clear(pat, m));
-    return store_wide(c, S, r, lo, hi);
+    return find_op(c, false, s, n, {nullptr, pat, m}, lo, hi);
 }
 int fhs_str_rfind_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const fhs_char_t *pat, size_t m, fhs_char_t *lo,
                        fhs_char_t *hi) {                     // mod.rs:727-790 with the u8 of :739-744, :753, :783 widened
     if (!ok_all(c, s, n) || !ok_all(c, pat, m) || !lo || !hi) return bad(c);
-    if (int rc = wide_limit(c, n + 1, m)) return rc;        // the NUL pushed at :737 counts
-    Strings S(&c->eng);
-    FWide r = S.rfind_wide(load_str(c->eng, s, n), load_str(c->eng, pat, m));
-    return store_wide(c, S, r, lo, hi);
+    return find_op(c, true, s, n, {pat, nullptr, m}, lo, hi);
 }
 int fhs_str_len_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t *lo, fhs_char_t *hi) {   // mod.rs:478-493, no wrap
     if (!ok_all(c, s, n) || !lo || !hi) return bad(c);
-    Strings S(&c->eng);
-    FWide r = S.len_wide(load_str(c->eng, s, n));
-    return store_wide(c, S, r, lo, hi);
+    return count_op(c, false, s, n, lo, hi);
 }
 int fhs_flags_count_wide(fhs_ctx *c, const fhs_char_t *flags, size_t n, fhs_char_t *lo, fhs_char_t *hi) {
     if (!ok_all(c, flags, n) || !lo || !hi) return bad(c);
-    Strings S(&c->eng);
-    FWide r = S.count_flags_wide(load_str(c->eng, flags, n));
-    return store_wide(c, S, r, lo, hi);
+    return count_op(c, true, flags, n, lo, hi);
 }
 
 // ---- encrypted positions as operands: char_at / substr / take / split_at, position a char or a (lo, hi) pair ----
@@ -494,84 +494,74 @@ int store_nuls(fhs_ctx *c, fhs_char_t *out, size_t count) {
     }
     return FHS_OK;
 }
-}  // namespace
-int fhs_str_char_at(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, fhs_char_t *out) {
-    if (!ok_all(c, s, n) || !ok(c, pos) || !out) return bad(c);
+int char_at_op(fhs_ctx *c, const fhs_char_t *s, size_t n, const PosArg &pos, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !ok_pos(c, pos) || !out) return bad(c);
     if (n == 0) return store_nuls(c, out, 1);
     Strings S(&c->eng);
-    FChar r = S.char_at(load_str(c->eng, s, n), load(c->eng, pos));
+    const FStr text = load_str(c->eng, s, n);
+    FChar r = S.char_at(text, load_pos(c, pos));
     if (int rc = finish(c, S)) return rc;
     *out = store(c->eng, r);
     return FHS_OK;
 }
-int fhs_str_char_at_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, fhs_char_t *out) {
-    if (!ok_all(c, s, n) || !ok(c, pos_lo) || !ok(c, pos_hi) || !out) return bad(c);
-    if (n == 0) return store_nuls(c, out, 1);
-    Strings S(&c->eng);
-    FChar r = S.char_at(load_str(c->eng, s, n), FWide{load(c->eng, pos_lo), load(c->eng, pos_hi)});
-    if (int rc = finish(c, S)) return rc;
-    *out = store(c->eng, r);
-    return FHS_OK;
-}
-int fhs_str_substr(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, size_t count, fhs_char_t *out) {
-    if (!ok_all(c, s, n) || !ok(c, pos) || (count && !out)) return bad(c);
+int substr_op(fhs_ctx *c, const fhs_char_t *s, size_t n, const PosArg &pos, size_t count, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !ok_pos(c, pos) || (count && !out)) return bad(c);
     if (n == 0 || count == 0) return store_nuls(c, out, count);
     Strings S(&c->eng);
-    FStr r = S.substr(load_str(c->eng, s, n), load(c->eng, pos), count);
+    const FStr text = load_str(c->eng, s, n);
+    FStr r = S.substr(text, load_pos(c, pos), count);
     if (int rc = finish(c, S)) return rc;
     store_str(c->eng, r, out);
     return FHS_OK;
+}
+int take_op(fhs_ctx *c, const fhs_char_t *s, size_t n, const PosArg &pos, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !ok_pos(c, pos) || (n && !out)) return bad(c);
+    if (n == 0) return FHS_OK;
+    Strings S(&c->eng);
+    const FStr text = load_str(c->eng, s, n);
+    FStr r = S.take(text, load_pos(c, pos));
+    if (int rc = finish(c, S)) return rc;
+    store_str(c->eng, r, out);
+    return FHS_OK;
+}
+int split_at_op(fhs_ctx *c, const fhs_char_t *s, size_t n, const PosArg &pos, fhs_char_t *head, fhs_char_t *tail) {
+    if (!ok_all(c, s, n) || !ok_pos(c, pos) || (n && (!head || !tail))) return bad(c);
+    if (n == 0) return FHS_OK;
+    Strings S(&c->eng);
+    const FStr text = load_str(c->eng, s, n);
+    FStr h, t;
+    S.split_at(text, load_pos(c, pos), &h, &t);
+    if (int rc = finish(c, S)) return rc;
+    store_str(c->eng, h, head);
+    store_str(c->eng, t, tail);
+    return FHS_OK;
+}
+}  // namespace
+int fhs_str_char_at(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, fhs_char_t *out) {
+    return char_at_op(c, s, n, {{pos}, 1}, out);
+}
+int fhs_str_char_at_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, fhs_char_t *out) {
+    return char_at_op(c, s, n, {{pos_lo, pos_hi}, 2}, out);
+}
+int fhs_str_substr(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, size_t count, fhs_char_t *out) {
+    return substr_op(c, s, n, {{pos}, 1}, count, out);
 }
 int fhs_str_substr_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, size_t count,
                         fhs_char_t *out) {
-    if (!ok_all(c, s, n) || !ok(c, pos_lo) || !ok(c, pos_hi) || (count && !out)) return bad(c);
-    if (n == 0 || count == 0) return store_nuls(c, out, count);
-    Strings S(&c->eng);
-    FStr r = S.substr(load_str(c->eng, s, n), FWide{load(c->eng, pos_lo), load(c->eng, pos_hi)}, count);
-    if (int rc = finish(c, S)) return rc;
-    store_str(c->eng, r, out);
-    return FHS_OK;
+    return substr_op(c, s, n, {{pos_lo, pos_hi}, 2}, count, out);
 }
 int fhs_str_take(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, fhs_char_t *out) {
-    if (!ok_all(c, s, n) || !ok(c, pos) || (n && !out)) return bad(c);
-    if (n == 0) return FHS_OK;
-    Strings S(&c->eng);
-    FStr r = S.take(load_str(c->eng, s, n), load(c->eng, pos));
-    if (int rc = finish(c, S)) return rc;
-    store_str(c->eng, r, out);
-    return FHS_OK;
+    return take_op(c, s, n, {{pos}, 1}, out);
 }
 int fhs_str_take_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, fhs_char_t *out) {
-    if (!ok_all(c, s, n) || !ok(c, pos_lo) || !ok(c, pos_hi) || (n && !out)) return bad(c);
-    if (n == 0) return FHS_OK;
-    Strings S(&c->eng);
-    FStr r = S.take(load_str(c->eng, s, n), FWide{load(c->eng, pos_lo), load(c->eng, pos_hi)});
-    if (int rc = finish(c, S)) return rc;
-    store_str(c->eng, r, out);
-    return FHS_OK;
+    return take_op(c, s, n, {{pos_lo, pos_hi}, 2}, out);
 }
 int fhs_str_split_at(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, fhs_char_t *head, fhs_char_t *tail) {
-    if (!ok_all(c, s, n) || !ok(c, pos) || (n && (!head || !tail))) return bad(c);
-    if (n == 0) return FHS_OK;
-    Strings S(&c->eng);
-    FStr h, t;
-    S.split_at(load_str(c->eng, s, n), load(c->eng, pos), &h, &t);
-    if (int rc = finish(c, S)) return rc;
-    store_str(c->eng, h, head);
-    store_str(c->eng, t, tail);
-    return FHS_OK;
+    return split_at_op(c, s, n, {{pos}, 1}, head, tail);
 }
 int fhs_str_split_at_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, fhs_char_t *head,
                           fhs_char_t *tail) {
-    if (!ok_all(c, s, n) || !ok(c, pos_lo) || !ok(c, pos_hi) || (n && (!head || !tail))) return bad(c);
-    if (n == 0) return FHS_OK;
-    Strings S(&c->eng);
-    FStr h, t;
-    S.split_at(load_str(c->eng, s, n), FWide{load(c->eng, pos_lo), load(c->eng, pos_hi)}, &h, &t);
-    if (int rc = finish(c, S)) return rc;
-    store_str(c->eng, h, head);
-    store_str(c->eng, t, tail);
-    return FHS_OK;
+    return split_at_op(c, s, n, {{pos_lo, pos_hi}, 2}, head, tail);
 }
 
 int fhs_str_compare(fhs_ctx *c, const fhs_char_t *a, size_t na, const fhs_char_t *b, size_t nb, int cmp, fhs_char_t *out) {

@@ -105,15 +105,6 @@ FChar Strings::is_empty(const FStr &s) {                     // mod.rs:431-451
     return result;
 }
 
-FChar Strings::len(const FStr &s) {                          // mod.rs:478-493
-    const FChar zero = t(0);
-    if (s.empty()) return zero;
-    if (fused()) return f_len(s);
-    FChar result = t(0);
-    for (const FChar &c : s) result = ch_add(result, ch_ne(c, zero));
-    return result;
-}
-
 FStr Strings::repeat_clear(const FStr &s, size_t n) {        // mod.rs:517-538
     if (n == 0) return {};
     FStr r;
@@ -239,149 +230,111 @@ FStr Strings::shorter_from(const FStr &s, const FStr &from, const FStr &to, cons
     return result;
 }
 
-FChar Strings::rfind(const FStr &s_in, const FStr &pat) {    // mod.rs:727-790
-    const FChar one = t(1), zero = t(0);
-    FStr s = s_in;
-    s.push_back(zero);
-    FChar pos = t(FHS_MAX_FIND_LENGTH);
-    if (s.size() >= FHS_MAX_FIND_LENGTH + pat.size()) {
-        err = {FHS_ERR_LIMIT, "Maximum supported size for find reached"};
-        return zero;
-    }
-    if (fused()) return f_rfind(s, pat);
-    if (pat.empty()) {
-        FChar last = zero;
-        for (size_t i = 0; i < s.size(); i++) last = ch_ite(ch_ne(s[i], zero), t((uint8_t)(i + 1)), last);
-        return last;
-    }
-    if (pat.size() > s.size()) return t(255);
-    const size_t end = adjust_end_of_pattern(s.size() - pat.size());
-    for (size_t i = 0; i < end; i++) {
-        FChar flag = one;
-        for (size_t j = 0; j < pat.size(); j++) flag = ch_bitand(flag, ch_eq(pat[j], s[i + j]));
-        pos = ch_ite(flag, t((uint8_t)i), pos);
-    }
-    return pos;
+// ---------------------------------------------------------------------------------------------
+// positions and counts: find, rfind, len and the flag count, each written once for a result of one half (the reference's
+// u8: absent = 255, strings below 255 + |pattern| characters) or two (lo, hi: absent = 65535, below 65535 + |pattern|).
+// Everything else is the reference's, quirks included (src/main.rs:20, mod.rs:742-744, :1025-1027, :1044).
+// ---------------------------------------------------------------------------------------------
+static unsigned absent_value(size_t halves) { return halves == 1 ? FHS_MAX_FIND_LENGTH : FHS_WIDE_ABSENT; }
+
+bool Strings::limit_reached(size_t n, size_t m, size_t halves) {
+    return n >= (size_t)(halves == 1 ? FHS_MAX_FIND_LENGTH : FHS_MAX_FIND_LENGTH_WIDE) + m;
 }
 
-FChar Strings::find(const FStr &s, const FStr &pat) {        // mod.rs:1010-1053
-    if (s.empty() && pat.empty()) return t(0);
-    const FChar one = t(1);
-    FChar pos = t(FHS_MAX_FIND_LENGTH);
-    if (s.size() >= FHS_MAX_FIND_LENGTH + pat.size()) {      // :1025-1027
-        err = {FHS_ERR_LIMIT, "Maximum supported size for find reached"};
-        return t(0);
-    }
-    if (pat.size() > s.size()) return t(255);
-    if (fused()) return f_find(s, pat);
-    for (size_t i = s.size() - pat.size() + 1; i-- > 0;) {
-        FChar flag = one;
-        for (size_t j = pat.size(); j-- > 0;) flag = ch_bitand(flag, ch_eq(pat[j], s[i + j]));
-        pos = ch_ite(flag, t((uint8_t)i), pos);
-    }
-    return pos;
+Pos Strings::pos_trivial(unsigned v, size_t halves) const {
+    Pos p;
+    for (size_t h = 0; h < halves; h++) p.push_back(t((uint8_t)(v >> (8 * h))));
+    return p;
 }
-
-// ---------------------------------------------------------------------------------------------
-// wide positions and counts: the loops above with the u8 position / counter as two chars (lo, hi), value lo + 256 hi.
-// The reference stops at 255 (src/main.rs:20, mod.rs:742-744, :1025-1027, :1044); everything else is kept, quirks included.
-// ---------------------------------------------------------------------------------------------
-bool Strings::wide_limit_reached(size_t n, size_t m) { return n >= (size_t)FHS_MAX_FIND_LENGTH_WIDE + m; }
-
-FWide Strings::wide_trivial(unsigned v) const { return {t((uint8_t)(v & 255)), t((uint8_t)((v >> 8) & 255))}; }
 
 FChar Strings::num_char(const Num &v, size_t first) {
     FChar c;
     for (int k = 0; k < 4; k++) c.b[k] = v[first + k];
     return c;
 }
-FWide Strings::num_wide(const Num &v) { return {num_char(v, 0), num_char(v, 4)}; }
-
-void Strings::wide_add_flag(FWide &counter, const FChar &flag) {
-    FChar lo = ch_add(counter.lo, flag);
-    counter.hi = ch_add(counter.hi, ch_lt(lo, counter.lo));  // the low char wrapped: carry
-    counter.lo = lo;
+Pos Strings::num_pos(const Num &v) {
+    Pos p;
+    for (size_t first = 0; first + 4 <= v.size(); first += 4) p.push_back(num_char(v, first));
+    return p;
 }
 
-FWide Strings::find_wide(const FStr &s, const FStr &pat) {   // mod.rs:1010-1053 with a 16-bit position
-    if (s.empty() && pat.empty()) return wide_trivial(0);
-    if (wide_limit_reached(s.size(), pat.size())) {          // :1025-1027
-        err = {FHS_ERR_LIMIT, "Maximum supported size for find reached"};
-        return wide_trivial(0);
-    }
-    if (pat.size() > s.size()) return wide_trivial(FHS_WIDE_ABSENT);
-    if (fused()) return num_wide(f_find_digits(f_find_window_flags(s, pat), 8));
-    const FChar one = t(1);
-    FWide pos = wide_trivial(FHS_WIDE_ABSENT);
-    for (size_t i = s.size() - pat.size() + 1; i-- > 0;) {
-        FChar flag = one;
-        for (size_t j = pat.size(); j-- > 0;) flag = ch_bitand(flag, ch_eq(pat[j], s[i + j]));
-        pos.lo = ch_ite(flag, t((uint8_t)(i & 255)), pos.lo);
-        pos.hi = ch_ite(flag, t((uint8_t)(i >> 8)), pos.hi);
-    }
-    return pos;
+// as written: pos = flag ? v : pos, one if_then_else per half
+void Strings::pos_set_if(Pos &pos, const FChar &flag, size_t v) {
+    for (size_t h = 0; h < pos.size(); h++) pos[h] = ch_ite(flag, t((uint8_t)(v >> (8 * h))), pos[h]);
 }
 
-FWide Strings::rfind_wide(const FStr &s_in, const FStr &pat) {   // mod.rs:727-790 with a 16-bit position
-    const FChar one = t(1), zero = t(0);
+// as written: counter += flag; with two halves the carry is the wrap of the low one
+void Strings::pos_add_flag(Pos &counter, const FChar &flag) {
+    FChar lo = ch_add(counter[0], flag);
+    if (counter.size() > 1) counter[1] = ch_add(counter[1], ch_lt(lo, counter[0]));
+    counter[0] = lo;
+}
+
+// as written: AND_j eq(pat[j], s[at + j]), chained from the last j down (find) or from the first up (rfind)
+FChar Strings::window_eq(const FStr &s, size_t at, const FStr &pat, bool downwards) {
+    FChar flag = t(1);
+    for (size_t k = 0; k < pat.size(); k++) {
+        const size_t j = downwards ? pat.size() - 1 - k : k;
+        flag = ch_bitand(flag, ch_eq(pat[j], s[at + j]));
+    }
+    return flag;
+}
+
+Pos Strings::rfind(const FStr &s_in, const FStr &pat, size_t halves) {   // mod.rs:727-790
+    const FChar zero = t(0);
     FStr s = s_in;
     s.push_back(zero);                                       // :737
-    if (wide_limit_reached(s.size(), pat.size())) {          // :742-744
-        err = {FHS_ERR_LIMIT, "Maximum supported size for find reached"};
-        return wide_trivial(0);
+    if (limit_reached(s.size(), pat.size(), halves)) {       // :742-744
+        err = {FHS_ERR_LIMIT, LIMIT_MSG};
+        return pos_trivial(0, halves);
     }
-    if (fused()) return num_wide(f_rfind_digits(s, pat, 8));
+    if (fused()) return num_pos(f_rfind_digits(s, pat, 4 * halves));
     if (pat.empty()) {                                       // :747-760
-        FWide last = wide_trivial(0);
-        for (size_t i = 0; i < s.size(); i++) {
-            FChar nz = ch_ne(s[i], zero);
-            last.lo = ch_ite(nz, t((uint8_t)((i + 1) & 255)), last.lo);
-            last.hi = ch_ite(nz, t((uint8_t)((i + 1) >> 8)), last.hi);
-        }
+        Pos last = pos_trivial(0, halves);
+        for (size_t i = 0; i < s.size(); i++) pos_set_if(last, ch_ne(s[i], zero), i + 1);
         return last;
     }
-    if (pat.size() > s.size()) return wide_trivial(FHS_WIDE_ABSENT);
-    FWide pos = wide_trivial(FHS_WIDE_ABSENT);
+    Pos pos = pos_trivial(absent_value(halves), halves);
+    if (pat.size() > s.size()) return pos;
     const size_t end = adjust_end_of_pattern(s.size() - pat.size());
-    for (size_t i = 0; i < end; i++) {
-        FChar flag = one;
-        for (size_t j = 0; j < pat.size(); j++) flag = ch_bitand(flag, ch_eq(pat[j], s[i + j]));
-        pos.lo = ch_ite(flag, t((uint8_t)(i & 255)), pos.lo);
-        pos.hi = ch_ite(flag, t((uint8_t)(i >> 8)), pos.hi);
-    }
+    for (size_t i = 0; i < end; i++) pos_set_if(pos, window_eq(s, i, pat, false), i);
     return pos;
 }
 
-FWide Strings::len_wide(const FStr &s) {                     // mod.rs:478-493 with a 16-bit counter
-    if (s.empty()) return wide_trivial(0);
-    if (fused()) {
-        std::vector<Ref> nz;
-        for (const FChar &c : s) nz.push_back(char_zero_test(c, false));
-        return num_wide(count_flags(nz, 8));
+Pos Strings::find(const FStr &s, const FStr &pat, size_t halves) {       // mod.rs:1010-1053
+    if (s.empty() && pat.empty()) return pos_trivial(0, halves);
+    if (limit_reached(s.size(), pat.size(), halves)) {       // :1025-1027
+        err = {FHS_ERR_LIMIT, LIMIT_MSG};
+        return pos_trivial(0, halves);
     }
-    const FChar zero = t(0);
-    FWide result = wide_trivial(0);
-    for (const FChar &c : s) wide_add_flag(result, ch_ne(c, zero));
-    return result;
+    Pos pos = pos_trivial(absent_value(halves), halves);
+    if (pat.size() > s.size()) return pos;
+    if (fused()) return num_pos(f_find_digits(f_find_window_flags(s, pat), 4 * halves));
+    for (size_t i = s.size() - pat.size() + 1; i-- > 0;) pos_set_if(pos, window_eq(s, i, pat, true), i);
+    return pos;
 }
 
-FWide Strings::count_flags_wide(const FStr &flags) {
-    if (flags.empty()) return wide_trivial(0);
+// len counts the characters that are not NUL (mod.rs:478-493), count_flags the 0/1 flag chars that are set
+Pos Strings::count(const FStr &s, bool are_flags, size_t halves) {
+    if (s.empty()) return pos_trivial(0, halves);
     if (fused()) {
         std::vector<Ref> f;
-        for (const FChar &c : flags) f.push_back(c.b[0]);
-        return num_wide(count_flags(f, 8));
+        for (const FChar &c : s) f.push_back(are_flags ? c.b[0] : char_zero_test(c, false));
+        return num_pos(count_flags(f, 4 * halves));
     }
-    FWide result = wide_trivial(0);
-    for (const FChar &c : flags) wide_add_flag(result, c);
+    const FChar zero = t(0);
+    Pos result = pos_trivial(0, halves);
+    for (const FChar &c : s) pos_add_flag(result, are_flags ? c : ch_ne(c, zero));
     return result;
 }
+Pos Strings::len(const FStr &s, size_t halves) { return count(s, false, halves); }
+Pos Strings::count_flags(const FStr &flags, size_t halves) { return count(flags, true, halves); }
 
 FChar Strings::eq(const FStr &a, const FStr &b) {            // mod.rs:1122-1149
     if (fused()) return f_eq(a, b);
     const FChar zero = t(0), one = t(1);
     FChar is_eq = one;
-    FChar len_ne = ch_ne(len(a), len(b));
+    FChar len_ne = ch_ne(len(a)[0], len(b)[0]);
     for (size_t i = 0; i < std::min(a.size(), b.size()); i++) {
         FChar same = ch_eq(a[i], b[i]);
         FChar both0 = ch_bitand(ch_eq(a[i], zero), ch_eq(b[i], zero));
@@ -515,7 +468,7 @@ FChar Strings::comparison(const FStr &a_in, const FStr &b_in, int cmp) {   // mo
         ret = ch_ite(flag, c, ret);
     }
     FChar sub_eq = ch_eq(ret, t255);
-    FChar l1 = len(a), l2 = len(b);
+    FChar l1 = len(a)[0], l2 = len(b)[0];
     FChar leq = ch_eq(l1, l2), lgt = ch_gt(l1, l2), llt = ch_lt(l1, l2);
     FChar by_len;
     switch (cmp) {
@@ -625,7 +578,7 @@ std::vector<FStr> Strings::xsplit(const FStr &s_in, const FStr &pat, bool inclus
     FStr mask(size, one);
     if (n) allow = ch_ne(*n, zero);
     if (!reverse && pat.empty() && n) {                      // split.rs:925-937
-        FChar enc_len = len(s);
+        FChar enc_len = len(s)[0];
         FChar skip = ch_bitand(ch_gt(*n, one), ch_le(*n, enc_len));
         cur_buf = s_ite(skip, t(1), cur_buf);
     }
@@ -1095,11 +1048,9 @@ std::vector<Ref> Strings::prefix_or(const std::vector<Ref> &f) {
     return p;
 }
 
-// find (mod.rs:1010-1053) re-associated: window flags, exclusive prefix OR, first = f & !prefix,
-// position digits as sums of first_i * digit(i) (at most one term is non-zero), 255 when absent.
-FChar Strings::f_find(const FStr &s, const FStr &pat) { return f_find_from_flags(f_find_window_flags(s, pat)); }
-
-// the match flag of every window of `s` (the first two dependency levels of find: nibble tests, AND per window)
+// find (mod.rs:1010-1053) re-associated: window flags, exclusive prefix OR, and the index of the first flag set from
+// the prefix ORs (first_index), 255 / 65535 when absent.
+// The match flag of every window of `s` (the first two dependency levels of find: nibble tests, AND per window)
 std::vector<Ref> Strings::f_find_window_flags(const FStr &s, const FStr &pat) {
     if (s.size() < pat.size()) return {};
     const size_t W = s.size() - pat.size() + 1;
@@ -1108,26 +1059,16 @@ std::vector<Ref> Strings::f_find_window_flags(const FStr &s, const FStr &pat) {
     return f;
 }
 
-// ... and the rest of find on ALL window flags in string order: index of the first one set, 255 if none.  The sharded
-// find exchanges the flags and runs this part on every rank (fhs_dist_str_find).
-// The wide form (8 digits, W <= 65536) is the thermometer route at every length.
+// ... and the rest of find on ALL window flags in string order: index of the first one set as 4 or 8 digits (at most
+// 4^digits flags: the limit on the string's length sees to that), every digit 3 if none.
 Strings::Num Strings::f_find_digits(const std::vector<Ref> &f, size_t digits) {
     std::vector<Ref> p = prefix_or(f);
     Ref found = or_tree(f);
     return first_index(p, found, digits);
 }
 
-FChar Strings::f_find_from_flags(const std::vector<Ref> &f) {
-    const size_t W = f.size();
-    if (W <= 256) return num_char(f_find_digits(f, 4));      // 255 = 3,3,3,3 when absent (:1023)
-    std::vector<Ref> p = prefix_or(f);
-    Ref found = or_tree(f);
-    std::vector<Ref> first(W);
-    for (size_t i = 0; i < W; i++) first[i] = pbs(lin(e_, {{2, &f[i]}, {1, &p[i]}}), LUT_IS2);
-    Ref one = trivial_block(e_, 1);
-    Ref nf = lin(e_, {{1, &one}, {-1, &found}});
-    return position_of(first, 0, &nf, 255);
-}
+// The sharded find exchanges the flags and runs this part on every rank (fhs_dist_str_find): a u8 position, 255 if none
+FChar Strings::f_find_from_flags(const std::vector<Ref> &f) { return num_char(f_find_digits(f, 4)); }
 
 // Index of the first set flag from the exclusive prefix ORs before[j] = OR(f[0 .. j-1]) (before[W] = found): the flags
 // g[j] = found - before[j] = [the first match sits at index >= j] form a thermometer, so floor(index / 4^d) = sum_r
@@ -1323,17 +1264,13 @@ Ref Strings::char_significant(const FChar &c) {
     return lin(e_, {{1, &one}, {-1, &bad}});
 }
 
-// u8 position encoded by one-hot flags: sum_i pick_i * (i + offset) digit-wise (at most one pick is set);
-// when `absent_flag` is set the result is `absent_value` (255 for find/rfind, mod.rs:1023).
+// Position encoded by one-hot flags: sum_i pick_i * (i + offset) digit-wise (at most one pick is set);
+// when `absent_flag` is set the result is `absent_value` (255 for rfind, mod.rs:1023).
 // Noise: a sum of k bootstrap outputs with weights c carries sum c^2 output variances into the next bootstrap, so
 // the weighted picks are grouped by WEIGHT (sum of digit^2 <= FHS_NOISE_BUDGET_SUM_C2, not by count), every group is
 // refreshed with LUT_MSG before groups are added up, and the digits handed back to the caller are refreshed too:
 // like every op of the reference (fheasciichar.rs:35-104) the result is a fresh, clean-carry ciphertext.
-// `digits` = 8: a 16-bit position, absent_value up to 65535.
-FChar Strings::position_of(const std::vector<Ref> &pick, size_t off, const Ref *absent_flag, int absent_value) {
-    return num_char(position_of(pick, off, absent_flag, absent_value, 4));
-}
-
+// `digits` = 4: a u8 position; 8: a 16-bit one, absent_value up to 65535.
 Strings::Num Strings::position_of(const std::vector<Ref> &pick, size_t off, const Ref *absent_flag, int absent_value,
                                   size_t digits) {
     const size_t W = pick.size();
@@ -1398,10 +1335,7 @@ Strings::Num Strings::position_of(const std::vector<Ref> &pick, size_t off, cons
 
 // rfind (mod.rs:727-790) re-associated: the LAST matching window wins (the loop ascends and overwrites);
 // `s` already carries the NUL pushed at :737
-FChar Strings::f_rfind(const FStr &s, const FStr &pat) { return num_char(f_rfind_digits(s, pat, 4)); }
-
 Strings::Num Strings::f_rfind_digits(const FStr &s, const FStr &pat, size_t digits) {
-    const int absent = digits == 4 ? FHS_MAX_FIND_LENGTH : FHS_WIDE_ABSENT;
     if (pat.empty()) {                                      // :747-760: index after the last non-NUL char
         std::vector<Ref> nz(s.size());
         for (size_t i = 0; i < s.size(); i++) nz[i] = char_nonzero(s[i]);
@@ -1420,7 +1354,7 @@ Strings::Num Strings::f_rfind_digits(const FStr &s, const FStr &pat, size_t digi
     Ref found = or_tree(f);
     Ref one = trivial_block(e_, 1);
     Ref nf = lin(e_, {{1, &one}, {-1, &found}});
-    return position_of(last, 0, &nf, absent, digits);
+    return position_of(last, 0, &nf, (int)absent_value(digits / 4), digits);
 }
 
 // ends_with (mod.rs:241-288) re-associated: the result is the match flag of the LAST window that
@@ -1687,10 +1621,8 @@ FStr Strings::f_compact(const FStr &s) {
     return cur;
 }
 
-// sum of 0/1 flags mod 256: groups of 15 -> (low, high) digit pair, then 4-operand radix adds
-FChar Strings::count_flags(std::vector<Ref> flags) { return num_char(count_flags(flags, 4)); }
-
-// ... mod 4^digits: with 8 digits the carry runs on through digits 4 to 7 (a carry out of digit 7 needs 65536 flags), but
+// sum of 0/1 flags mod 4^digits: groups of 15 -> (low, high) digit pair, then 4-operand radix adds.
+// With 8 digits the carry runs on through digits 4 to 7 (a carry out of digit 7 needs 65536 flags), but
 // only as far as a partial sum can reach: a digit above the largest possible value stays a trivial 0 instead of two
 // bootstraps on a carry that is always 0.  The four low digits are always computed, as the u8 form has them.
 Strings::Num Strings::count_flags(const std::vector<Ref> &flags, size_t digits) {
@@ -1743,12 +1675,6 @@ Strings::Num Strings::count_flags(const std::vector<Ref> &flags, size_t digits) 
     return nums[0];
 }
 
-FChar Strings::f_len(const FStr &s) {
-    std::vector<Ref> nz;
-    for (const FChar &c : s) nz.push_back(char_zero_test(c, false));
-    return count_flags(nz);
-}
-
 FChar Strings::f_eq(const FStr &a, const FStr &b) {
     // (both zero) or equal == equal, so the per-position test of mod.rs:1137-1146 is a plain equality
     std::vector<Ref> f;
@@ -1786,24 +1712,13 @@ FStr Strings::f_case(const FStr &s, bool to_lower) {
 
 // ---------------------------------------------------------------------------------------------
 // encrypted positions as operands: char_at, substr, take, split_at.  The reference has no such
-// method -- its positions are only ever decrypted.  A position is the u8 of find / rfind / len or the (lo, hi) pair of
-// their wide forms; its value is taken literally as an index into the buffer, NULs and all.
+// method -- its positions are only ever decrypted.  A position is what find / rfind / len return, one half or two; its
+// value is taken literally as an index into the buffer, NULs and all.
 // ---------------------------------------------------------------------------------------------
-FChar Strings::char_at(const FStr &s, const FChar &pos) { return pos_substr(s, Pos{pos}, 1)[0]; }
-FChar Strings::char_at(const FStr &s, const FWide &pos) { return pos_substr(s, Pos{pos.lo, pos.hi}, 1)[0]; }
-FStr Strings::substr(const FStr &s, const FChar &pos, size_t count) { return pos_substr(s, Pos{pos}, count); }
-FStr Strings::substr(const FStr &s, const FWide &pos, size_t count) { return pos_substr(s, Pos{pos.lo, pos.hi}, count); }
-FStr Strings::take(const FStr &s, const FChar &pos) { return pos_take(s, Pos{pos}); }
-FStr Strings::take(const FStr &s, const FWide &pos) { return pos_take(s, Pos{pos.lo, pos.hi}); }
-void Strings::split_at(const FStr &s, const FChar &pos, FStr *head, FStr *tail) {
-    const Pos p{pos};
-    *head = pos_take(s, p);                                  // the bits of the shift are those the thermometer's digits
-    *tail = pos_substr(s, p, s.size());                      // came from: one refresh, found again by the engine
-}
-void Strings::split_at(const FStr &s, const FWide &pos, FStr *head, FStr *tail) {
-    const Pos p{pos.lo, pos.hi};
-    *head = pos_take(s, p);
-    *tail = pos_substr(s, p, s.size());
+FChar Strings::char_at(const FStr &s, const Pos &pos) { return substr(s, pos, 1)[0]; }
+void Strings::split_at(const FStr &s, const Pos &pos, FStr *head, FStr *tail) {
+    *head = take(s, pos);                                    // the bits of the shift are those the thermometer's digits
+    *tail = substr(s, pos, s.size());                        // came from: one refresh, found again by the engine
 }
 
 // as written: the position against a clear index with the char operators, the wide form from its two halves
@@ -1818,7 +1733,7 @@ FChar Strings::pos_gt(const Pos &pos, size_t j) {
     return ch_bitor(ch_gt(pos[1], jh), ch_bitand(ch_eq(pos[1], jh), ch_gt(pos[0], jl)));
 }
 
-FStr Strings::pos_substr(const FStr &s, const Pos &pos, size_t count) {
+FStr Strings::substr(const FStr &s, const Pos &pos, size_t count) {
     const size_t n = s.size();
     FStr out(count, t(0));
     if (n == 0 || count == 0) return out;
@@ -1831,7 +1746,7 @@ FStr Strings::pos_substr(const FStr &s, const Pos &pos, size_t count) {
     return out;
 }
 
-FStr Strings::pos_take(const FStr &s, const Pos &pos) {
+FStr Strings::take(const FStr &s, const Pos &pos) {
     const size_t n = s.size();
     if (n == 0) return {};
     if (fused()) return f_pos_take(s, pos_digits(pos));

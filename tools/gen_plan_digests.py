@@ -31,6 +31,7 @@ if ROOT not in sys.path:
 
 FIXTURE = os.path.join(ROOT, "tests", "golden", "plan_digests.json")
 TR_UPLOAD, TR_ROW, TR_EXT, TR_GROUP_END = 1, 2, 3, 4
+FHS_ERR_LIMIT = -4
 
 
 def _read_words(sk, fn, *args):
@@ -102,11 +103,15 @@ def _hash(*chunks):
 
 
 def _chars_of(result):
-    from fhestring_amd.api import FheAsciiChar
+    from fhestring_amd.api import FheAsciiChar, FheSplit, FheU16
     if isinstance(result, FheAsciiChar):
         return [result]
     if hasattr(result, "chars"):
         return list(result.chars)
+    if isinstance(result, FheU16):
+        return [result.lo, result.hi]
+    if isinstance(result, FheSplit):
+        return _chars_of(result.buffers) + [result.pattern_found]
     out = []
     for r in result:
         out.extend(_chars_of(r))
@@ -114,7 +119,10 @@ def _chars_of(result):
 
 
 def record(body, mode=1, setup=None):
-    """one scenario on a fresh planner context -> its digest"""
+    """one scenario on a fresh planner context -> its digest.  A body that ends in an error of the library (FhsError, or
+    the OverflowError the binding makes of FHS_ERR_LIMIT) digests the error code with the statistics and the plan trace
+    recorded up to that point; a digest without an error is what it was before errors were digested."""
+    from fhestring_amd import FhsError
     from fhestring_amd.api import MyServerKey
     sk = MyServerKey.planner()
     try:
@@ -124,13 +132,19 @@ def record(body, mode=1, setup=None):
             setup(sk)
         sk.ctx._check(L.fhs_debug_plan_trace(h, 1))
         sk.stats(reset=True)
-        result = body(sk)
+        result, error = [], []
+        try:
+            result = body(sk)
+        except FhsError as err:
+            error = [{"error": err.code}]
+        except OverflowError:
+            error = [{"error": FHS_ERR_LIMIT}]
         trace = _read_words(sk, L.fhs_debug_plan_read)            # flushes
         parts = [(trace, _trace_token_mask(trace))]
         for ch in _chars_of(result):
             t = _read_words(sk, L.fhs_debug_char_terms, C.c_uint64(ch.h))
             parts.append((t, _terms_token_mask(t)))
-        return _hash(_rename(parts).tobytes(), sk.stats(), sk.level_widths(), sk.launch_groups())
+        return _hash(_rename(parts).tobytes(), sk.stats(), sk.level_widths(), sk.launch_groups(), *error)
     finally:
         sk.close()
 
