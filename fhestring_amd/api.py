@@ -1381,6 +1381,25 @@ class MyServerKey:
                                                            C.byref(out)))
         return FheAsciiChar(self, out.value)
 
+    def like_clear(self, string, pattern, escape=None, ignore_case=False):
+        """SQL LIKE / ILIKE against a clear pattern (fhs_str_like_clear): a 0/1 flag char.  `%` any
+        run of buffer characters, `_` one character that is not NUL, anything else itself; `escape` (one character) makes
+        the `%`, `_` or escape character behind it a literal.  Anchored at both ends: the match ends at the end of the
+        buffer or before a NUL.  pattern: str (ASCII) or bytes."""
+        s = self._chars(string)
+        data = pattern.encode("ascii") if isinstance(pattern, str) else bytes(pattern)
+        if escape is None:
+            esc = -1
+        else:
+            e = escape.encode("ascii") if isinstance(escape, str) else bytes(escape)
+            if len(e) != 1:
+                raise ValueError("escape must be one character")
+            esc = e[0]
+        out = C.c_uint64()
+        self.ctx._check(self.ctx._L.fhs_str_like_clear(self.ctx._h, _harr(s), len(s), data, len(data), esc,
+                                                       _K["FHS_LIKE_IGNORE_CASE"] if ignore_case else 0, C.byref(out)))
+        return FheAsciiChar(self, out.value)
+
     def starts_with(self, string, pattern, public_parameters=None):      # mod.rs:344
         return self._flag_op("starts_with", string, pattern)
 

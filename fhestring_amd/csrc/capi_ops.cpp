@@ -403,6 +403,23 @@ int fhs_str_contains_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char
     *out = store(c->eng, r);
     return FHS_OK;
 }
+// LIKE against a clear pattern.  The pattern is judged before the string is loaded: loading
+// refreshes noisy operands, which records bootstraps.
+int fhs_str_like_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, int escape, uint32_t flags,
+                       fhs_char_t *out) {
+    if (!ok_all(c, s, n) || (m && !pat) || !out) return bad(c);
+    if (flags & ~(uint32_t)FHS_LIKE_IGNORE_CASE) return c->eng.ctx.fail(FHS_ERR_ARG, "fhs_str_like_clear: unknown flag bits");
+    std::vector<Strings::LikeTok> tok;
+    if (!Strings::like_parse(pat, m, escape, &tok))
+        return c->eng.ctx.fail(FHS_ERR_ARG, "fhs_str_like_clear: a NUL in the pattern, an escape byte that is 0, '%' or '_', or "
+                                            "an escape that is not followed by '%', '_' or itself");
+    Strings S(&c->eng);
+    const int known = Strings::like_trivial(tok, n);
+    FChar r = known >= 0 ? ch_trivial(&c->eng, (uint8_t)known)
+                         : S.like(load_str(c->eng, s, n), tok, (flags & FHS_LIKE_IGNORE_CASE) != 0);
+    *out = store(c->eng, r);
+    return FHS_OK;
+}
 int fhs_str_is_empty(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t *out) {
     if (!ok_all(c, s, n) || !out) return bad(c);
     Strings S(&c->eng);

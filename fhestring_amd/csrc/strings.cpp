@@ -1895,4 +1895,193 @@ FStr Strings::f_pos_take(const FStr &s, const Num &dg) {
     return out;
 }
 
+// ---------------------------------------------------------------------------------------------
+// LIKE against a clear pattern.  The reference has no such method; the semantics are those of
+//     re.match(rb'\A' + body + rb'(?=\x00|\Z)', buf, re.S [| re.I])
+// with body = [\x00-\xff]* for ANY, [^\x00] for ONE and the escaped byte for a literal, on the buffer as it is.
+// ---------------------------------------------------------------------------------------------
+bool Strings::like_parse(const char *pat, size_t m, int escape, std::vector<LikeTok> *out) {
+    if (escape != -1 && (escape <= 0 || escape > 255 || escape == '%' || escape == '_')) return false;
+    out->clear();
+    for (size_t i = 0; i < m; i++) {
+        const uint8_t c = (uint8_t)pat[i];
+        if (c == 0) return false;
+        if ((int)c == escape) {                              // e%, e_ and ee are the literals %, _ and e
+            const uint8_t d = i + 1 < m ? (uint8_t)pat[++i] : 0;
+            if (d != '%' && d != '_' && (int)d != escape) return false;
+            out->push_back({LikeTok::LIT, d});
+        } else if (c == '%') out->push_back({LikeTok::ANY, 0});
+        else if (c == '_') out->push_back({LikeTok::ONE, 0});
+        else out->push_back({LikeTok::LIT, c});
+    }
+    return true;
+}
+
+int Strings::like_trivial(const std::vector<LikeTok> &pat, size_t n) {
+    size_t fixed = 0;
+    for (const LikeTok &k : pat) fixed += k.kind != LikeTok::ANY;
+    if (fixed > n) return 0;
+    return fixed == 0 && !pat.empty() ? 1 : -1;
+}
+
+static bool ascii_letter(uint8_t c) { return (c >= 'A' && c <= 'Z') || (c >= 'a' && c <= 'z'); }
+
+FChar Strings::like(const FStr &s, const std::vector<LikeTok> &pat, bool ignore_case) {
+    const int k = like_trivial(pat, s.size());
+    if (k >= 0) return t((uint8_t)k);
+    return fused() ? f_like(s, pat, ignore_case) : like_as_written(s, pat, ignore_case);
+}
+
+// As written: the textbook dynamic programme, one row per token.  reach[j][i] = the first j tokens match the first i
+// characters; LIT: reach[j-1][i-1] & eq(s[i-1], c) (either case OR-ed under ignore_case), ONE: reach[j-1][i-1] &
+// ne(s[i-1], 0), ANY: reach[j-1][i] | reach[j][i-1]; result OR_i reach[m][i] & end[i], end[i] = (i == n) | eq(s[i], 0).
+// A flag that is a trivial constant is not sent through a bitand / bitor: x & 1 = x, x & 0 = 0, x | 0 = x, x | 1 = 1.
+FChar Strings::like_as_written(const FStr &s, const std::vector<LikeTok> &pat, bool ignore_case) {
+    const size_t n = s.size();
+    const FChar zero = t(0), one = t(1);
+    auto konst = [&](const FChar &f) {                       // 0 / 1 for a trivial flag, -1 for an encrypted one
+        int v = 0;
+        for (int k = 0; k < 4; k++) {
+            if (!e_->is_triv(f.b[k].id())) return -1;
+            v |= (e_->triv_val(f.b[k].id()) & 3) << (2 * k);
+        }
+        return v;
+    };
+    auto band = [&](const FChar &a, const FChar &b) {
+        const int ka = konst(a), kb = konst(b);
+        if (ka == 0 || kb == 0) return zero;
+        if (ka == 1) return b;
+        if (kb == 1) return a;
+        return ch_bitand(a, b);
+    };
+    auto bor = [&](const FChar &a, const FChar &b) {
+        const int ka = konst(a), kb = konst(b);
+        if (ka == 1 || kb == 1) return one;
+        if (ka == 0) return b;
+        if (kb == 0) return a;
+        return ch_bitor(a, b);
+    };
+    std::vector<std::vector<std::pair<int, FChar>>> tests(n);   // per character: (byte, eq(s[i], byte)); -1: ne(s[i], 0)
+    auto test = [&](size_t i, int c) {
+        for (const auto &kv : tests[i])
+            if (kv.first == c) return kv.second;
+        tests[i].emplace_back(c, c < 0 ? ch_ne(s[i], zero) : ch_eq(s[i], t((uint8_t)c)));
+        return tests[i].back().second;
+    };
+    std::vector<FChar> prev(n + 1, zero), cur(n + 1, zero);
+    prev[0] = one;
+    for (const LikeTok &k : pat) {
+        if (k.kind == LikeTok::ANY) {
+            cur[0] = prev[0];
+            for (size_t i = 1; i <= n; i++) cur[i] = bor(prev[i], cur[i - 1]);
+        } else {
+            cur[0] = zero;
+            for (size_t i = 1; i <= n; i++) {
+                if (konst(prev[i - 1]) == 0) { cur[i] = zero; continue; }
+                FChar hit = k.kind == LikeTok::ONE ? test(i - 1, -1) : test(i - 1, k.c);
+                if (k.kind == LikeTok::LIT && ignore_case && ascii_letter(k.c)) hit = bor(hit, test(i - 1, k.c ^ 0x20));
+                cur[i] = band(prev[i - 1], hit);
+            }
+        }
+        prev.swap(cur);
+    }
+    FChar result = zero;
+    for (size_t i = 0; i <= n; i++) {
+        if (konst(prev[i]) == 0) continue;
+        result = bor(result, band(prev[i], i == n ? one : test(i, 0)));
+    }
+    return result;
+}
+
+// Fused: the tokens split at ANY into segments.  A segment's window flag at i is window_match's AND over the nibble tests
+// of its literals -- is0(nibble - c) against any number of clear c is one blind rotation per nibble (rotation sharing), so
+// every segment of every pattern rides on the 2 n rotations contains_clear runs -- with the shared per-character flag
+// nz[i] = [s[i] != 0] for a ONE.  Segment k can END at lo_k + L_k + w (lo_k = the lengths before it, w < W = n - all
+// lengths + 1: further right the rest would not fit) iff its window there matches and the segment before it can end at
+// or before its start: E_k[w] = M_k[lo_k + w] & A_k[w], A_k = inclusive prefix OR of E_{k-1}; A_k[w] joins the last level
+// of the window's AND instead of a bootstrap of its own.  The first segment is tested at 0 only (no leading ANY), or A is
+// trivially 1 (and_tree drops it); the last one also carries end[j] = 1 - nz[j] (j < n; end[n] = 1) unless the pattern
+// ends in ANY, where the result is the OR of the last segment's flags: '%lit%' records what contains_clear(lit) records.
+// ignore_case: the cases of a letter share the low nibble and have high nibbles 4 / 6 or 5 / 7; the high-nibble flag is the
+// sum of two extractions of one rotation, charged as fully correlated by lin_c2 (4) -- an AND of 15 flags holds at most 8
+// of them: 8 * 4 + 7 = 39 of the budget of 64.
+FChar Strings::f_like(const FStr &s, const std::vector<LikeTok> &pat, bool ignore_case) {
+    const size_t n = s.size();
+    const Ref one = trivial_block(e_, 1);
+    std::vector<std::vector<LikeTok>> seg(1);
+    size_t fixed = 0;
+    for (const LikeTok &k : pat) {
+        if (k.kind == LikeTok::ANY) seg.emplace_back();
+        else { seg.back().push_back(k); fixed++; }
+    }
+    std::vector<Ref> nz(n);
+    auto nonzero = [&](size_t i) {
+        if (!nz[i]) nz[i] = char_zero_test(s[i], false);
+        return nz[i];
+    };
+    auto end_at = [&](size_t j) {
+        if (j == n) return one;
+        const Ref z = nonzero(j);
+        return lin(e_, {{1, &one}, {-1, &z}});
+    };
+    // AND of a window's flags and of `extra` (the flags that come from deeper in the DAG: they join the tree's last level)
+    auto window = [&](const std::vector<LikeTok> &sg, size_t at, const std::vector<Ref> &extra_in) {
+        std::vector<Ref> extra;
+        for (const Ref &x : extra_in) {
+            if (!e_->is_triv(x.id())) extra.push_back(x);
+            else if ((e_->triv_val(x.id()) & 1) == 0) return trivial_block(e_, 0);
+        }
+        std::vector<Ref> f;
+        for (size_t j = 0; j < sg.size(); j++) {
+            if (sg[j].kind == LikeTok::ONE) { f.push_back(nonzero(at + j)); continue; }
+            std::vector<Ref> a = block_eq_flags(s[at + j], t(sg[j].c));
+            if (ignore_case && ascii_letter(sg[j].c)) {      // the other case: the same low-nibble test, the other row
+                const std::vector<Ref> b = block_eq_flags(s[at + j], t(sg[j].c ^ 0x20));
+                a[1] = lin(e_, {{1, &a[1]}, {1, &b[1]}});
+            }
+            f.push_back(a[0]);
+            f.push_back(a[1]);
+        }
+        if (extra.empty()) return and_tree(f);
+        while (f.size() + extra.size() > 15) {
+            std::vector<Ref> nxt;
+            for (size_t i = 0; i < f.size(); i += 15)
+                nxt.push_back(and_tree(std::vector<Ref>(f.begin() + i, f.begin() + std::min(i + 15, f.size()))));
+            f.swap(nxt);
+        }
+        f.insert(f.end(), extra.begin(), extra.end());
+        return and_tree(f);
+    };
+    if (seg.size() == 1)                                     // no ANY: one segment, anchored at both ends
+        return ch_flag(e_, window(seg[0], 0, {end_at(fixed)}));
+    const size_t W = n - fixed + 1;
+    auto inclusive_or = [&](std::vector<Ref> f) {            // prefix_or is exclusive: one more (unused) flag behind
+        f.push_back(trivial_block(e_, 0));
+        const std::vector<Ref> p = prefix_or(f);
+        return std::vector<Ref>(p.begin() + 1, p.end());
+    };
+    std::vector<Ref> E, A;                                   // E: where the last segment done can end; A: made from E on demand
+    size_t lo = seg[0].size();
+    if (seg[0].empty()) A.assign(W, one);
+    else {
+        E.assign(1, window(seg[0], 0, {}));
+        A.assign(W, E[0]);
+    }
+    bool a_ready = true;
+    for (size_t k = 1; k + 1 < seg.size(); k++) {
+        if (seg[k].empty()) continue;                        // adjacent ANYs
+        if (!a_ready) A = inclusive_or(E);
+        E.resize(W);
+        for (size_t w = 0; w < W; w++) E[w] = window(seg[k], lo + w, {A[w]});
+        lo += seg[k].size();
+        a_ready = false;
+    }
+    const std::vector<LikeTok> &last = seg.back();
+    if (last.empty()) return ch_flag(e_, or_tree(E));        // fixed > 0: some segment has been done
+    if (!a_ready) A = inclusive_or(E);
+    std::vector<Ref> R(W);
+    for (size_t w = 0; w < W; w++) R[w] = window(last, lo + w, {A[w], end_at(lo + w + last.size())});
+    return ch_flag(e_, or_tree(R));
+}
+
 }  // namespace fhs

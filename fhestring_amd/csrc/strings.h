@@ -42,6 +42,16 @@ class Strings {
     FStr substr(const FStr &s, const Pos &pos, size_t count);
     FStr take(const FStr &s, const Pos &pos);
     void split_at(const FStr &s, const Pos &pos, FStr *head, FStr *tail);
+    // SQL LIKE against a CLEAR pattern (the reference has none).  Tokens: ANY = '%', any run of buffer
+    // characters, NULs included; ONE = '_', one character that is not NUL; otherwise a literal byte, under ignore_case
+    // (ASCII letters of the pattern only) either case of it.  Anchored at index 0; ends at j == n or s[j] == NUL.
+    struct LikeTok { enum Kind : uint8_t { LIT, ONE, ANY } kind; uint8_t c; };
+    // pat[m] with an optional escape byte (-1: none) -> tokens; false on a NUL, a bad escape byte or a dangling escape
+    static bool like_parse(const char *pat, size_t m, int escape, std::vector<LikeTok> *out);
+    // what the token counts alone decide on n characters: 0 (more ONE / LIT tokens than characters), 1 (ANY tokens only),
+    // -1 otherwise
+    static int like_trivial(const std::vector<LikeTok> &pat, size_t n);
+    FChar like(const FStr &s, const std::vector<LikeTok> &pat, bool ignore_case);
     FChar eq(const FStr &a, const FStr &b);
     FChar ne(const FStr &a, const FStr &b);
     FChar eq_ignore_case(const FStr &a, const FStr &b);
@@ -124,6 +134,8 @@ class Strings {
     // ---- fused forms of the tests, comparisons and maps ----
     FChar f_contains(const FStr &s, const FStr &needle);
     FChar f_ends_with(const FStr &s, const FStr &needle, std::vector<Ref> *pick_out);
+    FChar like_as_written(const FStr &s, const std::vector<LikeTok> &pat, bool ignore_case);
+    FChar f_like(const FStr &s, const std::vector<LikeTok> &pat, bool ignore_case);
     FChar f_eq(const FStr &a, const FStr &b);
     FChar f_eq_ignore_case(const FStr &a, const FStr &b);
     // lexicographic order as a tree of three-state values s = sign(a - b) in {-1, 0, 1}, most significant first

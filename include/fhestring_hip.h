@@ -316,6 +316,22 @@ int fhs_str_take_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_
 int fhs_str_split_at(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos, fhs_char_t *head /*[n]*/, fhs_char_t *tail /*[n]*/);
 int fhs_str_split_at_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t pos_lo, fhs_char_t pos_hi, fhs_char_t *head /*[n]*/, fhs_char_t *tail /*[n]*/);
 
+/* ---- LIKE against a clear pattern ----------------------------------------------------------------------------
+ * SQL LIKE / ILIKE on the n characters of s (the reference has no such method); *out is a 0/1 flag char.  In the m
+ * bytes of pat, '%' matches any run of buffer characters (none included, NULs included), '_' exactly one character
+ * that is not NUL, any other byte itself; with an escape byte e the pairs e%, e_ and ee are the literals %, _ and e.
+ * The match starts at index 0 and must end at an index j with j == n or buf[j] == 0: on text followed by NUL padding
+ * (what every method here produces) this is SQL LIKE on the text; on any buffer it is Python's
+ *   re.match(rb'\A' + body + rb'(?=\x00|\Z)', buf, re.S)
+ * with body = [\x00-\xff]* for '%', [^\x00] for '_' and the escaped byte for a literal.  FHS_LIKE_IGNORE_CASE folds
+ * the ASCII letters of the pattern (re.I).  An empty pattern matches the empty string only, a pattern of '%' alone
+ * everything, and a pattern with more tokens other than '%' than n nothing: the last two record nothing.  Both modes;
+ * no length limit.  FHS_ERR_ARG, before anything is recorded: a NUL in pat, an escape byte that is 0, '%' or '_', an
+ * escape at the end of pat or before anything but '%', '_' or itself, unknown flag bits, a null out. */
+#define FHS_LIKE_IGNORE_CASE 1
+int fhs_str_like_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, int escape /* -1: none, else 1..255 */,
+                       uint32_t flags, fhs_char_t *out);
+
 /* ---- multi-GPU inside the library (one process per GPU, RCCL over xGMI) ---------------------------------
  * north_star: "characters of an FheString are independent PBS batches, so long strings shard across the GPUs of one
  * node with an RCCL gather".  fhs_dist_init creates this context's communicator (librccl.so.1 is loaded at run time;

@@ -241,6 +241,15 @@ int main() {
         fhs_char_t r = 0, f = 0;
         CHECK(fhs_str_contains(c, s.data(), s.size(), p.data(), p.size(), &r) == FHS_OK);
         CHECK(fhs_str_contains_clear(c, s.data(), s.size(), "abc", 3, &r) == FHS_OK);
+        // LIKE: every token kind, segments of every position, escapes, both case modes; the malformed patterns
+        for (const char *pat : {"", "%", "a%", "%c", "%ab%", "ab c%b_", "a%b%c%_", "_%_", "%%a%%", "ab cab cab cab cab c%", "a!%b!_!!%"})
+            for (uint32_t fl = 0; fl < 2; fl++)
+                CHECK(fhs_str_like_clear(c, s.data(), s.size(), pat, std::strlen(pat), '!', fl, &r) == FHS_OK && r);
+        CHECK(fhs_str_like_clear(c, s.data(), s.size(), "a\0b", 3, -1, 0, &r) == FHS_ERR_ARG);
+        CHECK(fhs_str_like_clear(c, s.data(), s.size(), "ab!", 3, '!', 0, &r) == FHS_ERR_ARG);
+        CHECK(fhs_str_like_clear(c, s.data(), s.size(), "ab", 2, '%', 0, &r) == FHS_ERR_ARG);
+        CHECK(fhs_str_like_clear(c, s.data(), s.size(), "ab", 2, -1, 2, &r) == FHS_ERR_ARG);
+        CHECK(fhs_str_like_clear(c, s.data(), s.size(), "ab", 2, -1, 0, nullptr) == FHS_ERR_ARG);
         CHECK(fhs_str_starts_with(c, s.data(), s.size(), p.data(), p.size(), &r) == FHS_OK);
         CHECK(fhs_str_ends_with(c, s.data(), s.size(), p.data(), p.size(), &r) == FHS_OK);
         CHECK(fhs_str_find(c, s.data(), s.size(), p.data(), p.size(), &r) == FHS_OK);
