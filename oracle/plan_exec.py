@@ -4,12 +4,15 @@ A planner context (fhs_ctx_create_planner: host logic only, no device) records a
 context would -- fused DAG, rotation-sharing groups, launch groups -- and with fhs_debug_plan_trace writes what it WOULD
 run (include/fhestring_hip.h "plan trace").  `PlanRun` feeds real ciphertexts through that list with the oracle's
 bootstrap (oracle/tfhe_oracle.c: any mode; 6 = the AVX2 + FMA f64-FFT port that bench.py reports as cpu_baseline) on host
-threads, linear combinations in numpy (wrapping u64).  Two uses:
+threads, linear combinations in numpy (wrapping u64).  Three uses:
 
   * tests/test_plan_exec.py: the fused DAGs, executed WITHOUT any HIP kernel on real ciphertexts, decrypt like Python --
     the string layer's re-association is checked independently of the GPU arithmetic;
   * bench.py cpu_baseline: BASELINE config 3 (find, encrypted pattern, 256 characters: 2 574 bootstraps in 6 levels) run to
-    completion on the host cores, the time a CPU takes for the SAME DAG the GPU runs.
+    completion on the host cores, the time a CPU takes for the SAME DAG the GPU runs (BASELINE.md 4.4);
+  * oracle/dag_parity.py: with exact_extractions -- a shared extraction read from its leader's accumulator, not
+    bootstrapped on its own -- and the oracle mode that mirrors the device's arithmetic, the replay has the words a device
+    context must produce for the same calls (tests/test_dag_parity_device.py, smoke() step 10).
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may use this; the product never imports oracle/.
 """
@@ -24,11 +27,15 @@ TR_UPLOAD, TR_ROW, TR_EXT, TR_GROUP_END = 1, 2, 3, 4
 
 
 class PlanRun:
-    def __init__(self, oracle_server_key, threads, mode=6):
+    def __init__(self, oracle_server_key, threads, mode=6, string_mode=1, exact_extractions=False):
+        """mode: the oracle's bootstrap arithmetic; string_mode: the string layer's (fhs_set_mode: 1 fused, 0 as written).
+        exact_extractions: a TR_EXT row is taken from its leader's accumulator, as the device takes it -- leader and
+        followers are ONE orc_pbs_shifted, one blind rotation per group -- instead of being bootstrapped on its own with
+        the shifted constant.  Both decrypt alike; only the former has the device's words (tests/test_dag_parity*.py)."""
         from fhestring_amd.api import MyServerKey
-        self.S, self.threads, self.mode = oracle_server_key, threads, mode
+        self.S, self.threads, self.mode, self.exact = oracle_server_key, threads, mode, exact_extractions
         self.sk = MyServerKey.planner()              # the product's own host logic
-        self.sk.set_mode(1)
+        self.sk.set_mode(string_mode)
         self.L, self.h = self.sk.ctx._L, self.sk.ctx._h
         self.sk.ctx._check(self.L.fhs_debug_plan_trace(self.h, 1))
         self.uploads = []                            # rows in upload order
@@ -36,6 +43,7 @@ class PlanRun:
         self.n_up = 0
         self._luts = {}
         self.pbs = self.groups = 0
+        self.rotations = self.extractions = 0        # exact_extractions only: blind rotations run, rows taken from a leader's
         self.pbs_seconds = 0.0
 
     def close(self):
@@ -72,6 +80,8 @@ class PlanRun:
     def run(self):
         """execute everything recorded since the last run() (the planner flushes inside fhs_debug_plan_read)"""
         t = self._read_trace().tolist()
+        if self.exact:
+            return self._run_exact(t)
         i, rows, by_out = 0, [], {}
         while i < len(t):
             tag = t[i]
@@ -103,6 +113,55 @@ class PlanRun:
                     for r, ct in zip(rows, res):
                         self.store[r[0]] = ct
                     self.pbs += len(rows)
+                    self.groups += 1
+                rows, by_out = [], {}
+                i += 2
+            else:
+                raise ValueError("bad plan trace word %d at %d" % (tag, i))
+        assert not rows
+
+    def _run_exact(self, t):
+        """the same list with every shared extraction read from its leader's accumulator: per launch group, one
+        orc_pbs_shifted per TR_ROW (shift 0 = the row itself, then K / 128 of each of its TR_EXT rows) on host threads"""
+        from concurrent.futures import ThreadPoolExecutor
+        i, rows, by_out = 0, [], {}                   # rows: [out, lut, input, [follower outs], [shifts]]
+        while i < len(t):
+            tag = t[i]
+            if tag == TR_UPLOAD:
+                self.store[t[i + 1]] = self.uploads[self.n_up]
+                self.n_up += 1
+                i += 2
+            elif tag == TR_ROW:
+                out, lut, konst, n = t[i + 1:i + 5]
+                terms = [(t[i + 5 + 2 * k], t[i + 6 + 2 * k]) for k in range(n)]
+                by_out[out] = len(rows)
+                rows.append([out, lut, self._lin(konst, terms), [out], [0]])
+                i += 5 + 2 * n
+            elif tag == TR_EXT:
+                lead, out, K = t[i + 1:i + 4]
+                if K % 128 or not 0 < K < 4096:
+                    raise ValueError("extraction at coefficient %d" % K)
+                rows[by_out[lead]][3].append(out)
+                rows[by_out[lead]][4].append(K // 128)
+                i += 4
+            elif tag == TR_GROUP_END:
+                if rows:
+                    t0 = time.perf_counter()
+                    one = lambda r: self.S.pbs_shifted(r[2], self.lut_poly(r[1]), r[4], mode=self.mode)
+                    for lut in {r[1] for r in rows}:
+                        self.lut_poly(lut)            # (filled here, not from the threads)
+                    if self.threads > 1 and len(rows) > 1:
+                        with ThreadPoolExecutor(self.threads) as ex:
+                            res = list(ex.map(one, rows))
+                    else:
+                        res = [one(r) for r in rows]
+                    self.pbs_seconds += time.perf_counter() - t0
+                    for r, cts in zip(rows, res):     # after the whole group: its rows are independent of one another
+                        for out, ct in zip(r[3], cts):
+                            self.store[out] = ct
+                        self.extractions += len(r[3]) - 1
+                    self.rotations += len(rows)
+                    self.pbs += sum(len(r[3]) for r in rows)
                     self.groups += 1
                 rows, by_out = [], {}
                 i += 2
