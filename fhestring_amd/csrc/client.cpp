@@ -91,6 +91,15 @@ void ggsw_encrypt(const fhs_client *ck, uint64_t msg, Rng &mask, Rng &noise, uin
     uint64_t *const b[2] = {out + POLY_N, out + 3 * POLY_N};
     ggsw_bodies(ck, msg, noise, m, b);
 }
+// One row of a GLWE keyswitch key towards the secret `sk` (packing key, re-key key): a mask on the grid and
+// body = mask (*) sk + noise + (msg << shift), rounded to the grid.  2048 draws of `mask`, then 2048 of `noise`.
+void keyswitch_key_row(Rng &mask_rng, Rng &noise, const uint64_t *sk, const uint64_t *msg, int shift, uint64_t *mask,
+                       uint64_t *body) {
+    std::vector<uint64_t> prod(POLY_N);
+    for (int n = 0; n < POLY_N; n++) mask[n] = mask_rng.next() & GRID_MASK;
+    mul_binary(mask, sk, prod.data());
+    for (int n = 0; n < POLY_N; n++) body[n] = round_to_grid(prod[n] + noise.noise(GLWE_NOISE) + (msg[n] << shift), BSK_QUANT_BITS);
+}
 
 void keygen(fhs_client *ck) {
     Rng r(ck->key, 1, DOM_SECRET);
@@ -463,7 +472,7 @@ void keygen_packing(fhs_client *ck) {
     parallel_for(FHS_PACK_TREE_LEVELS, FHS_PACK_TREE_LEVELS, 1, [&](size_t k) {   // one thread per tree level
         const int lv = (int)k + 1;
         const uint32_t g = (1u << lv) + 1;
-        std::vector<uint64_t> sg(POLY_N), prod(POLY_N);
+        std::vector<uint64_t> sg(POLY_N);
         for (uint32_t i = 0; i < (uint32_t)POLY_N; i++) {          // S(X^g): coefficient i goes to i g mod 2N
             const uint32_t r = (i * g) & (2 * POLY_N - 1);
             sg[r & (POLY_N - 1)] = r >= (uint32_t)POLY_N ? (uint64_t)0 - ck->glwe_sk[i] : ck->glwe_sk[i];
@@ -472,12 +481,7 @@ void keygen_packing(fhs_client *ck) {
             const uint64_t sid = PACK_STREAM_BASE + (uint64_t)FHS_PACK_LEVELS * (lv - 1) + l;
             Rng gm(ck->key, sid, DOM_MASK), e(ck->key, sid, DOM_NOISE);
             uint64_t *mask = ck->pack_key.data() + (((size_t)(lv - 1) * FHS_PACK_LEVELS + l) * 2) * POLY_N;
-            uint64_t *body = mask + POLY_N;
-            for (int n = 0; n < POLY_N; n++) mask[n] = gm.next() & GRID_MASK;
-            mul_binary(mask, ck->glwe_sk.data(), prod.data());
-            for (int n = 0; n < POLY_N; n++)
-                body[n] = round_to_grid(prod[n] + e.noise(GLWE_NOISE) + (sg[n] << (64 - FHS_PACK_BASE_LOG * (l + 1))),
-                                        BSK_QUANT_BITS);
+            keyswitch_key_row(gm, e, ck->glwe_sk.data(), sg.data(), 64 - FHS_PACK_BASE_LOG * (l + 1), mask, mask + POLY_N);
         }
     });
 }
@@ -610,15 +614,10 @@ constexpr uint64_t SEED_TAG_REKEY = 0x5345454452454b31ull;
 bool rekey_key(fhs_client *from, fhs_client *to, uint64_t *out) {
     ChaKey key;
     if (!public_seed(to, SEED_TAG_REKEY, to->rekey_calls.fetch_add(1), key)) return false;
-    std::vector<uint64_t> prod(POLY_N);
     for (int l = 0; l < FHS_REKEY_LEVELS; l++) {
         Rng gm(key, l, DOM_MASK), e(key, l, DOM_NOISE);
-        uint64_t *mask = out + (size_t)l * 2 * POLY_N, *body = mask + POLY_N;
-        for (int n = 0; n < POLY_N; n++) mask[n] = gm.next() & GRID_MASK;
-        mul_binary(mask, to->glwe_sk.data(), prod.data());
-        for (int n = 0; n < POLY_N; n++)
-            body[n] = round_to_grid(prod[n] + e.noise(GLWE_NOISE) + (from->glwe_sk[n] << (64 - FHS_REKEY_BASE_LOG * (l + 1))),
-                                    BSK_QUANT_BITS);
+        uint64_t *mask = out + (size_t)l * 2 * POLY_N;
+        keyswitch_key_row(gm, e, to->glwe_sk.data(), from->glwe_sk.data(), 64 - FHS_REKEY_BASE_LOG * (l + 1), mask, mask + POLY_N);
     }
     return true;
 }

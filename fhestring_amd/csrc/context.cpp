@@ -306,26 +306,32 @@ int Context::load_multibit_key(const uint64_t *bsk_mb2) {
     return 0;
 }
 
-// Packing key: converted on the host to the layout ntt_transform.h expects (both primes, 58-bit grid, 1/N folded in),
-// exactly like the exact-arithmetic bootstrapping key, whatever arithmetic is selected.  Comes after the server key (whose
-// load uploads the twiddle tables) and belongs to it.
+// A GLWE keyswitch key (packing key, re-key key): converted on the host to the layout ntt_transform.h expects (both primes,
+// 58-bit grid, 1/N folded in), exactly like the exact-arithmetic bootstrapping key, whatever arithmetic is selected.
+int Context::load_keyswitch_key(const uint64_t *key, size_t n_polys, DevBuf &d_key_ntt, const char *malloc_what,
+                                const char *copy_what, hipError_t (*prepare)()) {
+    if (!ntt_slot_roots_are_bitreversed()) return fail(-3, "internal: NTT slot order is not bit-reversed");
+    const size_t n_d = n_polys * 2 * POLY_N;
+    std::vector<double> host(n_d);
+    convert_polys_to_ntt(key, host.data(), n_polys, BSK_QUANT_BITS);
+    HIP_TRY(hipStreamSynchronize(stream), "stream sync");     // a queued keyswitch may still read the previous key
+    HIP_TRY(d_key_ntt.reserve_exact(n_d * sizeof(double)), malloc_what);
+    HIP_TRY(hipMemcpy(d_key_ntt.ptr, host.data(), n_d * sizeof(double), hipMemcpyHostToDevice), copy_what);
+    HIP_TRY(prepare(), "kernel attributes");
+    return 0;
+}
+
+// Packing key: comes after the server key (whose load uploads the twiddle tables) and belongs to it.
 int Context::load_packing_key(const uint64_t *key) {
     if (!key) return fail(-1, "null key pointer");
     if (!key_loaded) return fail(-3, "load the server key before the packing key");
     HIP_TRY(hipSetDevice(device), "hipSetDevice");
-    if (!ntt_slot_roots_are_bitreversed()) return fail(-3, "internal: NTT slot order is not bit-reversed");
-    const size_t n_d = PACK_KEY_POLYS * 2 * POLY_N;
-    std::vector<double> host(n_d);
-    convert_polys_to_ntt(key, host.data(), PACK_KEY_POLYS, BSK_QUANT_BITS);
-    HIP_TRY(hipStreamSynchronize(stream), "stream sync");     // a queued packing may still read the previous key
-    HIP_TRY(d_pack_key_ntt.reserve_exact(n_d * sizeof(double)), "hipMalloc packing key");
-    HIP_TRY(hipMemcpy(d_pack_key_ntt.ptr, host.data(), n_d * sizeof(double), hipMemcpyHostToDevice), "copy packing key");
-    HIP_TRY(prepare_device_for_packing(), "kernel attributes");
-    return 0;
+    return load_keyswitch_key(key, PACK_KEY_POLYS, d_pack_key_ntt, "hipMalloc packing key", "copy packing key",
+                              prepare_device_for_packing);
 }
 
-// Re-key key of the string store: the same conversion as the packing key's.  It has nothing to do with the server key
-// but needs the twiddle tables its load uploads, and goes when the server key is replaced, like every auxiliary key.
+// Re-key key of the string store.  It has nothing to do with the server key but needs the twiddle tables its load
+// uploads, and goes when the server key is replaced, like every auxiliary key.
 int Context::load_rekey_key(const uint64_t *key) {
     HIP_TRY(hipSetDevice(device), "hipSetDevice");
     if (!key) {
@@ -334,15 +340,8 @@ int Context::load_rekey_key(const uint64_t *key) {
         return 0;
     }
     if (!key_loaded) return fail(-3, "load the server key before the re-key key");
-    if (!ntt_slot_roots_are_bitreversed()) return fail(-3, "internal: NTT slot order is not bit-reversed");
-    const size_t n_d = REKEY_KEY_POLYS * 2 * POLY_N;
-    std::vector<double> host(n_d);
-    convert_polys_to_ntt(key, host.data(), REKEY_KEY_POLYS, BSK_QUANT_BITS);
-    HIP_TRY(hipStreamSynchronize(stream), "stream sync");
-    HIP_TRY(d_rekey_key_ntt.reserve_exact(n_d * sizeof(double)), "hipMalloc re-key key");
-    HIP_TRY(hipMemcpy(d_rekey_key_ntt.ptr, host.data(), n_d * sizeof(double), hipMemcpyHostToDevice), "copy re-key key");
-    HIP_TRY(prepare_device_for_rekey(), "kernel attributes");
-    return 0;
+    return load_keyswitch_key(key, REKEY_KEY_POLYS, d_rekey_key_ntt, "hipMalloc re-key key", "copy re-key key",
+                              prepare_device_for_rekey);
 }
 
 int Context::blind_rotate(const uint64_t *d_ks, const uint32_t *d_lut_idx, const uint64_t *d_luts, uint64_t *d_out,

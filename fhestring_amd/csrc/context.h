@@ -81,6 +81,9 @@ class Context {
     // packing key (dropped by a server-key reload)
     DevBuf d_rekey_key_ntt;          // double: [2][2 cols][2 primes][2048]
     int load_rekey_key(const uint64_t *key);     // [FHS_REKEY_KEY_WORDS] u64 standard domain, or nullptr: unload
+    // the conversion and upload behind both loaders (internal)
+    int load_keyswitch_key(const uint64_t *key, size_t n_polys, DevBuf &d_key_ntt, const char *malloc_what, const char *copy_what,
+                           hipError_t (*prepare)());
     int load_multibit_key(const uint64_t *bsk_mb2);   // [371][K1,K2,K3][4][2048] u64 standard domain (fhs_client_bsk_mb2)
     int fft4_max_batch = 512;                // batches up to this size use the 4-wavefront kernel (lower latency)
     size_t launch_chunk[N_ARITH] = {};       // per arithmetic: ciphertexts per blind-rotation launch (0 = whole batch)

@@ -14,6 +14,9 @@
 
 namespace fhs {
 
+// a packed GLWE, a parked entry's GLWE and a public-key GLWE hold the same blocks: the store moves words between them
+static_assert(PACK_GROUP == REKEY_GROUP && PACK_GROUP == FHS_PK_GROUP && PACK_GROUP == FHS_PACK_GROUP,
+              "one group size for the packing tree, the re-key and the public-key expansion");
 
 bool TransferBuffer::ensure(size_t rows, hipStream_t s) {
     const size_t words = rows * BIG_CT + rows;

@@ -78,4 +78,44 @@ void torus_poly_to_ntt(const uint64_t *poly, int quant_bits, const NttPrime &t, 
     for (unsigned n = 0; n < N; n++) out[n] = t.mul(out[n], t.ninv);
 }
 
+std::vector<uint64_t> key_to_ntt(const uint64_t *key, size_t n_polys) {
+    std::vector<uint64_t> key_ntt(n_polys * 2 * N);
+    for (size_t pi = 0; pi < n_polys; pi++)
+        for (int q = 0; q < 2; q++) torus_poly_to_ntt(key + pi * N, BSK_QUANT_BITS, ntt_prime(q), key_ntt.data() + (pi * 2 + q) * N);
+    return key_ntt;
+}
+
+void keyswitch_sums(const uint64_t *key_ntt, int L, const int64_t *digits, uint64_t *ks_mask, uint64_t *ks_body) {
+    std::vector<uint64_t> buf((size_t)(2 * L + 4) * N);
+    uint64_t *dig = buf.data() /* [prime][L] */, *acc = dig + (size_t)2 * L * N /* [col][prime] */;
+    for (unsigned n = 0; n < N; n++)
+        for (int l = 0; l < L; l++)
+            for (int q = 0; q < 2; q++) dig[((size_t)q * L + l) * N + n] = to_residue(digits[(size_t)n * L + l], ntt_prime(q).p);
+    for (int q = 0; q < 2; q++) {
+        const NttPrime &pt = ntt_prime(q);
+        for (int l = 0; l < L; l++) ntt_forward(dig + ((size_t)q * L + l) * N, pt);
+        for (int c = 0; c < 2; c++) {
+            uint64_t *a = acc + ((size_t)c * 2 + q) * N;
+            for (unsigned n = 0; n < N; n++) {
+                uint64_t s = 0;
+                for (int l = 0; l < L; l++)
+                    s += pt.mul(dig[((size_t)q * L + l) * N + n], key_ntt[((((size_t)l * 2 + c) * 2 + q) * N) + n]);
+                a[n] = s % pt.p;
+            }
+            ntt_inverse(a, pt);
+        }
+    }
+    // CRT to the centred integer, back to the torus: << 6 (the key was divided by 2^6)
+    const NttPrime &p1 = ntt_prime(1);
+    static const uint64_t crt = p1.pow(NTT_P0 % NTT_P1, NTT_P1 - 2);   // p0^-1 mod p1
+    for (int c = 0; c < 2; c++)
+        for (unsigned n = 0; n < N; n++) {
+            const uint64_t r0 = acc[((size_t)c * 2 + 0) * N + n], r1 = acc[((size_t)c * 2 + 1) * N + n];
+            const uint64_t r0m = r0 % NTT_P1;
+            const uint64_t k = p1.mul(r1 >= r0m ? r1 - r0m : r1 + NTT_P1 - r0m, crt);
+            const int64_t kc = k > NTT_P1 / 2 ? (int64_t)k - (int64_t)NTT_P1 : (int64_t)k;
+            (c ? ks_body : ks_mask)[n] = (r0 + NTT_P0 * (uint64_t)kc) << BSK_QUANT_BITS;
+        }
+}
+
 }  // namespace fhs

@@ -45,4 +45,28 @@ inline uint64_t round_to_grid(uint64_t x, int bits) { return (x + (1ull << (bits
 // for the 2048 torus words of `poly`, slots in the order of ntt_forward.
 void torus_poly_to_ntt(const uint64_t *poly, int quant_bits, const NttPrime &t, uint64_t *out);
 
+// ---- the GLWE keyswitch of the packing tree and of the re-key family (pack_host.cpp, rekey_host.cpp; device:
+// glwe_keyswitch.h), on a key of 16-bit digit levels on the bootstrapping key's grid ----
+constexpr int KEYSWITCH_BASE_LOG = 16;
+// signed digits of the closest multiple of 2^(64 - 16 L) to x, most significant first (l = 0), each in [-2^15, 2^15);
+// a carry out of the top digit is a multiple of 2^64
+inline void decompose(uint64_t x, int L, int64_t *d) {
+    const int sh = 64 - L * KEYSWITCH_BASE_LOG;
+    uint64_t v = (x + (1ull << (sh - 1))) >> sh;
+    uint64_t carry = 0;
+    for (int l = L - 1; l >= 0; l--) {
+        int64_t dg = (int64_t)((v & ((1ull << KEYSWITCH_BASE_LOG) - 1)) + carry);
+        v >>= KEYSWITCH_BASE_LOG;
+        if (dg >= (int64_t)1 << (KEYSWITCH_BASE_LOG - 1)) { dg -= (int64_t)1 << KEYSWITCH_BASE_LOG; carry = 1; }
+        else carry = 0;
+        d[l] = dg;
+    }
+}
+// a keyswitch key of n_polys torus polynomials as residues: [n_polys][prime][2048], rounded to the 58-bit grid, 1/N
+// folded in (torus_poly_to_ntt)
+std::vector<uint64_t> key_to_ntt(const uint64_t *key, size_t n_polys);
+// the 64-bit keyswitch sums of one GLWE mask before any rounding: ks_mask / ks_body[2048] = sum_l d_l (*) K[l].col with
+// digits[n * L + l] = digit l of coefficient n (decompose) and key_ntt = [L][mask, body][prime][2048]
+void keyswitch_sums(const uint64_t *key_ntt, int L, const int64_t *digits, uint64_t *ks_mask, uint64_t *ks_body);
+
 }  // namespace fhs

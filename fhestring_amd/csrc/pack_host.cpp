@@ -11,47 +11,25 @@
 #include "host_ntt.h"
 #include "host_parallel.h"
 #include "pbs_kernels.h"
+#include "storage_words.h"
 
 namespace {
 
 using namespace fhs;
 constexpr int N = POLY_N;
-constexpr int L = FHS_PACK_LEVELS, BETA = FHS_PACK_BASE_LOG;
+constexpr int L = FHS_PACK_LEVELS;
+static_assert(FHS_PACK_BASE_LOG == KEYSWITCH_BASE_LOG, "the packing key has the shared keyswitch's digit width");
 
-// the packing key in the NTT domain: [11][L][mask, body][prime][2048], rounded to the 58-bit grid, 1/N folded in
-struct HostKey {
-    std::vector<uint64_t> w;
-    const uint64_t *poly(int lv, int l, int col, int q) const {
-        return w.data() + (((((size_t)(lv - 1) * L + l) * 2 + col) * 2 + q) * N);
-    }
-};
-void convert_key(const uint64_t *key, HostKey &hk) {
-    hk.w.resize((size_t)FHS_PACK_TREE_LEVELS * L * 2 * 2 * N);
-    for (size_t pi = 0; pi < (size_t)FHS_PACK_TREE_LEVELS * L * 2; pi++)
-        for (int q = 0; q < 2; q++) torus_poly_to_ntt(key + pi * N, BSK_QUANT_BITS, ntt_prime(q), hk.w.data() + (pi * 2 + q) * N);
-}
-
-// signed digits of x, most significant first (l = 0), each in [-2^(BETA-1), 2^(BETA-1))
-inline void decompose(uint64_t x, int64_t d[L]) {
-    constexpr int SH = 64 - L * BETA;
-    uint64_t v = (x + (1ull << (SH - 1))) >> SH;     // closest multiple of 2^SH; a carry out of the top is a multiple of 2^64
-    uint64_t carry = 0;
-    for (int l = L - 1; l >= 0; l--) {
-        int64_t dg = (int64_t)((v & ((1ull << BETA) - 1)) + carry);
-        v >>= BETA;
-        if (dg >= (int64_t)1 << (BETA - 1)) { dg -= (int64_t)1 << BETA; carry = 1; }
-        else carry = 0;
-        d[l] = dg;
-    }
-}
+// the packing key as residues (key_to_ntt): [11][L][mask, body][prime][2048]; one tree level's part is a keyswitch key
+constexpr size_t KEY_POLYS = (size_t)FHS_PACK_TREE_LEVELS * L * 2;
+const uint64_t *level_key(const std::vector<uint64_t> &key_ntt, int lv) { return key_ntt.data() + (size_t)(lv - 1) * L * 2 * 2 * N; }
 
 // one tree node: out = P + AutoKS_g(M), T = X^t O, P = E + T, M = E - T, g = 2^lv + 1, t = N >> lv.
 // e / o / out: mask[2048] | body[2048]; o == nullptr: the odd child is absent (zero).
-void pack_node(const HostKey &hk, int lv, const uint64_t *e, const uint64_t *o, uint64_t *out) {
+void pack_node(const std::vector<uint64_t> &key_ntt, int lv, const uint64_t *e, const uint64_t *o, uint64_t *out) {
     const uint32_t t = (uint32_t)N >> lv, g = (1u << lv) + 1;
-    std::vector<uint64_t> buf((size_t)(4 + 2 * L + 4) * N);
-    uint64_t *P = buf.data(), *A1 = P + 2 * N /* A'(X) | B'(X) */, *dig = A1 + 2 * N /* [2 primes][L] */,
-             *acc = dig + (size_t)2 * L * N /* [col][prime] */;
+    std::vector<uint64_t> buf((size_t)6 * N);
+    uint64_t *P = buf.data(), *A1 = P + 2 * N /* A'(X) | B'(X) */, *ks = A1 + 2 * N /* mask | body */;
     for (int c = 0; c < 2; c++)
         for (uint32_t i = 0; i < (uint32_t)N; i++) {
             uint64_t tv = 0;
@@ -62,37 +40,11 @@ void pack_node(const HostKey &hk, int lv, const uint64_t *e, const uint64_t *o, 
             const uint32_t r = (i * g) & (2 * N - 1);                  // the automorphism X -> X^g
             A1[c * N + (r & (N - 1))] = r >= (uint32_t)N ? (uint64_t)0 - m : m;
         }
-    for (int n = 0; n < N; n++) {
-        int64_t d[L];
-        decompose(A1[n], d);
-        for (int l = 0; l < L; l++)
-            for (int q = 0; q < 2; q++) dig[((size_t)q * L + l) * N + n] = to_residue(d[l], ntt_prime(q).p);
-    }
-    for (int q = 0; q < 2; q++) {
-        const NttPrime &pt = ntt_prime(q);
-        for (int l = 0; l < L; l++) ntt_forward(dig + ((size_t)q * L + l) * N, pt);
-        for (int c = 0; c < 2; c++) {
-            uint64_t *a = acc + ((size_t)c * 2 + q) * N;
-            for (int n = 0; n < N; n++) {
-                uint64_t s = 0;
-                for (int l = 0; l < L; l++) s += pt.mul(dig[((size_t)q * L + l) * N + n], hk.poly(lv, l, c, q)[n]);
-                a[n] = s % pt.p;
-            }
-            ntt_inverse(a, pt);
-        }
-    }
-    // CRT to the centred integer, back to the torus: << 6 (the key was divided by 2^6)
-    const NttPrime &p1 = ntt_prime(1);
-    static const uint64_t crt = p1.pow(NTT_P0 % NTT_P1, NTT_P1 - 2);   // p0^-1 mod p1
+    std::vector<int64_t> d((size_t)N * L);
+    for (int n = 0; n < N; n++) decompose(A1[n], L, d.data() + (size_t)n * L);
+    keyswitch_sums(level_key(key_ntt, lv), L, d.data(), ks, ks + N);
     for (int c = 0; c < 2; c++)
-        for (int n = 0; n < N; n++) {
-            const uint64_t r0 = acc[((size_t)c * 2 + 0) * N + n], r1 = acc[((size_t)c * 2 + 1) * N + n];
-            const uint64_t r0m = r0 % NTT_P1;
-            uint64_t k = p1.mul(r1 >= r0m ? r1 - r0m : r1 + NTT_P1 - r0m, crt);
-            const int64_t ks = k > NTT_P1 / 2 ? (int64_t)k - (int64_t)NTT_P1 : (int64_t)k;
-            const uint64_t v = (r0 + NTT_P0 * (uint64_t)ks) << BSK_QUANT_BITS;
-            out[c * N + n] = P[c * N + n] + (c ? A1[N + n] : 0) - v;
-        }
+        for (int n = 0; n < N; n++) out[c * N + n] = P[c * N + n] + (c ? A1[N + n] : 0) - ks[c * N + n];
 }
 
 // leaf GLWE of one block, pre-scaled by 1/N with rounding: A_0 = a_0, A_{N-i} = -a_i, B_0 = b
@@ -106,7 +58,7 @@ void leaf_glwe(const uint64_t *blk, uint64_t *out) {
 
 // one group: `count` blocks (1..2048) -> mask[2048], body[2048].  Node k of level lv holds the blocks = k mod (N >> lv);
 // its children at level lv - 1 are nodes k (even) and k + (N >> lv) (odd); a node is live when block k exists.
-void pack_group(const HostKey &hk, const uint64_t *blocks, size_t count, uint64_t *mask, uint64_t *body) {
+void pack_group(const std::vector<uint64_t> &key_ntt, const uint64_t *blocks, size_t count, uint64_t *mask, uint64_t *body) {
     std::vector<uint64_t> cur, prev;
     for (int lv = 1; lv <= FHS_PACK_TREE_LEVELS; lv++) {
         const size_t n_lv = (size_t)N >> lv, live = std::min(count, n_lv);
@@ -118,9 +70,9 @@ void pack_group(const HostKey &hk, const uint64_t *blocks, size_t count, uint64_
                 std::vector<uint64_t> leaves(4 * N);
                 leaf_glwe(blocks + k * BIG_CT, leaves.data());
                 if (has_o) leaf_glwe(blocks + (k + n_lv) * BIG_CT, leaves.data() + 2 * N);
-                pack_node(hk, lv, leaves.data(), has_o ? leaves.data() + 2 * N : nullptr, cur.data() + k * 2 * N);
+                pack_node(key_ntt, lv, leaves.data(), has_o ? leaves.data() + 2 * N : nullptr, cur.data() + k * 2 * N);
             } else {
-                pack_node(hk, lv, prev.data() + k * 2 * N, has_o ? prev.data() + (k + n_lv) * 2 * N : nullptr,
+                pack_node(key_ntt, lv, prev.data() + k * 2 * N, has_o ? prev.data() + (k + n_lv) * 2 * N : nullptr,
                           cur.data() + k * 2 * N);
             }
         });
@@ -141,10 +93,9 @@ void fhs_packed_bytes(size_t n_chars, size_t *mask_words, size_t *body_words) {
 
 int fhs_pack_host(const uint64_t *key, const uint64_t *blocks, size_t n_blocks, uint64_t *mask64, uint64_t *body64) {
     if (!key || (n_blocks && (!blocks || !mask64 || !body64))) return FHS_ERR_ARG;
-    HostKey hk;
-    convert_key(key, hk);
+    const std::vector<uint64_t> key_ntt = key_to_ntt(key, KEY_POLYS);
     for (size_t g = 0; g * FHS_PACK_GROUP < n_blocks; g++)
-        pack_group(hk, blocks + g * FHS_PACK_GROUP * BIG_CT, std::min<size_t>(FHS_PACK_GROUP, n_blocks - g * FHS_PACK_GROUP),
+        pack_group(key_ntt, blocks + g * FHS_PACK_GROUP * BIG_CT, std::min<size_t>(FHS_PACK_GROUP, n_blocks - g * FHS_PACK_GROUP),
                    mask64 + g * N, body64 + g * N);
     return FHS_OK;
 }
@@ -152,11 +103,10 @@ int fhs_pack_host(const uint64_t *key, const uint64_t *blocks, size_t n_blocks, 
 int fhs_pack_switch16(const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, void *mask16_, void *body16_) {
     uint16_t *mask16 = static_cast<uint16_t *>(mask16_), *body16 = static_cast<uint16_t *>(body16_);
     if (n_blocks && (!mask64 || !body64 || !mask16 || !body16)) return FHS_ERR_ARG;
-    auto sw = [](uint64_t x) { return (uint16_t)(((x + (1ull << 47)) >> 48) & 0xffff); };
     for (size_t g = 0; g * FHS_PACK_GROUP < n_blocks; g++) {
         const size_t count = std::min<size_t>(FHS_PACK_GROUP, n_blocks - g * FHS_PACK_GROUP);
-        for (int i = 0; i < N; i++) mask16[g * N + i] = sw(mask64[g * N + i]);
-        for (size_t j = 0; j < count; j++) body16[g * FHS_PACK_GROUP + j] = sw(body64[g * N + j]);
+        for (int i = 0; i < N; i++) mask16[g * N + i] = round16(mask64[g * N + i]);
+        for (size_t j = 0; j < count; j++) body16[g * FHS_PACK_GROUP + j] = round16(body64[g * N + j]);
     }
     return FHS_OK;
 }
@@ -164,20 +114,18 @@ int fhs_pack_switch16(const uint64_t *mask64, const uint64_t *body64, size_t n_b
 int fhs_pack_switch32(const uint64_t *mask64, const uint64_t *body64, size_t n_blocks, void *mask32_, void *body32_) {
     uint32_t *mask32 = static_cast<uint32_t *>(mask32_), *body32 = static_cast<uint32_t *>(body32_);
     if (n_blocks && (!mask64 || !body64 || !mask32 || !body32)) return FHS_ERR_ARG;
-    auto sw = [](uint64_t x) { return (uint32_t)((x + (1ull << 31)) >> 32); };
     for (size_t g = 0; g * FHS_PACK_GROUP < n_blocks; g++) {
         const size_t count = std::min<size_t>(FHS_PACK_GROUP, n_blocks - g * FHS_PACK_GROUP);
-        for (int i = 0; i < N; i++) mask32[g * N + i] = sw(mask64[g * N + i]);
-        for (size_t j = 0; j < count; j++) body32[g * FHS_PACK_GROUP + j] = sw(body64[g * N + j]);
+        for (int i = 0; i < N; i++) mask32[g * N + i] = round32(mask64[g * N + i]);
+        for (size_t j = 0; j < count; j++) body32[g * FHS_PACK_GROUP + j] = round32(body64[g * N + j]);
     }
     return FHS_OK;
 }
 
 int fhs_debug_pack_node(const uint64_t *key, int lv, const uint64_t *e, const uint64_t *o, uint64_t *out) {
     if (!key || !e || !o || !out || lv < 1 || lv > FHS_PACK_TREE_LEVELS) return FHS_ERR_ARG;
-    HostKey hk;
-    convert_key(key, hk);
-    pack_node(hk, lv, e, o, out);
+    const std::vector<uint64_t> key_ntt = key_to_ntt(key, KEY_POLYS);
+    pack_node(key_ntt, lv, e, o, out);
     return FHS_OK;
 }
 

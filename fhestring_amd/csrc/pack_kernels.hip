@@ -12,8 +12,9 @@
 // two waves of a prime duplicate that work: the simplest mapping, and the whole packing is a few blind rotations' worth).
 // Level 1 reads the pool blocks through a table, divides by N with rounding and builds the leaf GLWE
 // (A_0 = a_0, A_{N-i} = -a_i, B = b) on the fly.
-#include "ntt_transform.h"
+#include "glwe_keyswitch.h"
 #include "pack_kernels.h"
+#include "storage_words.h"
 
 namespace fhs {
 
@@ -82,17 +83,7 @@ __global__ __launch_bounds__(256) void pack_level_kernel(PackLevelParams P) {
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int j = wave >> 1;   // output polynomial (0 mask, 1 body)
     const int q = wave & 1;    // prime
-    double *my = reinterpret_cast<double *>(smem) + wave * LDS_WAVE_SLOTS;
-    const double *sibling = reinterpret_cast<double *>(smem) + (wave ^ 1) * LDS_WAVE_SLOTS;  // other prime
-    uint64_t *my_u = reinterpret_cast<uint64_t *>(my);
-
-    const double p = q ? (double)NTT_P1 : (double)NTT_P0;
-    const double pinv = 1.0 / p;
-    const double p1 = (double)NTT_P1, p1inv = 1.0 / p1;
-    const double *fwd_lane = P.tw.fwd_lane + q * 32 * 64;
-    const double *inv_lane = P.tw.inv_lane + q * 32 * 64;
-    const double twA = lane < 32 ? C_FWD_UNI[q][lane] : C_INV_UNI[q][lane];
-    const double twB = C_INV_UNI[q][lane & 31];
+    const KeyswitchWave kw(P.tw, smem, lane, wave);
 
     // children: nodes k (even blocks) and k + n_lv (odd blocks) of the level below; at level 1 they are blocks
     PackChild E, O;
@@ -121,44 +112,9 @@ __global__ __launch_bounds__(256) void pack_level_kernel(PackLevelParams P) {
 #pragma unroll
     for (int r = 0; r < 32; r++) a1[r] = node_auto<LEAF>(E, O, 0, lane + 64 * r, t, ginv);
 
-    // sum over the digits of NTT(d_l) * NTT(K_g[l][j]) modulo p
-    typedef double __attribute__((ext_vector_type(2))) double2_t;
-    double acc[32];
-#pragma unroll
-    for (int c = 0; c < 32; c++) acc[c] = 0.0;
-#pragma unroll
-    for (int l = 0; l < PACK_LEVELS; l++) {
-        double x[32];
-#pragma unroll
-        for (int r = 0; r < 32; r++) x[r] = pack_digit(a1[r], l);
-        __builtin_amdgcn_wave_barrier();
-        ntt_forward(x, my, lane, twA, fwd_lane, p, pinv);
-        // key layout [16][64 lanes][2]: one 16-byte load per lane covers coefficients (c, c + 1) of the contiguous layout
-        const double2_t *key = reinterpret_cast<const double2_t *>(
-            P.key_ntt + (((((size_t)(P.lv - 1) * PACK_LEVELS + l) * 2 + j) * 2 + q) * POLY_N)) + lane;
-#pragma unroll
-        for (int c = 0; c < 32; c += 2) {
-            const double2_t kv = key[(c >> 1) * 64];
-            const double m0 = mulmod(x[c], kv.x, p, pinv), m1 = mulmod(x[c + 1], kv.y, p, pinv);
-            acc[c] += m0;
-            acc[c + 1] += m1;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 32; c++) acc[c] = reduce_once(acc[c], p, pinv);   // three products: back inside the inverse's input range
-    __builtin_amdgcn_wave_barrier();
-    ntt_inverse(acc, my, lane, twA, twB, inv_lane, p, pinv);
-    __builtin_amdgcn_wave_barrier();
-
-    // exchange residues with the other prime's wave, CRT for the owned half (coefficients lane + 64 (2 o + q))
+    // ks = sum_l d_l (*) K_g[l][j] of this wave's half of polynomial j (glwe_keyswitch.h; it holds the workgroup's barrier)
     uint64_t ks[16];
-#pragma unroll
-    for (int o = 0; o < 16; o++) ks[o] = 0;
-    if (q == 0) phase_publish_residues<0>(acc, my, lane);
-    else phase_publish_residues<1>(acc, my, lane);
-    __syncthreads();
-    if (q == 0) phase_crt<0>(acc, ks, sibling, my_u, lane, C_CRT, p1, p1inv);
-    else phase_crt<1>(acc, ks, sibling, my_u, lane, C_CRT, p1, p1inv);
+    glwe_keyswitch_sums<PACK_LEVELS>(kw, [&a1](int r, int l) { return pack_digit(a1[r], l); }, P.key_ntt, P.lv - 1, ks);
 
     // out = P + AutoKS(M): mask P_A - sum, body P_B + B(X^g) - sum
     uint64_t *out = P.dst + ((size_t)grp * n_lv + k) * 2 * POLY_N + (size_t)j * POLY_N;
@@ -173,42 +129,37 @@ __global__ __launch_bounds__(256) void pack_level_kernel(PackLevelParams P) {
     }
 }
 
-size_t pack_lds_bytes() { return (size_t)4 * LDS_WAVE_SLOTS * sizeof(double); }
-
 hipError_t prepare_device_for_packing() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(pack_level_kernel<true>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)pack_lds_bytes());
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)keyswitch_lds_bytes());
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void *>(pack_level_kernel<false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pack_lds_bytes());
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)keyswitch_lds_bytes());
 }
 
 hipError_t launch_pack_level(const PackLevelParams &p, hipStream_t s) {
-    if (p.groups <= 0 || p.total == 0 || p.lv < 1 || p.lv > PACK_TREE_LEVELS) return hipErrorInvalidValue;
-    if ((size_t)p.total > (size_t)p.groups * PACK_GROUP || (size_t)p.total <= (size_t)(p.groups - 1) * PACK_GROUP)
-        return hipErrorInvalidValue;
+    if (!fills_groups(p.total, p.groups, PACK_GROUP) || p.lv < 1 || p.lv > PACK_TREE_LEVELS) return hipErrorInvalidValue;
     const uint32_t n_lv = (uint32_t)POLY_N >> p.lv;
     const dim3 grid(p.groups > 1 ? n_lv : (p.total < n_lv ? p.total : n_lv), p.groups);
-    if (p.lv == 1) hipLaunchKernelGGL(pack_level_kernel<true>, grid, dim3(256), pack_lds_bytes(), s, p);
-    else hipLaunchKernelGGL(pack_level_kernel<false>, grid, dim3(256), pack_lds_bytes(), s, p);
+    if (p.lv == 1) hipLaunchKernelGGL(pack_level_kernel<true>, grid, dim3(256), keyswitch_lds_bytes(), s, p);
+    else hipLaunchKernelGGL(pack_level_kernel<false>, grid, dim3(256), keyswitch_lds_bytes(), s, p);
     return hipGetLastError();
 }
 
-// ---- storage switch: every word of the packed GLWE -> ((x + 2^47) >> 48) & 0xffff ----
+// ---- storage switch: every word of the packed GLWE -> round16 (storage_words.h) ----
 __global__ __launch_bounds__(256) void pack_switch16_kernel(const uint64_t *__restrict__ glwe, uint16_t *__restrict__ mask16,
                                                             uint16_t *__restrict__ body16, uint32_t total) {
     const uint32_t grp = blockIdx.x;
     const uint32_t count = min((uint32_t)PACK_GROUP, total - grp * PACK_GROUP);
     const uint64_t *a = glwe + (size_t)grp * 2 * POLY_N, *b = a + POLY_N;
     for (uint32_t i = threadIdx.x; i < (uint32_t)POLY_N; i += 256) {
-        mask16[(size_t)grp * POLY_N + i] = (uint16_t)((a[i] + (1ull << 47)) >> 48);
-        if (i < count) body16[(size_t)grp * PACK_GROUP + i] = (uint16_t)((b[i] + (1ull << 47)) >> 48);
+        mask16[(size_t)grp * POLY_N + i] = round16(a[i]);
+        if (i < count) body16[(size_t)grp * PACK_GROUP + i] = round16(b[i]);
     }
 }
 hipError_t launch_pack_switch16(const uint64_t *d_glwe, uint16_t *d_mask16, uint16_t *d_body16, int groups, uint32_t total,
                                 hipStream_t s) {
-    if (groups <= 0 || (size_t)total > (size_t)groups * PACK_GROUP || (size_t)total <= (size_t)(groups - 1) * PACK_GROUP)
-        return hipErrorInvalidValue;
+    if (!fills_groups(total, groups, PACK_GROUP)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(pack_switch16_kernel, dim3(groups), dim3(256), 0, s, d_glwe, d_mask16, d_body16, total);
     return hipGetLastError();
 }

@@ -13,6 +13,7 @@
 #include "host_parallel.h"
 #include "keyfile.h"
 #include "pbs_kernels.h"
+#include "storage_words.h"
 
 namespace {
 
@@ -29,7 +30,6 @@ struct PublicKey {
     std::atomic<uint64_t> test_seed{0}, calls{0};
 };
 
-inline uint32_t store32(uint64_t x) { return (uint32_t)((x + (1ull << 31)) >> 32); }
 
 // one group: mask = A U + E1, body = B U + E2 + messages, U binary -- both negacyclic products as sums of signed shifts
 void encrypt_group(const PublicKey &pk, const ChaKey &key, uint64_t g, const uint8_t *msg, size_t count, uint32_t *mask32,
@@ -43,10 +43,10 @@ void encrypt_group(const PublicKey &pk, const ChaKey &key, uint64_t g, const uin
         for (int k = 0; k < j; k++) { mask[k] -= a[k + N - j]; body[k] -= b[k + N - j]; }
         for (int k = j; k < N; k++) { mask[k] += a[k - j]; body[k] += b[k - j]; }
     }
-    for (int k = 0; k < N; k++) mask32[k] = store32(mask[k] + e1.noise(GLWE_NOISE));
+    for (int k = 0; k < N; k++) mask32[k] = round32(mask[k] + e1.noise(GLWE_NOISE));
     for (size_t k = 0; k < (size_t)N; k++) {
         const uint64_t x = body[k] + e2.noise(GLWE_NOISE);       // (drawn for absent blocks too: one stream layout)
-        if (k < count) body32[k] = store32(x + ((uint64_t)msg[k] << DELTA_LOG));
+        if (k < count) body32[k] = round32(x + ((uint64_t)msg[k] << DELTA_LOG));
     }
 }
 

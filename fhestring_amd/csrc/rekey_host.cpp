@@ -9,63 +9,31 @@
 #include "host_ntt.h"
 #include "host_parallel.h"
 #include "pbs_kernels.h"
+#include "storage_words.h"
 
 namespace {
 
 using namespace fhs;
 constexpr int N = POLY_N;
 constexpr int L = FHS_REKEY_LEVELS;
-static_assert(L == 2 && FHS_REKEY_BASE_LOG == 16, "the digits below are the two 16-bit halves of a 32-bit word");
+static_assert(L == 2 && FHS_REKEY_BASE_LOG == KEYSWITCH_BASE_LOG, "the digits are the two 16-bit halves of a 32-bit word");
 
-inline uint32_t store32(uint64_t x) { return (uint32_t)((x + (1ull << 31)) >> 32); }
-inline uint16_t store16(uint64_t x) { return (uint16_t)((x + (1ull << 47)) >> 48); }
-
-// the 64-bit keyswitch sums of one group before any rounding: ks_mask / ks_body[2048] = sum_l d_l (*) K[l].col with
-// a << 32 = d_0 2^48 + d_1 2^32; key_ntt: [L][mask, body][prime][2048].  Shared by both storage formats below.
-void keyswitch_sums(const uint64_t *key_ntt, const uint32_t *a32, uint64_t *ks_mask, uint64_t *ks_body) {
-    std::vector<uint64_t> buf((size_t)(2 * L + 4) * N);
-    uint64_t *dig = buf.data() /* [prime][L] */, *acc = dig + (size_t)2 * L * N /* [col][prime] */;
-    for (int n = 0; n < N; n++) {
-        // a << 32 = d[0] 2^48 + d[1] 2^32 exactly, digits in [-2^15, 2^15); the carry out of d[0] is a multiple of 2^64
-        const uint32_t a = a32[n], lo = a & 0xffff, c = lo >= 0x8000;
-        const int64_t d[L] = {(int16_t)(uint16_t)((a >> 16) + c), (int16_t)(uint16_t)lo};
-        for (int l = 0; l < L; l++)
-            for (int q = 0; q < 2; q++) dig[((size_t)q * L + l) * N + n] = to_residue(d[l], ntt_prime(q).p);
-    }
-    for (int q = 0; q < 2; q++) {
-        const NttPrime &pt = ntt_prime(q);
-        for (int l = 0; l < L; l++) ntt_forward(dig + ((size_t)q * L + l) * N, pt);
-        for (int c = 0; c < 2; c++) {
-            uint64_t *a = acc + ((size_t)c * 2 + q) * N;
-            for (int n = 0; n < N; n++) {
-                uint64_t s = 0;
-                for (int l = 0; l < L; l++)
-                    s += pt.mul(dig[((size_t)q * L + l) * N + n], key_ntt[((((size_t)l * 2 + c) * 2 + q) * N) + n]);
-                a[n] = s % pt.p;
-            }
-            ntt_inverse(a, pt);
-        }
-    }
-    // CRT to the centred integer, back to the torus: << 6 (the key was divided by 2^6), as pack_host.cpp
-    const NttPrime &p1 = ntt_prime(1);
-    static const uint64_t crt = p1.pow(NTT_P0 % NTT_P1, NTT_P1 - 2);   // p0^-1 mod p1
-    for (int c = 0; c < 2; c++)
-        for (int n = 0; n < N; n++) {
-            const uint64_t r0 = acc[((size_t)c * 2 + 0) * N + n], r1 = acc[((size_t)c * 2 + 1) * N + n];
-            const uint64_t r0m = r0 % NTT_P1;
-            const uint64_t k = p1.mul(r1 >= r0m ? r1 - r0m : r1 + NTT_P1 - r0m, crt);
-            const int64_t kc = k > NTT_P1 / 2 ? (int64_t)k - (int64_t)NTT_P1 : (int64_t)k;
-            (c ? ks_body : ks_mask)[n] = (r0 + NTT_P0 * (uint64_t)kc) << BSK_QUANT_BITS;
-        }
+// the 64-bit keyswitch sums of one group before any rounding (host_ntt.h): ks = mask | body [2048] each, from the mask's
+// 32-bit words: a << 32 = d_0 2^48 + d_1 2^32 exactly.  Shared by all three formats below.
+std::vector<uint64_t> keyswitch_sums32(const uint64_t *key_ntt, const uint32_t *a32) {
+    std::vector<int64_t> d((size_t)N * L);
+    for (int n = 0; n < N; n++) decompose((uint64_t)a32[n] << 32, L, d.data() + (size_t)n * L);
+    std::vector<uint64_t> ks((size_t)2 * N);
+    keyswitch_sums(key_ntt, L, d.data(), ks.data(), ks.data() + N);
+    return ks;
 }
 
 // one group in place of (or next to) its source: mask[2048], body[count]
 void rekey_group(const uint64_t *key_ntt, const uint32_t *mask, const uint32_t *body, size_t count, uint32_t *mask_out,
                  uint32_t *body_out) {
-    std::vector<uint64_t> ks((size_t)2 * N);
-    keyswitch_sums(key_ntt, mask, ks.data(), ks.data() + N);                          // (every mask word is read here)
-    for (int n = 0; n < N; n++) mask_out[n] = store32((uint64_t)0 - ks[n]);
-    for (size_t j = 0; j < count; j++) body_out[j] = store32(((uint64_t)body[j] << 32) - ks[N + j]);
+    const std::vector<uint64_t> ks = keyswitch_sums32(key_ntt, mask);                 // (every mask word is read here)
+    for (int n = 0; n < N; n++) mask_out[n] = round32((uint64_t)0 - ks[n]);
+    for (size_t j = 0; j < count; j++) body_out[j] = round32(((uint64_t)body[j] << 32) - ks[N + j]);
 }
 
 // one group of the packed download for a recipient: the level-11 GLWE of the packing tree, 64-bit
@@ -74,11 +42,10 @@ void rekey_group(const uint64_t *key_ntt, const uint32_t *mask, const uint32_t *
 void rekey_packed_group(const uint64_t *key_ntt, const uint64_t *mask64, const uint64_t *body64, size_t count,
                         uint16_t *mask_out, uint16_t *body_out) {
     std::vector<uint32_t> a(N);
-    for (int n = 0; n < N; n++) a[n] = store32(mask64[n]);
-    std::vector<uint64_t> ks((size_t)2 * N);
-    keyswitch_sums(key_ntt, a.data(), ks.data(), ks.data() + N);
-    for (int n = 0; n < N; n++) mask_out[n] = store16((uint64_t)0 - ks[n]);
-    for (size_t j = 0; j < count; j++) body_out[j] = store16(body64[j] - ks[N + j]);
+    for (int n = 0; n < N; n++) a[n] = round32(mask64[n]);
+    const std::vector<uint64_t> ks = keyswitch_sums32(key_ntt, a.data());
+    for (int n = 0; n < N; n++) mask_out[n] = round16((uint64_t)0 - ks[n]);
+    for (size_t j = 0; j < count; j++) body_out[j] = round16(body64[j] - ks[N + j]);
 }
 
 // one covering group of the packed download of a parked entry: the entry's 32-bit words are the
@@ -87,22 +54,13 @@ void rekey_packed_group(const uint64_t *key_ntt, const uint64_t *mask64, const u
 void store_packed_group(const uint64_t *key_ntt, const uint32_t *mask32, const uint32_t *body32, size_t lo, size_t hi,
                         uint16_t *mask_out, uint16_t *body_out) {
     if (!key_ntt) {                                                  // own key: the storage switch alone
-        for (int n = 0; n < N; n++) mask_out[n] = store16((uint64_t)mask32[n] << 32);
-        for (size_t n = lo; n < hi; n++) body_out[n - lo] = store16((uint64_t)body32[n] << 32);
+        for (int n = 0; n < N; n++) mask_out[n] = round16((uint64_t)mask32[n] << 32);
+        for (size_t n = lo; n < hi; n++) body_out[n - lo] = round16((uint64_t)body32[n] << 32);
         return;
     }
-    std::vector<uint64_t> ks((size_t)2 * N);
-    keyswitch_sums(key_ntt, mask32, ks.data(), ks.data() + N);
-    for (int n = 0; n < N; n++) mask_out[n] = store16((uint64_t)0 - ks[n]);
-    for (size_t n = lo; n < hi; n++) body_out[n - lo] = store16(((uint64_t)body32[n] << 32) - ks[N + n]);
-}
-
-// the key as residues: [L][mask, body][prime][2048], rounded to the 58-bit grid, 1/N folded in
-std::vector<uint64_t> key_to_ntt(const uint64_t *key) {
-    std::vector<uint64_t> key_ntt((size_t)L * 2 * 2 * N);
-    for (size_t pi = 0; pi < (size_t)L * 2; pi++)
-        for (int q = 0; q < 2; q++) torus_poly_to_ntt(key + pi * N, BSK_QUANT_BITS, ntt_prime(q), key_ntt.data() + (pi * 2 + q) * N);
-    return key_ntt;
+    const std::vector<uint64_t> ks = keyswitch_sums32(key_ntt, mask32);
+    for (int n = 0; n < N; n++) mask_out[n] = round16((uint64_t)0 - ks[n]);
+    for (size_t n = lo; n < hi; n++) body_out[n - lo] = round16(((uint64_t)body32[n] << 32) - ks[N + n]);
 }
 
 }  // namespace
@@ -114,7 +72,7 @@ int fhs_rekey_host(const uint64_t *key, const void *mask32_, const void *body32_
     const uint32_t *mask32 = static_cast<const uint32_t *>(mask32_), *body32 = static_cast<const uint32_t *>(body32_);
     uint32_t *mask_out = static_cast<uint32_t *>(mask32_out_), *body_out = static_cast<uint32_t *>(body32_out_);
     if (!key || (n_blocks && (!mask32 || !body32 || !mask_out || !body_out))) return FHS_ERR_ARG;
-    const std::vector<uint64_t> key_ntt = key_to_ntt(key);
+    const std::vector<uint64_t> key_ntt = key_to_ntt(key, (size_t)L * 2);
     const size_t groups = (n_blocks + FHS_PACK_GROUP - 1) / FHS_PACK_GROUP;
     parallel_for(groups, host_threads(16), 1, [&](size_t g) {          // groups are independent, in place too
         const size_t count = std::min<size_t>(FHS_PACK_GROUP, n_blocks - g * FHS_PACK_GROUP);
@@ -128,7 +86,7 @@ int fhs_rekey_packed_host(const uint64_t *key, const uint64_t *mask64, const uin
                           void *body16_) {
     uint16_t *mask16 = static_cast<uint16_t *>(mask16_), *body16 = static_cast<uint16_t *>(body16_);
     if (!key || (n_blocks && (!mask64 || !body64 || !mask16 || !body16))) return FHS_ERR_ARG;
-    const std::vector<uint64_t> key_ntt = key_to_ntt(key);
+    const std::vector<uint64_t> key_ntt = key_to_ntt(key, (size_t)L * 2);
     const size_t groups = (n_blocks + FHS_PACK_GROUP - 1) / FHS_PACK_GROUP;
     parallel_for(groups, host_threads(16), 1, [&](size_t g) {
         const size_t count = std::min<size_t>(FHS_PACK_GROUP, n_blocks - g * FHS_PACK_GROUP);
@@ -153,7 +111,7 @@ int fhs_store_packed_host(const uint64_t *key, const void *mask32_, const void *
     if (count == 0) return FHS_OK;
     if (!mask32 || !body32 || !mask16 || !body16) return FHS_ERR_ARG;
     std::vector<uint64_t> key_ntt;
-    if (key) key_ntt = key_to_ntt(key);
+    if (key) key_ntt = key_to_ntt(key, (size_t)L * 2);
     const size_t t0 = 4 * first_char, t1 = t0 + 4 * count, g0 = t0 / FHS_PACK_GROUP, g1 = (t1 - 1) / FHS_PACK_GROUP;
     parallel_for(g1 - g0 + 1, host_threads(16), 1, [&](size_t k) {
         const size_t base = (g0 + k) * FHS_PACK_GROUP;               // the group's coefficient 0 as a block of the entry

@@ -13,9 +13,10 @@
 // rekey_packed_kernel is the same keyswitch between other formats: 64-bit words in, 16-bit words out (DESIGN.md section
 // 16; host reference fhs_rekey_packed_host), and rekey_entry_packed_kernel takes a window of a parked entry, 32-bit words,
 // to 16-bit words (section 17; fhs_store_packed_host).  The arithmetic between load and store exists once, in
-// keyswitch_sums.
-#include "ntt_transform.h"
+// glwe_keyswitch_sums (glwe_keyswitch.h), which the packing tree calls too.
+#include "glwe_keyswitch.h"
 #include "rekey_kernels.h"
+#include "storage_words.h"
 
 namespace fhs {
 
@@ -23,70 +24,20 @@ namespace fhs {
 
 namespace {
 
-__device__ __forceinline__ uint32_t switch32(uint64_t x) { return (uint32_t)((x + (1ull << 31)) >> 32); }
-__device__ __forceinline__ uint16_t switch16(uint64_t x) { return (uint16_t)((x + (1ull << 47)) >> 48); }
 static_assert(REKEY_LEVELS == 2 && REKEY_BASE_LOG == 16, "the digits are the two 16-bit halves of a 32-bit word");
 
-// The keyswitch between load and store, shared by all three kernels: from the group's mask as 32-bit words in the strided
-// layout (a[r] = word of coefficient lane + 64 r) to ks[o] = (sum_l d_l (*) K[l][j]) of coefficient lane + 64 (2 o + q),
-// the half of output polynomial j that wave (j, q) owns.  Holds the workgroup's one barrier: every wave's loads of `a`
-// are behind it when it returns, so the caller may store over its source.
+// The keyswitch between load and store, shared by all three kernels (glwe_keyswitch.h): from the group's mask as 32-bit
+// words in the strided layout (a[r] = word of coefficient lane + 64 r) to ks[o] of coefficient lane + 64 (2 o + q).
 __device__ __forceinline__ void keyswitch_sums(const uint32_t (&a)[32], const double *key_ntt, const NttTables &tw, char *smem,
                                                int lane, int wave, uint64_t (&ks)[16]) {
-    const int j = wave >> 1;   // output polynomial (0 mask, 1 body)
-    const int q = wave & 1;    // prime
-    double *my = reinterpret_cast<double *>(smem) + wave * LDS_WAVE_SLOTS;
-    const double *sibling = reinterpret_cast<double *>(smem) + (wave ^ 1) * LDS_WAVE_SLOTS;  // other prime
-    uint64_t *my_u = reinterpret_cast<uint64_t *>(my);
-
-    const double p = q ? (double)NTT_P1 : (double)NTT_P0;
-    const double pinv = 1.0 / p;
-    const double p1 = (double)NTT_P1, p1inv = 1.0 / p1;
-    const double *fwd_lane = tw.fwd_lane + q * 32 * 64;
-    const double *inv_lane = tw.inv_lane + q * 32 * 64;
-    const double twA = lane < 32 ? C_FWD_UNI[q][lane] : C_INV_UNI[q][lane];
-    const double twB = C_INV_UNI[q][lane & 31];
-
-    // sum over the digits of NTT(d_l) * NTT(K[l][j]) modulo p
-    typedef double __attribute__((ext_vector_type(2))) double2_t;
-    double acc[32];
-#pragma unroll
-    for (int c = 0; c < 32; c++) acc[c] = 0.0;
-#pragma unroll
-    for (int l = 0; l < REKEY_LEVELS; l++) {
-        double x[32];
-#pragma unroll
-        for (int r = 0; r < 32; r++) {
+    glwe_keyswitch_sums<REKEY_LEVELS>(
+        KeyswitchWave(tw, smem, lane, wave),
+        [a](int r, int l) {
             const uint32_t lo = a[r] & 0xffffu;
             // l = 1: the low half as a signed 16-bit value; l = 0: the high half plus the carry of a negative low digit
-            x[r] = l ? (double)(int16_t)(uint16_t)lo : (double)(int16_t)(uint16_t)((a[r] >> 16) + (lo >= 0x8000u ? 1u : 0u));
-        }
-        __builtin_amdgcn_wave_barrier();
-        ntt_forward(x, my, lane, twA, fwd_lane, p, pinv);
-        // key layout [16][64 lanes][2]: one 16-byte load per lane covers coefficients (c, c + 1) of the contiguous layout
-        const double2_t *key = reinterpret_cast<const double2_t *>(key_ntt + ((((size_t)l * 2 + j) * 2 + q) * POLY_N)) + lane;
-#pragma unroll
-        for (int c = 0; c < 32; c += 2) {
-            const double2_t kv = key[(c >> 1) * 64];
-            const double m0 = mulmod(x[c], kv.x, p, pinv), m1 = mulmod(x[c + 1], kv.y, p, pinv);
-            acc[c] += m0;
-            acc[c + 1] += m1;
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 32; c++) acc[c] = reduce_once(acc[c], p, pinv);   // two products: back inside the inverse's input range
-    __builtin_amdgcn_wave_barrier();
-    ntt_inverse(acc, my, lane, twA, twB, inv_lane, p, pinv);
-    __builtin_amdgcn_wave_barrier();
-
-    // exchange residues with the other prime's wave, CRT for the owned half (coefficients lane + 64 (2 o + q))
-#pragma unroll
-    for (int o = 0; o < 16; o++) ks[o] = 0;
-    if (q == 0) phase_publish_residues<0>(acc, my, lane);
-    else phase_publish_residues<1>(acc, my, lane);
-    __syncthreads();                                  // ... and every wave's mask loads are behind it: stores may begin
-    if (q == 0) phase_crt<0>(acc, ks, sibling, my_u, lane, C_CRT, p1, p1inv);
-    else phase_crt<1>(acc, ks, sibling, my_u, lane, C_CRT, p1, p1inv);
+            return l ? (double)(int16_t)(uint16_t)lo : (double)(int16_t)(uint16_t)((a[r] >> 16) + (lo >= 0x8000u ? 1u : 0u));
+        },
+        key_ntt, 0, ks);
 }
 
 }  // namespace
@@ -111,14 +62,14 @@ __global__ __launch_bounds__(256) void rekey_glwe_kernel(RekeyParams P) {
     if (j == 0) {
         uint32_t *out = P.dst_mask + (size_t)grp * POLY_N;
 #pragma unroll
-        for (int o = 0; o < 16; o++) out[lane + 64 * (2 * o + q)] = switch32((uint64_t)0 - ks[o]);
+        for (int o = 0; o < 16; o++) out[lane + 64 * (2 * o + q)] = round32((uint64_t)0 - ks[o]);
     } else {
         const uint32_t *in = P.src_body + (size_t)grp * REKEY_GROUP;
         uint32_t *out = P.dst_body + (size_t)grp * REKEY_GROUP;
 #pragma unroll
         for (int o = 0; o < 16; o++) {
             const uint32_t n = lane + 64 * (2 * o + q);
-            if (n < count) out[n] = switch32(((uint64_t)in[n] << 32) - ks[o]);
+            if (n < count) out[n] = round32(((uint64_t)in[n] << 32) - ks[o]);
         }
     }
 }
@@ -138,7 +89,7 @@ __global__ __launch_bounds__(256) void rekey_packed_kernel(RekeyPackedParams P) 
     const uint64_t *src_mask = P.src + (size_t)grp * 2 * POLY_N, *src_body = src_mask + POLY_N;
     uint32_t a[32];
 #pragma unroll
-    for (int r = 0; r < 32; r++) a[r] = switch32(src_mask[lane + 64 * r]);
+    for (int r = 0; r < 32; r++) a[r] = round32(src_mask[lane + 64 * r]);
 
     uint64_t ks[16];
     keyswitch_sums(a, P.key_ntt, P.tw, smem, lane, wave, ks);
@@ -146,13 +97,13 @@ __global__ __launch_bounds__(256) void rekey_packed_kernel(RekeyPackedParams P) 
     if (j == 0) {
         uint16_t *out = P.dst_mask + (size_t)grp * POLY_N;
 #pragma unroll
-        for (int o = 0; o < 16; o++) out[lane + 64 * (2 * o + q)] = switch16((uint64_t)0 - ks[o]);
+        for (int o = 0; o < 16; o++) out[lane + 64 * (2 * o + q)] = round16((uint64_t)0 - ks[o]);
     } else {
         uint16_t *out = P.dst_body + (size_t)grp * REKEY_GROUP;
 #pragma unroll
         for (int o = 0; o < 16; o++) {
             const uint32_t n = lane + 64 * (2 * o + q);
-            if (n < count) out[n] = switch16(src_body[n] - ks[o]);
+            if (n < count) out[n] = round16(src_body[n] - ks[o]);
         }
     }
 }
@@ -184,45 +135,41 @@ __global__ __launch_bounds__(256) void rekey_entry_packed_kernel(RekeyEntryPacke
     if (j == 0) {
         uint16_t *out = P.dst_mask + (size_t)grp * POLY_N;
 #pragma unroll
-        for (int o = 0; o < 16; o++) out[lane + 64 * (2 * o + q)] = switch16((uint64_t)0 - ks[o]);
+        for (int o = 0; o < 16; o++) out[lane + 64 * (2 * o + q)] = round16((uint64_t)0 - ks[o]);
     } else {
         const uint32_t *in = P.src_body + (size_t)base;
         uint16_t *out = P.dst_body;
 #pragma unroll
         for (int o = 0; o < 16; o++) {
             const uint32_t n = lane + 64 * (2 * o + q);
-            if (lo <= n && n < hi) out[base + n - P.first_coef] = switch16(((uint64_t)in[n] << 32) - ks[o]);
+            if (lo <= n && n < hi) out[base + n - P.first_coef] = round16(((uint64_t)in[n] << 32) - ks[o]);
         }
     }
 }
 
-static size_t rekey_lds_bytes() { return (size_t)4 * LDS_WAVE_SLOTS * sizeof(double); }
-
 hipError_t prepare_device_for_rekey() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(rekey_glwe_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)rekey_lds_bytes());
+                                       (int)keyswitch_lds_bytes());
     if (e != hipSuccess) return e;
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(rekey_packed_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)rekey_lds_bytes());
+                            (int)keyswitch_lds_bytes());
     if (e != hipSuccess) return e;
     return hipFuncSetAttribute(reinterpret_cast<const void *>(rekey_entry_packed_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)rekey_lds_bytes());
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)keyswitch_lds_bytes());
 }
 
 hipError_t launch_rekey_glwe(const RekeyParams &p, hipStream_t s) {
     if (p.groups <= 0 || p.total == 0 || !p.src_mask || !p.src_body || !p.dst_mask || !p.dst_body || !p.key_ntt)
         return hipErrorInvalidValue;
-    if ((size_t)p.total > (size_t)p.groups * REKEY_GROUP || (size_t)p.total <= (size_t)(p.groups - 1) * REKEY_GROUP)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rekey_glwe_kernel, dim3(p.groups), dim3(256), rekey_lds_bytes(), s, p);
+    if (!fills_groups(p.total, p.groups, REKEY_GROUP)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rekey_glwe_kernel, dim3(p.groups), dim3(256), keyswitch_lds_bytes(), s, p);
     return hipGetLastError();
 }
 
 hipError_t launch_rekey_packed(const RekeyPackedParams &p, hipStream_t s) {
     if (p.groups <= 0 || p.total == 0 || !p.src || !p.dst_mask || !p.dst_body || !p.key_ntt) return hipErrorInvalidValue;
-    if ((size_t)p.total > (size_t)p.groups * REKEY_GROUP || (size_t)p.total <= (size_t)(p.groups - 1) * REKEY_GROUP)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rekey_packed_kernel, dim3(p.groups), dim3(256), rekey_lds_bytes(), s, p);
+    if (!fills_groups(p.total, p.groups, REKEY_GROUP)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rekey_packed_kernel, dim3(p.groups), dim3(256), keyswitch_lds_bytes(), s, p);
     return hipGetLastError();
 }
 
@@ -230,9 +177,8 @@ hipError_t launch_rekey_entry_packed(const RekeyEntryPackedParams &p, hipStream_
     if (p.groups <= 0 || p.body_words == 0 || !p.src_mask || !p.src_body || !p.dst_mask || !p.dst_body || !p.key_ntt)
         return hipErrorInvalidValue;
     const size_t end = (size_t)p.first_coef + p.body_words;          // the last covering group holds its last coefficient
-    if (p.first_coef >= (uint32_t)REKEY_GROUP || end > (size_t)p.groups * REKEY_GROUP || end <= (size_t)(p.groups - 1) * REKEY_GROUP)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rekey_entry_packed_kernel, dim3(p.groups), dim3(256), rekey_lds_bytes(), s, p);
+    if (p.first_coef >= (uint32_t)REKEY_GROUP || !fills_groups(end, p.groups, REKEY_GROUP)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(rekey_entry_packed_kernel, dim3(p.groups), dim3(256), keyswitch_lds_bytes(), s, p);
     return hipGetLastError();
 }
 

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "pack_kernels.h"
+#include "storage_words.h"
 #include "store_kernels.h"
 
 namespace fhs {
@@ -19,8 +20,6 @@ namespace fhs {
 namespace {
 
 typedef uint64_t __attribute__((ext_vector_type(2))) u64x2_t;
-
-__device__ __forceinline__ uint32_t store_round32(uint64_t x) { return (uint32_t)((x + (1ull << 31)) >> 32); }
 
 // grid (8, groups): workgroups 0..3 of a group switch the four quarters of its mask, 4..7 those of its body, of which only
 // the words of present blocks are written (the entry holds no others).
@@ -34,11 +33,9 @@ __global__ __launch_bounds__(256) void store_switch32_kernel(const uint64_t *__r
     const u64x2_t v = *reinterpret_cast<const u64x2_t *>(glwe + ((size_t)grp * 2 + col) * POLY_N + w);
     // group first_group + grp of the ENTRY: masks and bodies both advance by 2048 words per group
     uint32_t *dst = (col ? body32 : mask32) + (size_t)(first_group + grp) * POLY_N + w;
-    if (w + 1 < count) *reinterpret_cast<uint2 *>(dst) = make_uint2(store_round32(v.x), store_round32(v.y));
-    else *dst = store_round32(v.x);                                          // an odd block count's last body
+    if (w + 1 < count) *reinterpret_cast<uint2 *>(dst) = make_uint2(round32(v.x), round32(v.y));
+    else *dst = round32(v.x);                                          // an odd block count's last body
 }
-
-__device__ __forceinline__ uint16_t store_round16(uint32_t w) { return (uint16_t)((w + (1u << 15)) >> 16); }   // wraps to 0
 
 // One launch over both arrays: quads [0, mask_quads) are the covering groups' masks, [mask_quads, mask_quads + body_quads)
 // the window's bodies (body32 points at the window's first body inside the entry, body16 at output word 0).
@@ -74,8 +71,7 @@ hipError_t launch_store_switch16(const uint32_t *mask32, const uint32_t *body32,
 
 hipError_t launch_store_switch32(const uint64_t *d_glwe, uint32_t *entry_mask32, uint32_t *entry_body32,
                                  uint32_t first_group, int groups, uint32_t total, hipStream_t s) {
-    if (groups <= 0 || (size_t)total > (size_t)groups * PACK_GROUP || (size_t)total <= (size_t)(groups - 1) * PACK_GROUP)
-        return hipErrorInvalidValue;
+    if (!fills_groups(total, groups, PACK_GROUP)) return hipErrorInvalidValue;
     if (((uintptr_t)d_glwe & 15) || ((uintptr_t)entry_mask32 & 7) || ((uintptr_t)entry_body32 & 7)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(store_switch32_kernel, dim3(8, groups), dim3(256), 0, s, d_glwe, entry_mask32, entry_body32, first_group,
                        total);

@@ -11,18 +11,19 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 FLAGS = "Makefile:flags"     # not a file: the compiler-flag lines of the Makefile (CXXFLAGS, ARCH, per-file SCHED_ strategy)
 _FFT = ["fft_transform.h", "fft_device.h", "fft_consts.inc", FLAGS]
 _NTT = ["ntt_transform.h", "ntt_consts.inc", FLAGS]
+_KS = ["glwe_keyswitch.h", "storage_words.h"] + _NTT     # the GLWE keyswitch shared by the packing tree and the re-keys
 KERNEL_SOURCES = {
     "blind_rotate_fft_kernel": ["fft_kernels.hip"] + _FFT,
     "blind_rotate_fft4_kernel": ["fft4_kernels.hip"] + _FFT[1:],
     "blind_rotate_mb2_kernel": ["fftmb_kernels.hip"] + _FFT,
     "blind_rotate_kernel": ["pbs_kernels.hip"] + _NTT,
     "blind_rotate_ntt_mb2_kernel": ["nttmb_kernels.hip"] + _NTT,
-    "pack_level_kernel": ["pack_kernels.hip", "pack_kernels.h"] + _NTT,
-    "rekey_glwe_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _NTT,
-    "rekey_packed_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _NTT,
-    "rekey_entry_packed_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _NTT,
-    "store_switch16_kernel": ["store_kernels.hip", "store_kernels.h", FLAGS],
-    "pack_switch16_kernel": ["pack_kernels.hip", "pack_kernels.h", FLAGS],
+    "pack_level_kernel": ["pack_kernels.hip", "pack_kernels.h"] + _KS,
+    "rekey_glwe_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _KS,
+    "rekey_packed_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _KS,
+    "rekey_entry_packed_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _KS,
+    "store_switch16_kernel": ["store_kernels.hip", "store_kernels.h", "storage_words.h", FLAGS],
+    "pack_switch16_kernel": ["pack_kernels.hip", "pack_kernels.h", "storage_words.h", FLAGS],
     "keyswitch_mfma_kernel": ["ks_kernels.hip", FLAGS],
     "keyswitch_mfma2_kernel": ["ks_kernels.hip", FLAGS],
     "ks_digits_tile_kernel": ["ks_kernels.hip", FLAGS],

@@ -8,6 +8,8 @@ import random
 import numpy as np
 import pytest
 
+from ring_util import digits, glwe_phases, negacyclic
+
 N = 2048
 GLWE_NOISE = 2.9403601535432533e-16          # client.cpp: GLWE noise as a fraction of the torus (packing key, fresh blocks)
 PACK_BASE_LOG, PACK_LEVELS = 16, 3
@@ -27,45 +29,10 @@ def _ascii(rng, n):
     return "".join(chr(rng.randrange(1, 128)) for _ in range(n))
 
 
-def _mul_binary(a, s):
-    """negacyclic a (*) s in wrapping uint64, s binary"""
-    out = np.zeros(N, np.uint64)
-    for j in np.nonzero(s)[0]:
-        j = int(j)
-        out[j:] += a[:N - j]
-        out[:j] -= a[N - j:]
-    return out
-
-
-def _negacyclic(d, k):
-    """sum_i d[i] X^i k(X) mod X^N + 1 in wrapping uint64 (d: signed digits as int64)"""
-    out = np.zeros(N, np.uint64)
-    du = d.astype(np.int64).view(np.uint64)
-    for i in np.nonzero(d)[0]:
-        i = int(i)
-        out[i:] += du[i] * k[:N - i]
-        out[:i] -= du[i] * k[N - i:]
-    return out
-
-
 def _automorphism(a, g):
     idx = (np.arange(N, dtype=np.int64) * g) % (2 * N)
     out = np.zeros(N, np.uint64)
     out[idx % N] = np.where(idx >= N, np.uint64(0) - a, a)
-    return out
-
-
-def _digits(x):
-    """ISSUE step 4: L signed digits of beta bits, most significant first"""
-    L, beta = PACK_LEVELS, PACK_BASE_LOG
-    v = ((x + np.uint64(1 << (63 - L * beta))) >> np.uint64(64 - L * beta)) & np.uint64((1 << (L * beta)) - 1)
-    carry = np.zeros(N, np.int64)
-    out = [None] * L
-    for l in range(L - 1, -1, -1):
-        d = (v & np.uint64((1 << beta) - 1)).astype(np.int64) + carry
-        v = v >> np.uint64(beta)
-        carry = (d >= (1 << (beta - 1))).astype(np.int64)
-        out[l] = d - (carry << beta)
     return out
 
 
@@ -79,17 +46,13 @@ def _node_schoolbook(key, lv, e, o):
         T[c, :t] = np.uint64(0) - o[c, N - t:]
     P, M = e + T, e - T
     a1, b1 = _automorphism(M[0], g), _automorphism(M[1], g)
-    dig = _digits(a1)
+    dig = digits(a1, PACK_LEVELS)
     assert all(int(d.min()) >= -(1 << 15) and int(d.max()) < (1 << 15) for d in dig)
     sm, sb = np.zeros(N, np.uint64), np.zeros(N, np.uint64)
     for l in range(PACK_LEVELS):
-        sm += _negacyclic(dig[l], kg[l, 0])
-        sb += _negacyclic(dig[l], kg[l, 1])
+        sm += negacyclic(dig[l], kg[l, 0])
+        sb += negacyclic(dig[l], kg[l, 1])
     return np.stack([P[0] - sm, P[1] + b1 - sb])
-
-
-def _phases(mask64, body64, glwe_sk):
-    return np.stack([body64[g] - _mul_binary(mask64[g], glwe_sk) for g in range(mask64.shape[0])])
 
 
 def _predicted_pack_sigma():
@@ -174,7 +137,7 @@ def test_noise_of_a_full_group(ck):
     m64, b64 = pack_host(ck.packing_key(), blocks)
     _, glwe_sk = ck.secret_keys()
     want = vals.astype(np.uint64) << np.uint64(59)
-    err = (_phases(m64, b64, glwe_sk)[0] - want).view(np.int64).astype(np.float64)
+    err = (glwe_phases(m64[0], b64[0], glwe_sk) - want).view(np.int64).astype(np.float64)
     sigma, predicted = float(err.std()), _predicted_pack_sigma()
     print("packing sigma: measured 2^%.2f, derived 2^%.2f" % (math.log2(sigma), math.log2(predicted)))
     assert abs(math.log2(predicted) - 43.1) < 0.1                # the figure DESIGN.md section 11 quotes
@@ -184,7 +147,7 @@ def test_noise_of_a_full_group(ck):
     m16 = p.mask16.astype(np.uint64) << np.uint64(48)
     b16 = np.zeros(N, np.uint64)
     b16[:2048] = p.body16.astype(np.uint64) << np.uint64(48)
-    err16 = (_phases(m16, b16[None, :], glwe_sk)[0] - want).view(np.int64).astype(np.float64)
+    err16 = (glwe_phases(m16[0], b16, glwe_sk) - want).view(np.int64).astype(np.float64)
     unit = 2.0 ** 48 * math.sqrt((1 + float(glwe_sk.sum())) / 12)
     print("after the 16-bit switch: sigma 2^%.2f, derived 2^%.2f, max 2^%.2f" %
           (math.log2(err16.std()), math.log2(unit), math.log2(np.abs(err16).max())))

@@ -12,6 +12,8 @@ import sys
 import numpy as np
 import pytest
 
+from ring_util import digits32, negacyclic, packed_phases, round16
+
 N = 2048
 LEVELS = 2
 FHS_ERR_STATE = -3
@@ -24,46 +26,16 @@ BOUNDARY = ((0x000000007FFFFFFF, 0x00000000), (0x0000000080000000, 0x00000001), 
 SENTINEL = 0xA5A5
 
 
-def _negacyclic(d, k):
-    """sum_i d[i] X^i (*) k in Z_2^64[X]/(X^N + 1): d int64 (small), k uint64, schoolbook with wrapping words"""
-    ext = np.concatenate([U64(0) - k, k])                        # ext[m] = +-k[m mod N]: the sign of X^N = -1
-    rows = np.lib.stride_tricks.sliding_window_view(ext[1:], N)[:N, ::-1]   # rows[n][i] = ext[n - i + N]
-    return (rows * d.astype(np.int64).view(U64)[None, :]).sum(axis=1, dtype=U64)
-
-
-def _digits(a):
-    lo = a & np.uint32(0xffff)
-    c = (lo >= 0x8000).astype(np.uint32)
-    d1 = lo.astype(np.uint16).view(np.int16).astype(np.int64)
-    d0 = (((a >> np.uint32(16)) + c) & np.uint32(0xffff)).astype(np.uint16).view(np.int16).astype(np.int64)
-    return d0, d1
-
-
-def _round16(x):
-    return ((x + U64(1 << 47)) >> U64(48)).astype(np.uint16)
-
-
 def _np_group(key, mask64, body64, count):
     """the formulas of one group"""
     K = ((key + U64(32)) & ~U64(63)).reshape(LEVELS, 2, N)        # round_to_grid(., 6)
     a = ((mask64 + U64(1 << 31)) >> U64(32)).astype(np.uint32)    # wraps at the top
-    d = _digits(a)
+    d = digits32(a)
     A = a.astype(U64) << U64(32)
     assert np.array_equal(d[0].view(U64) << U64(48), A - (d[1].view(U64) << U64(32)))         # A = d_0 2^48 + d_1 2^32
     assert all(int(x.min()) >= -(1 << 15) and int(x.max()) < (1 << 15) for x in d)
-    s = [sum((_negacyclic(d[l], K[l, col]) for l in range(LEVELS)), np.zeros(N, U64)) for col in range(2)]
-    return a, _round16(U64(0) - s[0]), _round16(body64[:count] - s[1][:count])
-
-
-def _phases16(p, n_blocks, glwe_sk):
-    """body - mask (*) S of every block of a packed string, words widened by << 48"""
-    out = np.zeros(n_blocks, U64)
-    s = glwe_sk.astype(np.int64)
-    for g in range(p.mask16.shape[0]):
-        count = min(N, n_blocks - g * N)
-        a_s = _negacyclic(s, p.mask16[g].astype(U64) << U64(48))
-        out[g * N:g * N + count] = (p.body16[g * N:g * N + count].astype(U64) << U64(48)) - a_s[:count]
-    return out
+    s = [sum((negacyclic(d[l], K[l, col]) for l in range(LEVELS)), np.zeros(N, U64)) for col in range(2)]
+    return a, round16(U64(0) - s[0]), round16(body64[:count] - s[1][:count])
 
 
 @pytest.fixture(scope="module")
@@ -97,7 +69,7 @@ def test_host_reference_equals_schoolbook_in_every_word():
     mask[0, :len(words)] = words
     a, wm, wb = _np_group(key, mask[0], body[0], N)
     assert [int(x) for x in a[:len(words)]] == [want for _, want in BOUNDARY]
-    assert int(_digits(a[3:4])[1][0]) == -0x8000 and int(_digits(a[3:4])[0][0]) == 1           # the low digit turns negative
+    assert int(digits32(a[3:4])[1][0]) == -0x8000 and int(digits32(a[3:4])[0][0]) == 1           # the low digit turns negative
     got = rekey_packed_host(key, mask, body, N)
     assert np.array_equal(got.mask16[0], wm) and np.array_equal(got.body16, wb)
     # ... and each of them alone, throughout a mask, with fewer bodies than coefficients
@@ -160,8 +132,8 @@ def test_noise_against_an_own_key_download(flow):
     want = np.array([(ord(ch) >> (2 * k)) & 3 for ch in text for k in range(4)], U64) << U64(59)
     sa, sb = a.secret_keys()[1], b.secret_keys()[1]
     own = pack_switch16(m64, b64, n_blocks)
-    e_own = (_phases16(own, n_blocks, sa) - want).view(np.int64).astype(np.float64)
-    e_rec = (_phases16(p, n_blocks, sb) - want).view(np.int64).astype(np.float64)
+    e_own = (packed_phases(own, sa) - want).view(np.int64).astype(np.float64)
+    e_rec = (packed_phases(p, sb) - want).view(np.int64).astype(np.float64)
     s_own, s_rec = float(e_own.std()), float(e_rec.std())
     derived = 2.0 ** 48 * math.sqrt((1 + float(sb.sum())) / 12)
     print("recipient download: sigma 2^%.2f, own-key sigma 2^%.2f, derived 2^%.2f, max |e| 2^%.2f (own key 2^%.2f)" %

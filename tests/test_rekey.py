@@ -10,6 +10,8 @@ import struct
 import numpy as np
 import pytest
 
+from ring_util import block_phases, digits32, negacyclic, round32
+
 N = 2048
 BIG_CT = 2049
 GLWE_NOISE = 2.9403601535432533e-16          # client.cpp: GLWE noise as a fraction of the torus
@@ -20,26 +22,6 @@ CHOSEN = (0x00000000, 0x00008000, 0x7FFF8000, 0x80000000, 0xFFFFFFFF, 0x00007FFF
 U64 = np.uint64
 
 
-def _negacyclic(d, k):
-    """sum_i d[i] X^i (*) k in Z_2^64[X]/(X^N + 1): d int64 (small), k uint64, schoolbook with wrapping words"""
-    ext = np.concatenate([U64(0) - k, k])                        # ext[m] = +-k[m mod N]: the sign of X^N = -1
-    rows = np.lib.stride_tricks.sliding_window_view(ext[1:], N)[:N, ::-1]   # rows[n][i] = ext[n - i + N]
-    return (rows * d.astype(np.int64).view(U64)[None, :]).sum(axis=1, dtype=U64)
-
-
-def _digits(mask32):
-    a = mask32.astype(np.uint32)
-    lo = a & np.uint32(0xffff)
-    c = (lo >= 0x8000).astype(np.uint32)
-    d1 = lo.astype(np.uint16).view(np.int16).astype(np.int64)
-    d0 = (((a >> np.uint32(16)) + c) & np.uint32(0xffff)).astype(np.uint16).view(np.int16).astype(np.int64)
-    return d0, d1
-
-
-def _round32(x):
-    return ((x + U64(1 << 31)) >> U64(32)).astype(np.uint32)
-
-
 def _np_rekey(key, mask32, body32, n_blocks):
     """the issue's formulas, group by group"""
     K = ((key + U64(32)) & ~U64(63)).reshape(LEVELS, 2, N)        # round_to_grid(., 6)
@@ -47,20 +29,15 @@ def _np_rekey(key, mask32, body32, n_blocks):
     m_out, b_out = np.zeros_like(mask32), np.zeros(n_blocks, np.uint32)
     for g in range(mask32.shape[0]):
         count = min(N, n_blocks - g * N)
-        d = _digits(mask32[g])
+        d = digits32(mask32[g])
         A = mask32[g].astype(U64) << U64(32)
         assert np.array_equal(d[0].view(U64) << U64(48), A - (d[1].view(U64) << U64(32)))     # A = d_0 2^48 + d_1 2^32
         assert all(int(x.min()) >= -(1 << 15) and int(x.max()) < (1 << 15) for x in d)
-        s = [sum((_negacyclic(d[l], K[l, col]) for l in range(LEVELS)), np.zeros(N, U64)) for col in range(2)]
-        m_out[g] = _round32(U64(0) - s[0])
+        s = [sum((negacyclic(d[l], K[l, col]) for l in range(LEVELS)), np.zeros(N, U64)) for col in range(2)]
+        m_out[g] = round32(U64(0) - s[0])
         b = body32[g * N:g * N + count].astype(U64) << U64(32)
-        b_out[g * N:g * N + count] = _round32(b - s[1][:count])
+        b_out[g * N:g * N + count] = round32(b - s[1][:count])
     return m_out, b_out
-
-
-def _phases(blocks, glwe_sk):
-    blocks = blocks.reshape(-1, BIG_CT)
-    return blocks[:, N] - (blocks[:, :N] * glwe_sk[None, :]).sum(axis=1, dtype=U64)
 
 
 @pytest.fixture(scope="module")
@@ -130,7 +107,7 @@ def test_it_decrypts_under_the_new_key_with_the_derived_noise(clients):
         wrong = None
     assert wrong != text
     sa, sb = a.secret_keys()[1], b.secret_keys()[1]
-    added = (_phases(after, sb) - _phases(before, sa)).view(np.int64).astype(np.float64)
+    added = (block_phases(after, sb) - block_phases(before, sa)).view(np.int64).astype(np.float64)
     s_glwe = GLWE_NOISE * 2.0 ** 64
     derived = math.sqrt(LEVELS * N * 2.0 ** 32 / 12 * s_glwe ** 2 + 2.0 ** 64 / 12 * (1 + float(sb.sum())))
     sigma = float(added.std())
@@ -145,7 +122,7 @@ def _key_error(key, s_from, s_to):
     K = key.reshape(LEVELS, 2, N)
     out = []
     for l in range(LEVELS):
-        e = K[l, 1] - _negacyclic(s_to.astype(np.int64), K[l, 0]) - (s_from << U64(64 - BASE_LOG * (l + 1)))
+        e = K[l, 1] - negacyclic(s_to.astype(np.int64), K[l, 0]) - (s_from << U64(64 - BASE_LOG * (l + 1)))
         out.append(e.view(np.int64))
     return np.stack(out)
 

@@ -10,6 +10,8 @@ import random
 import numpy as np
 import pytest
 
+from ring_util import block_phases, round32
+
 N = 2048
 BIG_CT = 2049
 GLWE_NOISE = 2.9403601535432533e-16          # client.cpp: GLWE noise as a fraction of the torus (packing key, fresh blocks)
@@ -40,19 +42,9 @@ def _ascii(rng, n):
     return "".join(chr(rng.randrange(1, 128)) for _ in range(n))
 
 
-def _round32(x):
-    return ((x + np.uint64(1 << 31)) >> np.uint64(32)).astype(np.uint32)
-
-
-def _block_phases(blocks, glwe_sk):
-    """b - <a, s> of classic blocks [n][2049] under the big LWE key (the flattened GLWE key), wrapping uint64"""
-    blocks = blocks.reshape(-1, BIG_CT)
-    return blocks[:, N] - (blocks[:, :N] * glwe_sk[None, :]).sum(axis=1, dtype=np.uint64)
-
-
 def _block_values(blocks, glwe_sk):
     """value mod 32 of every block: the phase rounded to the 2^59 grid"""
-    return (((_block_phases(blocks, glwe_sk) + np.uint64(1 << 58)) >> np.uint64(59)) & np.uint64(31)).astype(np.uint8)
+    return (((block_phases(blocks, glwe_sk) + np.uint64(1 << 58)) >> np.uint64(59)) & np.uint64(31)).astype(np.uint8)
 
 
 def _predicted_pack_sigma():
@@ -89,11 +81,11 @@ def test_switch32_equals_numpy_in_every_word():
         c = pack_switch32(m64, b64, n_blocks)
         assert isinstance(c, CompactFheString) and len(c) == n_blocks // 4
         assert c.mask32.shape == (g, N) and c.body32.shape == (n_blocks,)
-        assert np.array_equal(c.mask32, _round32(m64)), n_blocks
+        assert np.array_equal(c.mask32, round32(m64)), n_blocks
         assert list(c.mask32[0, :4]) == [0, 0, 1, 0]
-        assert np.array_equal(c.body32, _round32(b64).reshape(-1)[:n_blocks]), n_blocks   # group g's bodies start at 2048 g
+        assert np.array_equal(c.body32, round32(b64).reshape(-1)[:n_blocks]), n_blocks   # group g's bodies start at 2048 g
     m32, b32 = pack_switch32(m64[:1], b64[:1], 3)                               # not whole characters: the raw arrays
-    assert np.array_equal(m32, _round32(m64[:1])) and np.array_equal(b32, _round32(b64[0, :3]))
+    assert np.array_equal(m32, round32(m64[:1])) and np.array_equal(b32, round32(b64[0, :3]))
 
 
 def test_round_trip_and_windows(ck):
@@ -133,7 +125,7 @@ def test_noise_of_restored_blocks(ck):
     restored = pack_switch32(*pack_host(ck.packing_key(), blocks), 2048).expand()
     _, glwe_sk = ck.secret_keys()
     want = vals.astype(np.uint64) << np.uint64(59)
-    err = (_block_phases(restored, glwe_sk) - want).view(np.int64).astype(np.float64)
+    err = (block_phases(restored, glwe_sk) - want).view(np.int64).astype(np.float64)
     sigma_pack = _predicted_pack_sigma()
     sigma_32 = 2.0 ** 32 * math.sqrt((1 + float(glwe_sk.sum())) / 12)
     predicted = math.sqrt(sigma_pack ** 2 + sigma_32 ** 2)

@@ -14,6 +14,8 @@ import sys
 import numpy as np
 import pytest
 
+from ring_util import packed_phases
+
 N = 2048
 FHS_ERR_ARG, FHS_ERR_STATE = -1, -3
 U64 = np.uint64
@@ -168,20 +170,6 @@ def test_no_word_outside_the_window_is_written():
     assert (m16 == SENTINEL).all() and (b16 == SENTINEL).all()
 
 
-def _negacyclic(d, k):
-    """sum_i d[i] X^i (*) k in Z_2^64[X]/(X^N + 1): d int64 (small), k uint64, schoolbook with wrapping words"""
-    ext = np.concatenate([U64(0) - k, k])
-    rows = np.lib.stride_tricks.sliding_window_view(ext[1:], N)[:N, ::-1]
-    return (rows * d.astype(np.int64).view(U64)[None, :]).sum(axis=1, dtype=U64)
-
-
-def _phases16(p, glwe_sk):
-    """body - mask (*) S of every block of a (windowed) packed string, words widened by << 48"""
-    s = glwe_sk.astype(np.int64)
-    a_s = np.concatenate([_negacyclic(s, m.astype(U64) << U64(48)) for m in p.mask16])
-    return (p.body16.astype(U64) << U64(48)) - a_s[p.first_coef:p.first_coef + p.body16.size]
-
-
 def test_the_flow_decrypts_under_the_own_key_and_under_the_recipients(flow):
     from fhestring_amd.api import store_packed_host
     a, b, text, c, key = flow
@@ -208,8 +196,8 @@ def test_noise(flow):
     a, b, text, c, key = flow
     want = np.array([(ord(ch) >> (2 * k)) & 3 for ch in text for k in range(4)], U64) << U64(59)
     sa, sb = a.secret_keys()[1], b.secret_keys()[1]
-    e_own = (_phases16(store_packed_host(None, c), sa) - want).view(np.int64).astype(np.float64)
-    e_rec = (_phases16(store_packed_host(key, c), sb) - want).view(np.int64).astype(np.float64)
+    e_own = (packed_phases(store_packed_host(None, c), sa) - want).view(np.int64).astype(np.float64)
+    e_rec = (packed_phases(store_packed_host(key, c), sb) - want).view(np.int64).astype(np.float64)
     s_own, s_rec = float(e_own.std()), float(e_rec.std())
     derived = 2.0 ** 48 * math.sqrt((1 + float(sb.sum())) / 12)
     print("store download: own-key sigma 2^%.2f, recipient sigma 2^%.2f, derived 2^%.2f, max |e| 2^%.2f / 2^%.2f" %
@@ -218,7 +206,7 @@ def test_noise(flow):
     assert s_own / 2 < s_rec < s_own * 2
     # a window's phases are the whole entry's, block for block: the window changes no word
     w = store_packed_host(key, c, 511, 2)
-    assert np.array_equal(_phases16(w, sb), _phases16(store_packed_host(key, c), sb)[2044:2052])
+    assert np.array_equal(packed_phases(w, sb), packed_phases(store_packed_host(key, c), sb)[2044:2052])
 
 
 def test_at_forms_of_the_client_decryption(clients):

@@ -2,8 +2,9 @@
 """Known-answer digests of the host-only client code -> tests/golden/client_kat.json.  CPU only, a few seconds.
 
 One insecure seeded client, MyClientKey(0xF5E57121), and everything the library derives from it on the host: the keys of
-every kind, the first string in each of the three ciphertext formats with its host expansion, and the host packing of
-that string.  Per array the file keeps the SHA-256 of its little-endian words, the first and the last word (the style
+every kind, the first string in each of the three ciphertext formats with its host expansion, the host packing of
+that string, and the re-key family (a re-key key to a second seeded client, the three host references of the GLWE
+keyswitch on that string and on two groups of random words).  Per array the file keeps the SHA-256 of its little-endian words, the first and the last word (the style
 of tests/golden/pbs_kat.json).  These are the product's own outputs, frozen: key generation, the generator streams, the
 exact host NTT behind pack_host and the thread fan-outs may be reorganised, but no word may change.  Regenerate only
 when a change of the client's outputs is intended, and say so in the commit:
@@ -63,6 +64,34 @@ def records():
     p32 = api.pack_switch32(mask64, body64, blocks.shape[0])
     rec["pack_mask32"], rec["pack_body32"] = digest(p32.mask32), digest(p32.body32)
     assert ck.decrypt_str_raw(chars) == TEXT and ck.decrypt_packed(p16) == TEXT
+    # the re-key family (every GLWE keyswitch besides the packing tree's), after everything above so that no earlier
+    # call counter moves: the first key made into a second seeded client, then the three host references on the string
+    # above and on two groups of seeded random public words, the second group holding 4 blocks
+    other = api.MyClientKey(SEED + 1)
+    rk = ck.rekey_key(other)
+    rec["rekey_key"] = digest(rk)
+
+    def rekey_family(tag, compact, m64, b64, first_char, count):
+        n = 4 * len(compact)
+        r = api.rekey_host(rk, compact)
+        rec[tag + "rekey_mask32"], rec[tag + "rekey_body32"] = digest(r.mask32), digest(r.body32)
+        r = api.rekey_packed_host(rk, m64, b64, n)
+        rec[tag + "rekey_packed_mask16"], rec[tag + "rekey_packed_body16"] = digest(r.mask16), digest(r.body16)
+        for name, key in (("own", None), ("to", rk)):
+            r = api.store_packed_host(key, compact, first_char, count)
+            rec[tag + "store_%s_mask16" % name], rec[tag + "store_%s_body16" % name] = digest(r.mask16), digest(r.body16)
+
+    rekey_family("", p32, mask64, body64, 3, 5)
+    rng = np.random.default_rng(SEED)
+    n_big = api.PACK_GROUP + 4
+    big32 = api.CompactFheString(n_big // 4, rng.integers(0, 1 << 32, (2, api.POLY_N), dtype=np.uint32),
+                                 rng.integers(0, 1 << 32, n_big, dtype=np.uint32))
+    big_m64, big_b64 = (rng.integers(0, 1 << 64, (2, api.POLY_N), dtype=np.uint64) for _ in range(2))
+    rekey_family("big_", big32, big_m64, big_b64, 510, 3)
+    big_blocks = rng.integers(0, 1 << 64, (n_big, blocks.shape[-1]), dtype=np.uint64)
+    big_mask64, big_body64 = api.pack_host(pack_key, big_blocks)
+    rec["big_pack_mask64"], rec["big_pack_body64"] = digest(big_mask64), digest(big_body64)
+    other.close()
     return rec
 
 
