@@ -1464,6 +1464,107 @@ class MyServerKey:
         f = self._chars(flags)
         return self._wide("fhs_flags_count_wide", _harr(f), len(f))
 
+    # ---- clear tables and classes on encrypted characters ----
+    @staticmethod
+    def class_set(cls):
+        """The 32-byte bitmap of a character class: bytes, a set (any iterable) of ints, or a spec such as "a-zA-Z0-9_",
+        with a leading ^ for the complement; x-y is a range, a - at either end and every other character itself."""
+        if isinstance(cls, str):
+            spec = cls.encode("latin-1")
+            negate = spec.startswith(b"^")
+            spec, members, i = spec[1:] if negate else spec, set(), 0
+            while i < len(spec):
+                if i + 2 < len(spec) and spec[i + 1] == 0x2D:
+                    if spec[i + 2] < spec[i]:
+                        raise ValueError("character class: range out of order in %r" % cls)
+                    members.update(range(spec[i], spec[i + 2] + 1))
+                    i += 3
+                else:
+                    members.add(spec[i])
+                    i += 1
+            if negate:
+                members = set(range(256)) - members
+        else:
+            members = set(int(v) for v in cls)
+            if any(v < 0 or v > 255 for v in members):
+                raise ValueError("character class: members are bytes")
+        bits = bytearray(32)
+        for v in members:
+            bits[v >> 3] |= 1 << (v & 7)
+        return bytes(bits)
+
+    def map_clear(self, string, table):
+        """fhs_str_map_clear: every buffer byte x becomes table[x] (256 entries), NULs included."""
+        table = bytes(table)
+        if len(table) != 256:
+            raise ValueError("map_clear: the table has 256 entries")
+        s = self._chars(string)
+        out = (C.c_uint64 * max(1, len(s)))()
+        self.ctx._check(self.ctx._L.fhs_str_map_clear(self.ctx._h, _harr(s), len(s), table, out))
+        return FheString([FheAsciiChar(self, out[i]) for i in range(len(s))])
+
+    def translate(self, string, mapping):
+        """bytes.translate on an encrypted string: mapping is a dict {byte: byte} (ints or one-character str / bytes) or
+        a 256-byte table (bytes.maketrans).  Bytes that are not mentioned stay; 0 -> 0 unless the mapping says otherwise."""
+        if isinstance(mapping, dict):
+            as_int = lambda v: v if isinstance(v, int) else (v.encode("latin-1") if isinstance(v, str) else bytes(v))[0]
+            table = bytearray(range(256))
+            for k, v in mapping.items():
+                table[as_int(k)] = as_int(v)
+            mapping = bytes(table)
+        return self.map_clear(string, mapping)
+
+    def class_flags(self, string, cls):
+        """fhs_str_class_flags: one 0/1 flag char per buffer character, 1 iff the byte is in the class (class_set)."""
+        s = self._chars(string)
+        out = (C.c_uint64 * max(1, len(s)))()
+        self.ctx._check(self.ctx._L.fhs_str_class_flags(self.ctx._h, _harr(s), len(s), self.class_set(cls), out))
+        return FheString([FheAsciiChar(self, out[i]) for i in range(len(s))])
+
+    def in_class(self, char_or_string, cls):
+        """A char: its 0/1 flag char; a string: the flags of its characters (class_flags)."""
+        if isinstance(char_or_string, FheAsciiChar):
+            return self.class_flags([char_or_string], cls)[0]
+        return self.class_flags(char_or_string, cls)
+
+    def find_class(self, string, cls):
+        """Index of the first character in the class as find returns it (255 if none); at most 256 characters."""
+        s = self._chars(string)
+        out = C.c_uint64()
+        rc = self.ctx._L.fhs_str_find_class(self.ctx._h, _harr(s), len(s), self.class_set(cls), C.byref(out))
+        if rc == -4:
+            raise OverflowError(self.ctx._L.fhs_last_error(self.ctx._h).decode())
+        self.ctx._check(rc)
+        return FheAsciiChar(self, out.value)
+
+    def find_class_wide(self, string, cls):
+        s = self._chars(string)
+        return self._wide("fhs_str_find_class_wide", _harr(s), len(s), self.class_set(cls))
+
+    def count_class(self, string, cls):
+        """The number of characters in the class, 16 bits wide: class_flags + count_flags_wide."""
+        return self.count_flags_wide(self.class_flags(string, cls))
+
+    def all_in_class(self, string, cls):
+        """1 iff every character of the text is in the class: the NUL padding counts as a member."""
+        bits = bytearray(self.class_set(cls))
+        bits[0] |= 1
+        return self.flags_and(self.class_flags(string, bytes(i for i in range(256) if bits[i >> 3] >> (i & 7) & 1)))
+
+    @staticmethod
+    def user_lut(values):
+        """fhs_user_lut: registers a 16-entry table (values below 32) process-wide and returns its id."""
+        values = bytes(values)
+        if len(values) != 16:
+            raise ValueError("a user table has 16 entries")
+        out = C.c_int()
+        rc = lib().fhs_user_lut(values, C.byref(out))
+        if rc == -4:
+            raise OverflowError("the registry of user look-up tables is full")
+        if rc:
+            raise _coded(FhsError("fhs_user_lut: a value above 31"), rc)
+        return out.value
+
     # ---- encrypted positions as operands (the reference only decrypts them; DESIGN.md section 19) ----
     # `pos` is an FheAsciiChar (find, rfind, len), an FheU16 (their _wide forms) or a Python int.  The buffer is taken as
     # it is, NULs included; a position past its end -- an absent one among them -- selects nothing.  An int is plain

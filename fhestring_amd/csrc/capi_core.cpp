@@ -228,9 +228,27 @@ int fhs_debug_live_resources(uint64_t out[5]) {
 }
 
 int fhs_debug_lut_poly(int lut_id, uint64_t *out) {
-    if (!out || lut_id < 0 || lut_id >= fhs::LUT_COUNT) return FHS_ERR_ARG;
+    if (!out || lut_id < 0 || (lut_id >= fhs::LUT_COUNT && !fhs::user_lut_values(lut_id))) return FHS_ERR_ARG;
     fhs::make_lut_poly(lut_id, out);
     return FHS_OK;
+}
+
+// ---- user tables ----
+int fhs_user_lut(const uint8_t values[16], int *lut_id) {
+    if (!values || !lut_id) return FHS_ERR_ARG;
+    for (int i = 0; i < 16; i++)
+        if (values[i] > 31) return FHS_ERR_ARG;
+    const int id = fhs::user_lut_register(values);
+    if (id < 0) return FHS_ERR_LIMIT;
+    *lut_id = id;
+    return FHS_OK;
+}
+int fhs_user_lut_count(void) { return fhs::user_lut_count(); }
+int fhs_lut_catalogue_count(void) { return fhs::LUT_COUNT; }
+int fhs_debug_read_lut(fhs_ctx *ctx, int lut_id, uint64_t *out) {
+    if (!ctx) return FHS_ERR_ARG;
+    if (!out) return ctx->eng.ctx.fail(FHS_ERR_ARG, "invalid handle or null argument");
+    return ctx->eng.read_lut(lut_id, out);
 }
 
 int fhs_debug_capture_read(fhs_ctx *ctx, uint64_t *rows, fhs_capture_rec *recs, size_t cap, size_t *n) {

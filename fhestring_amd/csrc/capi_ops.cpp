@@ -624,6 +624,47 @@ STR_MAP_OP(fhs_str_trim_start, trim_start)
 STR_MAP_OP(fhs_str_trim, trim)
 STR_MAP_OP(fhs_bubble_zeroes_right, bubble_zeroes_right)
 
+// ---- clear tables and sets ----
+namespace {
+// the plan first: it reads no operand, so a full registry fails before a noisy operand is refreshed
+int class_op(fhs_ctx *c, const fhs_char_t *s, size_t n, const uint8_t *set32, fhs_char_t *flags, fhs_char_t *lo, fhs_char_t *hi) {
+    const size_t halves = hi ? 2 : 1;
+    if (lo && n > ((size_t)1 << (8 * halves))) return c->eng.ctx.fail(FHS_ERR_LIMIT, Strings::LIMIT_MSG);
+    Strings S(&c->eng);
+    Strings::TablePlan plan;
+    if (!S.plan_class(set32, &plan)) return finish(c, S);
+    const FStr text = load_str(c->eng, s, n);
+    if (!lo) {
+        FStr r = S.class_flags(text, plan);
+        store_str(c->eng, r, flags);
+        return FHS_OK;
+    }
+    Pos r = S.find_class(text, plan, halves);
+    return store_pos(c, S, r, lo, hi);
+}
+}  // namespace
+int fhs_str_map_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const uint8_t *table, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !table || (n && !out)) return bad(c);
+    Strings S(&c->eng);
+    Strings::TablePlan plan;
+    if (!S.plan_map(table, &plan)) return finish(c, S);
+    FStr r = S.map_clear(load_str(c->eng, s, n), plan);
+    store_str(c->eng, r, out);
+    return FHS_OK;
+}
+int fhs_str_class_flags(fhs_ctx *c, const fhs_char_t *s, size_t n, const uint8_t *set32, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !set32 || (n && !out)) return bad(c);
+    return class_op(c, s, n, set32, out, nullptr, nullptr);
+}
+int fhs_str_find_class(fhs_ctx *c, const fhs_char_t *s, size_t n, const uint8_t *set32, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || !set32 || !out) return bad(c);
+    return class_op(c, s, n, set32, nullptr, out, nullptr);
+}
+int fhs_str_find_class_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const uint8_t *set32, fhs_char_t *lo, fhs_char_t *hi) {
+    if (!ok_all(c, s, n) || !set32 || !lo || !hi) return bad(c);
+    return class_op(c, s, n, set32, nullptr, lo, hi);
+}
+
 size_t fhs_str_replace_len(size_t n, size_t mf, size_t mt) {
     const size_t d = n + 1;                       // the reference pushes one NUL (mod.rs:841,898)
     if (mf >= mt) return d;                       // handle_longer_from

@@ -21,6 +21,59 @@ int Engine::on_key_loaded() {
     return 0;
 }
 
+// The user tables among ids[n] that this context has not used yet get the next slots of the device array and are expanded
+// there on the context's stream (expand_user_luts_kernel: only the 16-byte descriptors cross the bus), in front of the
+// launch group that names them.  An array that has to grow waits for the stream first -- queued launch groups read the
+// old one -- and takes its contents along; it doubles, so a context pays that wait a handful of times in its life.
+int Engine::ensure_luts(const uint32_t *ids, size_t n) {
+    std::vector<uint32_t> fresh;
+    for (size_t k = 0; k < n; k++)
+        if (ids[k] >= LUT_COUNT && !lut_slot_.count(ids[k]) && std::find(fresh.begin(), fresh.end(), ids[k]) == fresh.end())
+            fresh.push_back(ids[k]);
+    if (fresh.empty()) return 0;
+    std::vector<uint8_t> desc(fresh.size() * 16);
+    for (size_t k = 0; k < fresh.size(); k++) {
+        const uint8_t *v = user_lut_values((int)fresh[k]);
+        if (!v) return ctx.fail(-1, "look-up table id " + std::to_string(fresh[k]) + " is not registered");
+        std::memcpy(&desc[16 * k], v, 16);
+    }
+    if (hipSetDevice(ctx.device) != hipSuccess) return ctx.fail(-2, "hipSetDevice failed");
+    if (!d_luts_) return ctx.fail(-3, "server key not loaded");
+    const size_t need = lut_slots_ + fresh.size();
+    if (need > lut_cap_) {
+        const size_t cap = std::max({need, 2 * lut_cap_, (size_t)LUT_COUNT + 64});
+        DevBuf grown;
+        hipError_t e = hipStreamSynchronize(ctx.stream);
+        if (e == hipSuccess) e = grown.reserve_exact(cap * POLY_N * 8);
+        if (e == hipSuccess) e = hipMemcpy(grown.ptr, d_luts_.ptr, lut_slots_ * POLY_N * 8, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) return ctx.hip_fail(e, "growing the look-up table array");
+        d_luts_ = std::move(grown);
+        lut_cap_ = cap;
+    }
+    hipError_t e = launch_expand_user_luts(reinterpret_cast<const uint8_t(*)[16]>(desc.data()), (int)fresh.size(),
+                                           d_luts_.as<uint64_t>() + lut_slots_ * POLY_N, ctx.stream);
+    if (e != hipSuccess) return ctx.hip_fail(e, "user table expansion launch");
+    for (uint32_t id : fresh) lut_slot_[id] = (uint32_t)lut_slots_++;
+    return 0;
+}
+int Engine::ensure_luts(const TickLevel *levels, size_t n_levels) {
+    for (size_t j = 0; j < n_levels; j++)
+        if (int rc = ensure_luts(levels[j].lut.data(), levels[j].lut.size())) return rc;
+    return 0;
+}
+
+int Engine::read_lut(int lut_id, uint64_t *host_out) {
+    if (planner) return ctx.fail(-3, "a planner context has no device tables");
+    if (lut_id < 0 || (lut_id >= LUT_COUNT && !user_lut_values(lut_id))) return ctx.fail(-1, "unknown look-up table id");
+    const uint32_t id = (uint32_t)lut_id;
+    if (int rc = ensure_luts(&id, 1)) return rc;
+    if (!d_luts_) return ctx.fail(-3, "server key not loaded");
+    hipError_t e = hipStreamSynchronize(ctx.stream);
+    if (e == hipSuccess)
+        e = hipMemcpy(host_out, d_luts_.as<uint64_t>() + (size_t)lut_slot(id) * POLY_N, POLY_N * 8, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? 0 : ctx.hip_fail(e, "table download");
+}
+
 Engine::~Engine() {
     if (!planner && ctx.stream) (void)hipStreamSynchronize(ctx.stream);
 }
@@ -845,7 +898,7 @@ Engine::GroupView Engine::pack_group(const TickLevel *levels, size_t n_levels, s
             LinDesc d = l.descs[k];
             d.first_term += (uint32_t)ti;
             hd[di + k] = d;
-            hl[di + k] = l.lut[k];
+            hl[di + k] = lut_slot(l.lut[k]);                  // (ensure_luts has run: upload_group)
             ho[di + k] = l.out[k];
             if (v.n_ext) hb[di + k] = k < l.body.size() ? l.body[k] : nullptr;
         }
@@ -874,6 +927,7 @@ int Engine::ensure_group_buffers(size_t width, size_t bytes) {
 // packs the group, makes room and uploads it: stream-ordered after the previous group's kernels, which read the old
 // contents; pinned staging, so the host goes on
 int Engine::upload_group(const TickLevel *levels, size_t n_levels, GroupView &v) {
+    if (int rc = ensure_luts(levels, n_levels)) return rc;
     std::vector<uint8_t> host;
     v = pack_group(levels, n_levels, host);
     if (int rc = ensure_group_buffers(v.width, v.total)) return rc;

@@ -153,6 +153,9 @@ class Engine {
     int exec_level(size_t k, size_t lo, size_t hi, uint64_t *dense_out);
     int commit_level(size_t k, const uint64_t *d_all);
     int read_block(Bid b, uint64_t *host_out);        // flushes if needed
+    // diagnostic (fhs_debug_read_lut): the device copy of a table's polynomial [2048]; a user table that this context has
+    // not used yet is expanded first
+    int read_lut(int lut_id, uint64_t *host_out);
     // `count` blocks into consecutive 2049-word rows on the host: one gather launch and one copy through the pinned staging
     // buffer per 2048 blocks instead of one synchronous copy per block (the twin of from_host_many)
     int read_many(const Bid *b, size_t count, uint64_t *host_out);
@@ -264,7 +267,15 @@ class Engine {
     int plan_upload(size_t count, Bid *out);
     bool send_pass(size_t n, Bid *out, size_t ptr_at, size_t at, size_t words);
 
-    DevBuf d_luts_;                      // LUT table on device (catalogue)
+    // LUT polynomials on the device: the catalogue, then the user tables THIS context has used, in order of first use
+    // (DESIGN.md section 21).  The array grows only behind a drained stream (ensure_luts): a queued launch group reads
+    // the address it was launched with; a scheduled one (sched_, planned_) holds table ids and gets its slots and the
+    // array's address when it is uploaded.
+    DevBuf d_luts_;
+    size_t lut_slots_ = LUT_COUNT, lut_cap_ = LUT_COUNT;      // polynomials written / room
+    std::unordered_map<uint32_t, uint32_t> lut_slot_;         // user table id -> its slot
+    uint32_t lut_slot(uint32_t id) const { return id < LUT_COUNT ? id : lut_slot_.at(id); }
+    int ensure_luts(const uint32_t *ids, size_t n);           // expands the user tables among ids[n] that are not resident
     DevBuf plan_buf_, batch_in_;
 
     // rotation sharing (plan_job): a follower row is a further sample extraction of its leader's blind rotation
@@ -283,6 +294,7 @@ class Engine {
         std::vector<CaptureRec> recs;     // per row, only while capturing
         uint64_t job = 0;                 // rows of one job that land on the same tick share one TickLevel
     };
+    int ensure_luts(const TickLevel *levels, size_t n_levels);
     std::vector<TickLevel> planned_;      // plan_flush: whole levels waiting for exec_level / commit_level
     size_t planned_max_width_ = 0;
     std::map<uint64_t, std::vector<TickLevel>> sched_;            // tick -> job levels to run in that launch group

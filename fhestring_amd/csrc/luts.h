@@ -51,6 +51,16 @@ enum LutId : uint16_t {
     LUT_COUNT
 };
 
+// ---- user tables ----
+// 16-entry tables registered at run time (fhs_user_lut): process-wide, interned by content, ids LUT_COUNT, LUT_COUNT + 1,
+// ... in order of first registration.  BlockNode::lut is 16 bits wide: the capacity is what keeps every id below 2^16.
+// (A random 256-entry table factors into ~64 tables of its own, so a few thousand would not last a test run.  The host
+// registry is 16 bytes per table; a context's device array holds only the tables that context has used.)
+constexpr int USER_LUT_CAPACITY = 65536 - LUT_COUNT;
+int user_lut_register(const uint8_t values[16]);   // the id, or -1: the registry is full (nothing is recorded)
+int user_lut_count();
+const uint8_t *user_lut_values(int id);             // the 16 values (each < 32) of a registered id, nullptr otherwise
+
 inline int sel_sign(int v) {   // v = 4*s_hi + s_lo, s in {0:lt, 1:eq, 2:gt}; most significant decides
     const int hi = v >> 2, lo = v & 3;
     return hi != 1 ? hi : lo;
@@ -58,6 +68,10 @@ inline int sel_sign(int v) {   // v = 4*s_hi + s_lo, s in {0:lt, 1:eq, 2:gt}; mo
 
 // plaintext function of a LUT on v in [0,16); result is a block value (mod 32)
 inline int lut_function(int id, int v) {
+    if (id >= LUT_COUNT) {
+        const uint8_t *u = user_lut_values(id);
+        return u ? u[v & 15] : 0;
+    }
     switch (id) {
         case LUT_EQ_BIV: return (v >> 2) == (v & 3);
         case LUT_NE_BIV: return (v >> 2) != (v & 3);

@@ -139,6 +139,11 @@ hipError_t launch_gather_rows(const uint64_t *const *d_src, uint64_t *d_out, int
 // of rows are disjoint
 constexpr int POOL_ROW_WORDS = BIG_CT + 1;
 hipError_t launch_pool_move_blocks(const uint64_t *const *d_src, uint64_t *const *d_dst, int n, hipStream_t s);
+// util_kernels.hip: the body polynomials [n][2048] of n user tables (16 values below 32 each) -> d_dst, which has room
+// for n polynomials; the descriptors travel as kernel arguments, USER_LUT_BATCH tables per launch
+constexpr int USER_LUT_BATCH = 16;
+struct UserLutBatch { uint64_t desc[USER_LUT_BATCH][2]; };   // value x of table g: byte x & 7 of desc[g][x >> 3]
+hipError_t launch_expand_user_luts(const uint8_t (*desc)[16], int n, uint64_t *d_dst, hipStream_t s);
 // Rotation sharing: one more sample extraction of a finished blind rotation.  `lead` = the output LWE of that rotation
 // (its mask IS the accumulator's mask polynomial in extract-at-0 order), `body` = the accumulator's body polynomial
 // (body_ptrs of the blind-rotation kernels), K in [0, 4096) = negacyclic coefficient index to extract: out = what a

@@ -52,6 +52,31 @@ class Strings {
     // -1 otherwise
     static int like_trivial(const std::vector<LikeTok> &pat, size_t n);
     FChar like(const FStr &s, const std::vector<LikeTok> &pat, bool ignore_case);
+    // A clear 256-entry table or a 256-bit set applied to every character of a buffer, NULs included (DESIGN.md section
+    // 21).  The plan is made first and touches no operand: fused, it factors every output digit into user tables of the
+    // engine (luts.h) and registers them; false with err = FHS_ERR_LIMIT when the registry is full.
+    struct DigitPlan {
+        enum Kind : uint8_t { PASS, CONST, ONE_LO, ONE_HI, PICK, LINES } kind = PASS;
+        bool delta = false;                  // the construction gives out - in (mod 32), not out
+        int konst = 0;                       // CONST
+        int lut = 0;                         // ONE_LO / ONE_HI: the table; PICK: the pick table
+        int lut_hi = 0, lut_lo = 0;          // PICK: the class of the high / low nibble ...
+        int mul_hi = 1, mul_lo = 1;          // ... and their weights in the pick's index
+        bool by_columns = false;             // LINES: flags of the low nibble, lines over the high one
+        std::vector<std::pair<int, int>> lines;   // LINES: (flag table, line table) per distinct non-zero line
+        int cost() const { return kind == PICK ? 3 : (kind == ONE_LO || kind == ONE_HI ? 1 : (kind == LINES ? 3 * (int)lines.size() : 0)); }
+    };
+    struct TablePlan {
+        uint8_t table[256];                  // map: the table; class: 0/1 membership
+        bool is_class = false;
+        DigitPlan digit[4];                  // fused; a class uses digit[0]
+    };
+    bool plan_map(const uint8_t table[256], TablePlan *out);
+    bool plan_class(const uint8_t set32[32], TablePlan *out);
+    FStr map_clear(const FStr &s, const TablePlan &plan);                 // out[i] = table[s[i]]
+    FStr class_flags(const FStr &s, const TablePlan &plan);               // 0/1 flag chars: s[i] in the set
+    // index of the first character in the set, absent as find's; at most 256 (65536) characters
+    Pos find_class(const FStr &s, const TablePlan &plan, size_t halves = 1);
     FChar eq(const FStr &a, const FStr &b);
     FChar ne(const FStr &a, const FStr &b);
     FChar eq_ignore_case(const FStr &a, const FStr &b);
@@ -144,6 +169,13 @@ class Strings {
     FChar f_comparison(const FStr &a, const FStr &b, int cmp);
     FStr f_case(const FStr &s, bool to_lower);
     FStr f_trim(const FStr &s, bool from_end);
+
+    // ---- clear tables and sets ----
+    bool plan_matrix(const uint8_t m[16][16], bool allow_lines, bool dry, DigitPlan *out);
+    int user_table(const uint8_t values[16]);                          // registers; -1 and err when the registry is full
+    void nibbles(FChar &c, Ref *lo, Ref *hi);                          // b0 + 4 b1, b2 + 4 b3; refreshes c where it must
+    Ref apply_digit(const DigitPlan &p, const Ref &lo, const Ref &hi);
+    std::vector<Ref> f_class_flags(const FStr &s, const TablePlan &plan);
 
     // ---- replace ----
     FStr longer_from(const FStr &s, const FStr &from, FStr to, const FChar &n, bool use_counter);

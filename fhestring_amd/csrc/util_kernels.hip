@@ -50,4 +50,37 @@ hipError_t launch_pool_move_blocks(const uint64_t *const *d_src, uint64_t *const
     return hipGetLastError();
 }
 
+// User tables (fhs_user_lut): workgroup g writes the body polynomial of descriptor g -- what
+// make_lut_poly (luts.h) computes on the host -- to dst + g * 2048.  Only the 16-byte descriptors travel, as kernel
+// arguments; value x of a table is byte x of its descriptor.  Word i of the polynomial lies in box ((i + 64) / 128) mod 16
+// (16 boxes of 128, rotated left by half a box) and the 64 words that wrapped round are negated.  A lane writes four
+// 16-byte pieces (global_store_dwordx4, 1 KiB contiguous per wavefront instruction); the two words of a piece share
+// their box because the rotation is even.  No load, no LDS.
+static_assert(POLY_N == 2048 && POLY_N == 4 * 256 * 2, "four 16-byte pieces per lane");
+__global__ __launch_bounds__(256) void expand_user_luts_kernel(UserLutBatch batch, uint64_t *__restrict__ dst) {
+    typedef uint64_t piece_t __attribute__((ext_vector_type(2)));
+    const uint64_t lo = batch.desc[blockIdx.x][0], hi = batch.desc[blockIdx.x][1];
+    piece_t *o = reinterpret_cast<piece_t *>(dst + (size_t)blockIdx.x * POLY_N);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int p = j * 256 + threadIdx.x;                  // piece p = words 2p, 2p + 1
+        const int q = 2 * p + POLY_N / 32;                    // ... of the unrotated polynomial, before the wrap
+        const int box = (q >> 7) & 15;
+        uint64_t v = (((box < 8 ? lo : hi) >> (8 * (box & 7))) & 31) << 59;
+        if (q >= POLY_N) v = (uint64_t)0 - v;
+        o[p] = piece_t{v, v};
+    }
+}
+hipError_t launch_expand_user_luts(const uint8_t (*desc)[16], int n, uint64_t *d_dst, hipStream_t s) {
+    for (int at = 0; at < n; at += USER_LUT_BATCH) {
+        const int cnt = n - at < USER_LUT_BATCH ? n - at : USER_LUT_BATCH;
+        UserLutBatch b{};
+        for (int g = 0; g < cnt; g++)
+            for (int x = 0; x < 16; x++) b.desc[g][x >> 3] |= (uint64_t)(desc[at + g][x] & 31) << (8 * (x & 7));
+        hipLaunchKernelGGL(expand_user_luts_kernel, dim3(cnt), dim3(256), 0, s, b, d_dst + (size_t)at * POLY_N);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
+}
+
 }  // namespace fhs

@@ -332,6 +332,35 @@ int fhs_str_split_at_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t 
 int fhs_str_like_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, int escape /* -1: none, else 1..255 */,
                        uint32_t flags, fhs_char_t *out);
 
+/* ---- user look-up tables; clear tables and sets on strings -----------------------------
+ * fhs_user_lut registers a 16-entry table f(v), v in [0, 16), values block values below 32, and returns its id in
+ * *lut_id.  The registry is process-wide and interned by content: equal tables get the same id, ids count up from the
+ * end of the built-in catalogue in order of first registration, and every context (planner contexts included) folds,
+ * records and bootstraps with them like with a catalogue table.  A context expands the tables it uses on its GPU, next to
+ * the catalogue, in front of the first launch group that names them; only the 16 bytes cross the bus.  Capacity:
+ * 65536 minus the catalogue's size (table ids are 16 bits wide); past it FHS_ERR_LIMIT, and nothing is recorded.
+ * FHS_ERR_ARG: a null pointer or a value above 31.  fhs_user_lut_count: tables registered so far;
+ * fhs_lut_catalogue_count: the size of the built-in catalogue, the first user id. */
+int fhs_user_lut(const uint8_t *values /*[16]*/, int *lut_id);
+int fhs_user_lut_count(void);
+int fhs_lut_catalogue_count(void);
+/* diagnostic: the device copy of the polynomial [2048] of a catalogue or user table, what fhs_debug_lut_poly computes on
+ * the host; a user table this context has not used yet is expanded first.  FHS_ERR_STATE on a planner context or
+ * without a server key, FHS_ERR_ARG for an unknown id. */
+int fhs_debug_read_lut(fhs_ctx *ctx, int lut_id, uint64_t *out /*[2048]*/);
+/* A clear table or set applied to each of the n buffer characters as it is, NULs included; both modes.
+ * map_clear: out[i] = table[s[i]], table[256].  class_flags: out[i] = the 0/1 flag char of "s[i] is in the set", set32 a
+ * bitmap of 256 bits (byte x >> 3, bit x & 7).  find_class: the index of the first character in the set, as find
+ * returns it (FHS_MAX_FIND_LENGTH / FHS_WIDE_ABSENT if there is none; an index equal to that value reads the same);
+ * FHS_ERR_LIMIT above 256 (65536) characters, before anything is recorded.  Fused mode factors the table into user
+ * tables: nothing for a digit that does not change, at most three bootstraps per digit in two levels where its 16 x 16
+ * matrix over the nibbles has few distinct rows or columns, at most 192 per character otherwise; FHS_ERR_LIMIT when the
+ * registry is full, before anything is recorded. */
+int fhs_str_map_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const uint8_t *table /*[256]*/, fhs_char_t *out /*[n]*/);
+int fhs_str_class_flags(fhs_ctx *c, const fhs_char_t *s, size_t n, const uint8_t *set32 /*[32]*/, fhs_char_t *out /*[n]*/);
+int fhs_str_find_class(fhs_ctx *c, const fhs_char_t *s, size_t n, const uint8_t *set32 /*[32]*/, fhs_char_t *out);
+int fhs_str_find_class_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const uint8_t *set32 /*[32]*/, fhs_char_t *lo, fhs_char_t *hi);
+
 /* ---- multi-GPU inside the library (one process per GPU, RCCL over xGMI) ---------------------------------
  * north_star: "characters of an FheString are independent PBS batches, so long strings shard across the GPUs of one
  * node with an RCCL gather".  fhs_dist_init creates this context's communicator (librccl.so.1 is loaded at run time;
@@ -435,7 +464,7 @@ int fhs_debug_capture_read(fhs_ctx *ctx, uint64_t *rows, fhs_capture_rec *recs, 
  * A host executor replays the list with any bootstrap implementation: the CPU oracle runs the product's fused DAGs on
  * real ciphertexts this way (oracle/plan_exec.py).  fhs_debug_char_terms describes a result handle after the flush, per
  * block: kind (0 plaintext, 1 block, 2 linear combination), value or konst, n, (token coef) x n.  fhs_debug_lut_poly:
- * the catalogue's body polynomial [2048] of a LUT id (csrc/luts.h). */
+ * the body polynomial [2048] of a LUT id (csrc/luts.h), of the catalogue or a registered user table (fhs_user_lut). */
 int fhs_debug_plan_trace(fhs_ctx *ctx, int on);
 int fhs_debug_plan_read(fhs_ctx *ctx, uint64_t *out, size_t cap, size_t *n);
 int fhs_debug_char_terms(fhs_ctx *ctx, fhs_char_t h, uint64_t *out, size_t cap, size_t *n);

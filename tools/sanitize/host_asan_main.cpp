@@ -470,6 +470,51 @@ int main() {
         CHECK(fhs_str_contains_clear(d, up.data(), up.size(), "ab", 2, &r) == FHS_OK && fhs_submit(d) == FHS_OK);
         fhs_ctx_destroy(d);
     }
+    {   // user tables and the clear maps built on them: registry, the digit plans, both modes
+        fhs_ctx *d = nullptr;
+        CHECK(fhs_ctx_create_planner(&d) == FHS_OK && fhs_set_mode(d, 1) == FHS_OK);
+        uint8_t values[16], table[256], set32[32] = {0};
+        for (int v = 0; v < 16; v++) values[v] = (uint8_t)((v * 11 + 5) & 31);
+        int id = -1, again = -1;
+        const int count0 = fhs_user_lut_count();
+        CHECK(fhs_user_lut(values, &id) == FHS_OK && id >= fhs_lut_catalogue_count() && fhs_user_lut(values, &again) == FHS_OK &&
+              again == id && fhs_user_lut_count() == count0 + 1);
+        values[7] = 32;
+        CHECK(fhs_user_lut(values, &again) == FHS_ERR_ARG && fhs_user_lut(nullptr, &again) == FHS_ERR_ARG);
+        std::vector<uint64_t> poly(2048);
+        CHECK(fhs_debug_lut_poly(id, poly.data()) == FHS_OK && poly[0] == ((uint64_t)5 << 59) && poly[2047] == (uint64_t)0 - ((uint64_t)5 << 59));
+        CHECK(fhs_debug_lut_poly(fhs_lut_catalogue_count() + fhs_user_lut_count(), poly.data()) == FHS_ERR_ARG);
+        CHECK(fhs_debug_read_lut(d, id, poly.data()) == FHS_ERR_STATE);
+        auto s = dummy(d, 9);
+        std::vector<fhs_char_t> out(s.size());
+        fhs_char_t pos = 0, lo = 0, hi = 0;
+        for (int kind = 0; kind < 4; kind++) {               // a case fold, a permutation, every byte anywhere, few rows
+            for (int v = 0; v < 256; v++)
+                table[v] = (uint8_t)(kind == 0 ? (v >= 'a' && v <= 'z' ? v - 32 : v) : kind == 1 ? (v * 7 + 3) & 255
+                                   : kind == 2 ? (v * v * 31 + v / 3) & 255 : ((v >> 6) * 4 + (v & 3)) * 17);
+            CHECK(fhs_str_map_clear(d, s.data(), s.size(), table, out.data()) == FHS_OK);
+            for (fhs_char_t h : out) CHECK(fhs_release(d, h) == FHS_OK);
+        }
+        for (int v = 0; v < 256; v++)
+            if ((v * 37 + (v >> 3)) % 5 < 2) set32[v >> 3] |= (uint8_t)(1 << (v & 7));
+        CHECK(fhs_str_class_flags(d, s.data(), s.size(), set32, out.data()) == FHS_OK);
+        CHECK(fhs_str_find_class(d, s.data(), s.size(), set32, &pos) == FHS_OK);
+        CHECK(fhs_str_find_class_wide(d, s.data(), s.size(), set32, &lo, &hi) == FHS_OK && fhs_flush(d) == FHS_OK);
+        CHECK(fhs_str_map_clear(d, s.data(), s.size(), nullptr, out.data()) == FHS_ERR_ARG);
+        CHECK(fhs_set_mode(d, 0) == FHS_OK);                 // as written: a sparse table and a sparse set on trivial characters
+        for (int v = 0; v < 256; v++) table[v] = (uint8_t)v;
+        table['a'] = 'b';
+        table[0] = '-';
+        std::memset(set32, 0, sizeof set32);
+        set32['b' >> 3] |= (uint8_t)(1 << ('b' & 7));
+        fhs_char_t t2[2] = {fhs_trivial(d, 'a'), fhs_trivial(d, 0)}, m2[2], f2[2];
+        int triv = 0;
+        uint8_t val = 0;
+        CHECK(fhs_str_map_clear(d, t2, 2, table, m2) == FHS_OK && fhs_trivial_value(d, m2[1], &triv, &val) == FHS_OK && triv && val == '-');
+        CHECK(fhs_str_class_flags(d, m2, 2, set32, f2) == FHS_OK && fhs_trivial_value(d, f2[0], &triv, &val) == FHS_OK && triv && val == 1);
+        CHECK(fhs_str_find_class(d, m2, 2, set32, &pos) == FHS_OK && fhs_trivial_value(d, pos, &triv, &val) == FHS_OK && triv && val == 0);
+        fhs_ctx_destroy(d);
+    }
     {   // no device here: creation fails, the half-built object carries the error text and is destroyed like any other
         fhs_ctx *d = nullptr;
         CHECK(fhs_ctx_create(9999, &d) != FHS_OK && d != nullptr && std::strlen(fhs_last_error(d)) > 10);
