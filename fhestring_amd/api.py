@@ -1400,6 +1400,34 @@ class MyServerKey:
                                                        _K["FHS_LIKE_IGNORE_CASE"] if ignore_case else 0, C.byref(out)))
         return FheAsciiChar(self, out.value)
 
+    @staticmethod
+    def _regex_args(pattern, ignore_case, search):
+        data = pattern.encode("ascii") if isinstance(pattern, str) else bytes(pattern)
+        return data, (_K["FHS_REGEX_IGNORE_CASE"] if ignore_case else 0) | (_K["FHS_REGEX_SEARCH"] if search else 0)
+
+    def regex_clear(self, string, pattern, ignore_case=False, search=False):
+        """A regular expression against a clear pattern (fhs_str_regex_clear): the 0/1 flag char of
+        re.fullmatch(pattern, text, re.S) -- re.search with search=True, re.I as well with ignore_case=True -- on the text
+        up to the buffer's first NUL.  The syntax is a subset of Python's bytes `re` (include/fhestring_hip.h lists it);
+        what is outside it raises FhsError (FHS_ERR_ARG) and records nothing.  pattern: str (ASCII) or bytes."""
+        s = self._chars(string)
+        data, flags = self._regex_args(pattern, ignore_case, search)
+        out = C.c_uint64()
+        self.ctx._check(self.ctx._L.fhs_str_regex_clear(self.ctx._h, _harr(s), len(s), data, len(data), flags, C.byref(out)))
+        return FheAsciiChar(self, out.value)
+
+    @staticmethod
+    def regex_info(pattern, ignore_case=False, search=False):
+        """The parser of regex_clear alone (fhs_regex_info; no context): {"code": 0, "positions": pattern positions after the
+        counted repeats are expanded, "min_len": length of the shortest match}, or for a refused pattern {"code":
+        FHS_ERR_ARG or FHS_ERR_LIMIT, "err_offset": byte offset of what is refused}."""
+        data, flags = MyServerKey._regex_args(pattern, ignore_case, search)
+        pos, low, off = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        rc = lib().fhs_regex_info(data, len(data), flags, C.byref(pos), C.byref(low), C.byref(off))
+        if rc:
+            return {"code": rc, "err_offset": off.value}
+        return {"code": 0, "positions": pos.value, "min_len": low.value}
+
     def starts_with(self, string, pattern, public_parameters=None):      # mod.rs:344
         return self._flag_op("starts_with", string, pattern)
 

@@ -420,6 +420,43 @@ int fhs_str_like_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pa
     *out = store(c->eng, r);
     return FHS_OK;
 }
+// A regular expression against a clear pattern.  As with LIKE the pattern is judged, and what it
+// decides alone is answered, before the string is loaded; the class tables are registered before that too.
+int fhs_regex_info(const char *pat, size_t m, uint32_t flags, size_t *positions, size_t *min_len, size_t *err_offset) {
+    if (positions) *positions = 0;
+    if (min_len) *min_len = 0;
+    if (err_offset) *err_offset = 0;
+    if ((m && !pat) || (flags & ~(uint32_t)(FHS_REGEX_IGNORE_CASE | FHS_REGEX_SEARCH))) return FHS_ERR_ARG;
+    RegexProgram g;
+    const RegexStatus st = regex_compile(pat, m, (flags & FHS_REGEX_IGNORE_CASE) != 0, (flags & FHS_REGEX_SEARCH) != 0, &g,
+                                         err_offset, nullptr);
+    if (st != REGEX_OK) return st == REGEX_LIMIT ? FHS_ERR_LIMIT : FHS_ERR_ARG;
+    if (positions) *positions = g.positions();
+    if (min_len) *min_len = g.min_len;
+    return FHS_OK;
+}
+int fhs_str_regex_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, uint32_t flags, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || (m && !pat) || !out) return bad(c);
+    if (flags & ~(uint32_t)(FHS_REGEX_IGNORE_CASE | FHS_REGEX_SEARCH))
+        return c->eng.ctx.fail(FHS_ERR_ARG, "fhs_str_regex_clear: unknown flag bits");
+    RegexProgram g;
+    const char *why = "";
+    const RegexStatus st = regex_compile(pat, m, (flags & FHS_REGEX_IGNORE_CASE) != 0, (flags & FHS_REGEX_SEARCH) != 0, &g,
+                                         nullptr, &why);
+    if (st != REGEX_OK) return c->eng.ctx.fail(st == REGEX_LIMIT ? FHS_ERR_LIMIT : FHS_ERR_ARG, why);
+    Strings S(&c->eng);
+    const int known = Strings::regex_trivial(g, n);
+    FChar r;
+    if (known >= 0) r = ch_trivial(&c->eng, (uint8_t)known);
+    else {
+        Strings::RegexPlan plan;
+        if (!S.regex_plan(g, &plan)) return finish(c, S);
+        r = S.regex(load_str(c->eng, s, n), g, plan);
+        if (int rc = finish(c, S)) return rc;
+    }
+    *out = store(c->eng, r);
+    return FHS_OK;
+}
 int fhs_str_is_empty(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t *out) {
     if (!ok_all(c, s, n) || !out) return bad(c);
     Strings S(&c->eng);

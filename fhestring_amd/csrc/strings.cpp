@@ -2324,4 +2324,284 @@ FChar Strings::f_like(const FStr &s, const std::vector<LikeTok> &pat, bool ignor
     return ch_flag(e_, or_tree(R));
 }
 
+// ---------------------------------------------------------------------------------------------
+// Regular expressions against a clear pattern.  The reference has no such method; the semantics
+// are re.fullmatch(pat, text, re.S [| re.I]) -- re.search with FHS_REGEX_SEARCH, compiled as .*(?:pat).* -- on text =
+// the buffer up to its first NUL.  No atom matches NUL, so on the buffer the condition is LIKE's: the match starts at 0
+// and ends at j with j == n or s[j] == NUL.  The pattern arrives as its position automaton (regex.h): every edge into a
+// position q reads q's class, so one flag per (position, index) is all the state there is:
+//     act[q][i] = in_q(s[i]) & (OR_{p in pred(q)} act[p][i-1]  |  q in first, i == 0)
+//     result    = OR_j end[j] & OR_{q in last} act[q][j-1]   (+ end[0] if nullable),  end[j] = [s[j] == 0], end[n] = 1
+// ---------------------------------------------------------------------------------------------
+int Strings::regex_trivial(const RegexProgram &g, size_t n) {
+    if (g.min_len > n) return 0;
+    if (n == 0) return 1;                                    // the empty text and a nullable pattern
+    return g.matches_everything() ? 1 : -1;
+}
+
+bool Strings::regex_plan(const RegexProgram &g, RegexPlan *out) {
+    const size_t K = g.classes.size();
+    out->kind.assign(K, RegexPlan::TABLE);
+    out->byte.assign(K, 0);
+    out->both_cases.assign(K, 0);
+    out->table.assign(K, TablePlan());
+    for (size_t k = 0; k < K; k++) {
+        const RegexClass &c = g.classes[k];
+        const int members = c.count();
+        int lowest = 0;
+        while (lowest < 255 && !c.has(lowest)) lowest++;
+        if (members == 0) out->kind[k] = RegexPlan::DEAD;
+        else if (members == 255) out->kind[k] = RegexPlan::ANY;
+        else if (members == 1 || (members == 2 && lowest >= 'A' && lowest <= 'Z' && c.has(lowest | 0x20))) {
+            out->kind[k] = RegexPlan::BYTE;
+            out->byte[k] = (uint8_t)lowest;
+            out->both_cases[k] = members == 2;
+        } else if (!plan_class(c.bits, &out->table[k])) return false;    // (as written: the set only, nothing is registered)
+    }
+    if (!fused()) return true;
+    // Every threshold table regex_step can ask for is registered here, before an operand is loaded, so that a full
+    // registry fails with nothing recorded: a step with k >= 2 of a position's predecessors (an end: of the last
+    // positions) and u class flags, u = 2 nibble flags for a BYTE class of which one may fold away.
+    auto thresholds = [&](int preds, int flags) {
+        for (int k = 2; k <= preds; k++)
+            for (int u = 1; u <= flags; u++) {
+                const int w = k + 1;
+                if (w * u + k > 15) continue;                 // or_tree first, then one predecessor: an is-k table
+                uint8_t values[16];
+                for (int v = 0; v < 16; v++) values[v] = v >= w * u + 1;
+                if (user_table(values) < 0) return false;
+            }
+        return true;
+    };
+    int last = 0;
+    for (size_t q = 0; q < g.positions(); q++) {
+        int preds = 0;
+        for (size_t p = 0; p < g.positions(); p++) preds += (int)((g.pred[q] >> p) & 1);
+        last += (int)((g.last >> q) & 1);
+        if (!thresholds(preds, out->kind[g.cls[q]] == RegexPlan::BYTE ? 2 : 1)) return false;
+    }
+    return thresholds(last, 1);
+}
+
+FChar Strings::regex(const FStr &s, const RegexProgram &g, const RegexPlan &plan) {
+    const int k = regex_trivial(g, s.size());
+    if (k >= 0) return t((uint8_t)k);
+    return fused() ? f_regex(s, g, plan) : regex_as_written(s, g, plan);
+}
+
+// As written: exactly the recurrence above from char operations.  A class is the OR over its runs of consecutive bytes
+// of eq (one byte), ne 0 (every byte), or ge & le; a test of one character against one class is made once.  A flag that
+// is a trivial constant is not sent through a bitand / bitor, which also keeps positions that cannot be reached after
+// i + 1 characters free of charge.
+FChar Strings::regex_as_written(const FStr &s, const RegexProgram &g, const RegexPlan &plan) {
+    const size_t n = s.size(), P = g.positions(), K = g.classes.size();
+    const FChar zero = t(0), one = t(1);
+    auto konst = [&](const FChar &f) {                       // 0 / 1 for a trivial flag, -1 for an encrypted one
+        int v = 0;
+        for (int k = 0; k < 4; k++) {
+            if (!e_->is_triv(f.b[k].id())) return -1;
+            v |= (e_->triv_val(f.b[k].id()) & 3) << (2 * k);
+        }
+        return v;
+    };
+    auto band = [&](const FChar &a, const FChar &b) {
+        const int ka = konst(a), kb = konst(b);
+        if (ka == 0 || kb == 0) return zero;
+        if (ka == 1) return b;
+        if (kb == 1) return a;
+        return ch_bitand(a, b);
+    };
+    auto bor = [&](const FChar &a, const FChar &b) {
+        const int ka = konst(a), kb = konst(b);
+        if (ka == 1 || kb == 1) return one;
+        if (ka == 0) return b;
+        if (kb == 0) return a;
+        return ch_bitor(a, b);
+    };
+    std::vector<std::vector<FChar>> tests(K + 1, std::vector<FChar>(n));   // [class][index]; class K: s[i] == 0
+    std::vector<std::vector<char>> tested(K + 1, std::vector<char>(n, 0));
+    auto test = [&](size_t k, size_t i) {
+        if (tested[k][i]) return tests[k][i];
+        FChar f = zero;
+        if (k == K) f = ch_eq(s[i], zero);
+        else if (plan.kind[k] != RegexPlan::DEAD) {
+            const RegexClass &c = g.classes[k];
+            for (int lo = 1; lo < 256; lo++) {
+                if (!c.has(lo)) continue;
+                int hi = lo;
+                while (hi < 255 && c.has(hi + 1)) hi++;
+                FChar run;
+                if (lo == hi) run = ch_eq(s[i], t((uint8_t)lo));
+                else if (lo == 1 && hi == 255) run = ch_ne(s[i], zero);
+                else if (hi == 255) run = ch_ge(s[i], t((uint8_t)lo));
+                else run = band(ch_ge(s[i], t((uint8_t)lo)), ch_le(s[i], t((uint8_t)hi)));
+                f = bor(f, run);
+                lo = hi;
+            }
+        }
+        tested[k][i] = 1;
+        return tests[k][i] = f;
+    };
+    auto any_of = [&](const std::vector<FChar> &act, uint64_t set) {
+        FChar r = zero;
+        for (size_t p = 0; p < P; p++)
+            if ((set >> p) & 1) r = bor(r, act[p]);
+        return r;
+    };
+    FChar result = !g.nullable ? zero : (n ? test(K, 0) : one);
+    std::vector<FChar> prev(P, zero), cur(P, zero);
+    for (size_t i = 0; i < n; i++) {
+        for (size_t q = 0; q < P; q++) {
+            const FChar before = i == 0 ? (((g.first >> q) & 1) ? one : zero) : any_of(prev, g.pred[q]);
+            cur[q] = konst(before) == 0 ? zero : band(test((size_t)g.cls[q], i), before);
+        }
+        const FChar ended = any_of(cur, g.last);
+        if (konst(ended) != 0) result = bor(result, band(ended, i + 1 == n ? one : test(K, i + 1)));
+        prev.swap(cur);
+    }
+    return result;
+}
+
+// AND of the 0/1 flags `in` (at most two) AND the OR of the 0/1 flags `preds`, in ONE bootstrap where the noise budget
+// and the message space allow: with k predecessors the input is w * sum(in) + sum(preds), w = k + 1, which exceeds
+// w * |in| exactly when every `in` flag and at least one predecessor is set -- a threshold table (a user table; with one
+// predecessor the threshold is the largest value and the catalogue's is-k table does).  More predecessors than that go
+// through or_tree first.  Trivial flags fold.
+Ref Strings::regex_step(std::vector<Ref> in_all, std::vector<Ref> preds_all) {
+    const Ref zero = trivial_block(e_, 0);
+    std::vector<Ref> in, preds;
+    for (const Ref &x : in_all) {
+        if (!e_->is_triv(x.id())) in.push_back(x);
+        else if ((e_->triv_val(x.id()) & 1) == 0) return zero;
+    }
+    bool satisfied = false;
+    for (const Ref &x : preds_all) {
+        if (e_->is_triv(x.id())) { satisfied = satisfied || (e_->triv_val(x.id()) & 1); continue; }
+        bool seen = false;                                   // positions with one class and one history are one block
+        for (const Ref &y : preds) seen = seen || y.id() == x.id();
+        if (!seen) preds.push_back(x);
+    }
+    if (satisfied) preds.clear();
+    else if (preds.empty()) return zero;
+    if (in.empty()) return preds.empty() ? trivial_block(e_, 1) : or_tree(preds);
+    if (preds.empty()) return in.size() == 1 ? in[0] : and_tree(in);
+    for (;;) {
+        const int k = (int)preds.size(), u = (int)in.size(), w = k + 1;
+        std::vector<Term> tt;
+        for (const Ref &x : in) tt.push_back({w, x.id()});
+        for (const Ref &x : preds) tt.push_back({1, x.id()});
+        const Ref d(e_, e_->lin(tt.data(), tt.size(), 0));
+        const int top = w * u + k, threshold = w * u + 1;
+        if (top <= 15 && e_->sum_c2(d.id()) <= FHS_NOISE_BUDGET_SUM_C2) {
+            if (threshold == top) return pbs(d, lut_is_k(top));
+            uint8_t values[16];
+            for (int v = 0; v < 16; v++) values[v] = v >= threshold;
+            const int lut = user_table(values);              // registered by regex_plan: the interned id, cannot fail
+            return lut < 0 ? zero : pbs(d, lut);
+        }
+        if (k > 1) { preds.assign(1, or_tree(preds)); continue; }
+        for (Ref &x : in)                                     // one predecessor and still too much: refresh what is a sum
+            if (e_->sum_c2(x.id()) > 1) x = pbs(x, LUT_NZ);
+        if (e_->sum_c2(preds[0].id()) > 1) preds[0] = pbs(preds[0], LUT_NZ);
+    }
+}
+
+// Fused.  (1) The class tests of all characters stand at the front of the DAG: a class of one byte (or of the two cases
+// of one letter) is the two nibble flags of block_eq_flags -- extractions of the two rotations per character that
+// contains_clear and like_clear run, the other case's high nibble a second extraction summed to the first as in f_like
+// -- every character is the shared nz flag, and any other class is f_class_flags of its TablePlan on the characters where
+// a position of that class is live.  (2) One regex_step per live (q, i).  (3) (q, i) is live iff q can be reached after
+// exactly i + 1 characters and some last position is at most n - i - 1 characters away from q: a literal of length L
+// costs L steps on any n.  (4) The result is the or_tree over the ends: for j < n one regex_step of end[j] = 1 - nz[j]
+// with the last positions live at j - 1, for j == n those flags themselves; nz[j] is made only where an end can fall.
+FChar Strings::f_regex(const FStr &s, const RegexProgram &g, const RegexPlan &plan) {
+    const size_t n = s.size(), P = g.positions(), K = g.classes.size();
+    const Ref one = trivial_block(e_, 1);
+    const size_t FAR = (size_t)-1;
+    std::vector<size_t> dist(P, FAR);                        // characters from q to the nearest last position
+    for (size_t q = 0; q < P; q++)
+        if (((g.last >> q) & 1) && plan.kind[g.cls[q]] != RegexPlan::DEAD) dist[q] = 0;
+    for (size_t round = 0; round < P; round++)
+        for (size_t q = 0; q < P; q++)
+            for (size_t f = 0; f < P; f++)
+                if (((g.follow[q] >> f) & 1) && dist[f] != FAR && plan.kind[g.cls[q]] != RegexPlan::DEAD)
+                    dist[q] = std::min(dist[q], dist[f] + 1);
+    std::vector<uint64_t> live(n, 0);
+    uint64_t reach = g.first;
+    for (size_t i = 0; i < n; i++) {
+        uint64_t next = 0;
+        for (size_t q = 0; q < P; q++)
+            if (((reach >> q) & 1) && dist[q] != FAR && dist[q] <= n - i - 1) {
+                live[i] |= (uint64_t)1 << q;
+                next |= g.follow[q];
+            }
+        reach = next;
+    }
+    std::vector<Ref> nz(n);
+    auto nonzero = [&](size_t i) {
+        if (!nz[i]) nz[i] = char_zero_test(s[i], false);
+        return nz[i];
+    };
+    // (1) class tests: in[k][i] holds one flag, or the two nibble flags of a BYTE class
+    std::vector<std::vector<std::vector<Ref>>> in(K, std::vector<std::vector<Ref>>(n));
+    for (size_t k = 0; k < K; k++) {
+        std::vector<size_t> where;
+        for (size_t i = 0; i < n; i++)
+            for (size_t q = 0; q < P; q++)
+                if (((live[i] >> q) & 1) && (size_t)g.cls[q] == k) { where.push_back(i); break; }
+        if (plan.kind[k] == RegexPlan::TABLE) {
+            FStr sub;
+            for (size_t i : where) sub.push_back(s[i]);
+            const std::vector<Ref> f = f_class_flags(sub, plan.table[k]);
+            for (size_t j = 0; j < where.size(); j++) in[k][where[j]].assign(1, f[j]);
+            continue;
+        }
+        for (size_t i : where) {
+            if (plan.kind[k] == RegexPlan::ANY) { in[k][i].assign(1, nonzero(i)); continue; }
+            std::vector<Ref> a = block_eq_flags(s[i], t(plan.byte[k]));
+            if (plan.both_cases[k]) {                        // the other case: the same low-nibble test, the other row
+                const std::vector<Ref> b = block_eq_flags(s[i], t(plan.byte[k] | 0x20));
+                a[1] = lin(e_, {{1, &a[1]}, {1, &b[1]}});
+            }
+            in[k][i] = a;
+        }
+    }
+    // (2) the steps; positions with the same live predecessors share the OR (the engine finds the same bootstrap again)
+    std::vector<Ref> fin;
+    if (g.nullable) {
+        const Ref z = nonzero(0);                            // n > 0: the empty text is decided by regex_trivial otherwise
+        fin.push_back(lin(e_, {{1, &one}, {-1, &z}}));
+    }
+    std::vector<Ref> prev(P), cur(P);
+    for (size_t i = 0; i < n && !err.code; i++) {
+        std::vector<Ref> ended;
+        for (size_t q = 0; q < P; q++) {
+            cur[q] = Ref();
+            if (!((live[i] >> q) & 1)) continue;
+            std::vector<Ref> preds;
+            if (i == 0) preds.push_back(one);
+            else
+                for (size_t p = 0; p < P; p++)
+                    if (((g.pred[q] >> p) & 1) && prev[p]) preds.push_back(prev[p]);
+            cur[q] = regex_step(in[g.cls[q]][i], preds);
+            if ((g.last >> q) & 1) ended.push_back(cur[q]);
+        }
+        if (!ended.empty()) {                                // (4)
+            if (i + 1 == n) fin.insert(fin.end(), ended.begin(), ended.end());
+            else {
+                bool possible = false;
+                for (const Ref &x : ended) possible = possible || !e_->is_triv(x.id()) || (e_->triv_val(x.id()) & 1);
+                if (possible) {
+                    const Ref z = nonzero(i + 1);
+                    fin.push_back(regex_step({lin(e_, {{1, &one}, {-1, &z}})}, ended));
+                }
+            }
+        }
+        prev.swap(cur);
+    }
+    Ref r = or_tree(fin);
+    if (e_->sum_c2(r.id()) > 1) r = pbs(r, LUT_NZ);          // a lone class flag or 1 - nz: a linear form
+    return ch_flag(e_, r);
+}
+
 }  // namespace fhs

@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "radix.h"
+#include "regex.h"
 
 namespace fhs {
 
@@ -77,6 +78,23 @@ class Strings {
     FStr class_flags(const FStr &s, const TablePlan &plan);               // 0/1 flag chars: s[i] in the set
     // index of the first character in the set, absent as find's; at most 256 (65536) characters
     Pos find_class(const FStr &s, const TablePlan &plan, size_t halves = 1);
+    // A regular expression against a CLEAR pattern (the reference has none): the position automaton
+    // of regex.h evaluated on the characters.  No atom matches NUL; anchored at index 0; ends at j == n or s[j] == NUL, as
+    // LIKE does.  regex_trivial: what the automaton alone decides on n characters -- 0 (the shortest match is longer), 1
+    // (it matches every text, or n == 0 and it is nullable), -1 otherwise.  regex_plan is made first and touches no operand: fused, every class that is
+    // neither one byte (or the two cases of one letter), nor every character, gets the user tables of plan_class, and the
+    // threshold tables the steps can ask for are registered; as written nothing is registered.  false with err =
+    // FHS_ERR_LIMIT when the registry is full.
+    struct RegexPlan {
+        enum Kind : uint8_t { DEAD, ANY, BYTE, TABLE };      // per distinct class; DEAD: the empty set (\0)
+        std::vector<Kind> kind;
+        std::vector<uint8_t> byte;                            // BYTE: the byte, the upper case of a letter pair
+        std::vector<char> both_cases;                         // BYTE: the byte | 0x20 is in the class as well
+        std::vector<TablePlan> table;                         // TABLE (fused)
+    };
+    static int regex_trivial(const RegexProgram &g, size_t n);
+    bool regex_plan(const RegexProgram &g, RegexPlan *out);
+    FChar regex(const FStr &s, const RegexProgram &g, const RegexPlan &plan);
     FChar eq(const FStr &a, const FStr &b);
     FChar ne(const FStr &a, const FStr &b);
     FChar eq_ignore_case(const FStr &a, const FStr &b);
@@ -161,6 +179,9 @@ class Strings {
     FChar f_ends_with(const FStr &s, const FStr &needle, std::vector<Ref> *pick_out);
     FChar like_as_written(const FStr &s, const std::vector<LikeTok> &pat, bool ignore_case);
     FChar f_like(const FStr &s, const std::vector<LikeTok> &pat, bool ignore_case);
+    FChar regex_as_written(const FStr &s, const RegexProgram &g, const RegexPlan &plan);
+    FChar f_regex(const FStr &s, const RegexProgram &g, const RegexPlan &plan);
+    Ref regex_step(std::vector<Ref> in, std::vector<Ref> preds);      // AND of the flags `in` AND (OR of `preds`)
     FChar f_eq(const FStr &a, const FStr &b);
     FChar f_eq_ignore_case(const FStr &a, const FStr &b);
     // lexicographic order as a tree of three-state values s = sign(a - b) in {-1, 0, 1}, most significant first

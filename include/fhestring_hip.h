@@ -332,6 +332,38 @@ int fhs_str_split_at_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t 
 int fhs_str_like_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, int escape /* -1: none, else 1..255 */,
                        uint32_t flags, fhs_char_t *out);
 
+/* ---- regular expressions against a clear pattern ---------------------------------------
+ * With text = the n characters of s up to the first NUL (all of them if there is none), *out is the 0/1 flag char of
+ *   re.fullmatch(pat, text, re.S)                    Python, bytes; re.I as well with FHS_REGEX_IGNORE_CASE
+ *   re.search(pat, text, re.S)                       with FHS_REGEX_SEARCH: the same engine on .*(?:pat).*
+ * No atom ever matches NUL ('.', negated classes and \D \W \S exclude it), so on the buffer the condition is: the match
+ * starts at index 0, uses atoms only, and ends at j with j == n or buf[j] == 0 -- LIKE's end anchor.  n == 0 is allowed.
+ * The syntax is a strict subset of Python's bytes `re`:
+ *   literal bytes, and a backslash in front of any byte that is neither a letter nor a digit;
+ *   \t \n \r \f \v \0 \xHH;   .   \d \w \s \D \W \S (ASCII);
+ *   classes [...] with ranges, a leading ^, the escapes and shorthands above inside;
+ *   groups ( ) and (?: ), both only grouping;   |   and the quantifiers * + ? {m} {m,} {m,n} on an atom or a group.
+ * FHS_REGEX_IGNORE_CASE closes every positive set under the case swap of ASCII letters; a negated class is the
+ * complement of the closed set.  Everything else is FHS_ERR_ARG before anything is recorded: anchors and \b \B \A \Z,
+ * back-references and every other letter or digit escape, look-around, inline flags and named groups, lazy,
+ * possessive and stacked quantifiers, a quantifier with nothing to repeat, a '{' that is not one of the three counted
+ * forms, a NUL byte in pat, unbalanced brackets, an empty class ("[]", "[^]"), an unescaped '[' at the start of a class or a doubled
+ * - & ~ | inside one, a range from or to a shorthand, a reversed range or {m,n}, unknown flag bits, a null out.
+ * Counted repeats are expanded ({m,n}: n copies, {m,}: max(m, 1) copies; FHS_REGEX_SEARCH adds two positions): more than
+ * FHS_REGEX_MAX_POSITIONS pattern positions, more than 1024 written atoms, groups and '|' together, or groups nested deeper than 64, are
+ * FHS_ERR_LIMIT, and nothing is recorded; so is a full registry of user tables in fused mode, whose class and
+ * step tables are registered before the string is loaded (as written none is registered).  A pattern whose shortest match is longer than n gives a trivial 0; one that
+ * matches every text ('.*', a nullable pattern under FHS_REGEX_SEARCH), and a nullable pattern on n == 0, a trivial 1:
+ * all with nothing recorded and no operand loaded.  Both modes; the fused DAG is as deep as the string is long (one level per character).
+ * fhs_regex_info is the parser alone (no context): the number of positions and the length of the shortest match; for a
+ * refused pattern *err_offset is the byte offset of the first byte of what is refused (the bracket that is never closed,
+ * the second quantifier, the backslash of an escape; 0 for a limit).  Any of the three pointers may be null. */
+#define FHS_REGEX_IGNORE_CASE 1
+#define FHS_REGEX_SEARCH 2
+#define FHS_REGEX_MAX_POSITIONS 64
+int fhs_str_regex_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, uint32_t flags, fhs_char_t *out);
+int fhs_regex_info(const char *pat, size_t m, uint32_t flags, size_t *positions, size_t *min_len, size_t *err_offset);
+
 /* ---- user look-up tables; clear tables and sets on strings -----------------------------
  * fhs_user_lut registers a 16-entry table f(v), v in [0, 16), values block values below 32, and returns its id in
  * *lut_id.  The registry is process-wide and interned by content: equal tables get the same id, ids count up from the

@@ -231,6 +231,38 @@ int main() {
         for (size_t i = 0; i < n; i++) v.push_back(i % every == every / 2 ? fhs_upload(c, z.data()) : fhs_trivial(c, (uint8_t)("ab c"[i % 4])));
         return v;
     };
+    {   // the parser of regex_clear alone: valid patterns, malformed ones cut short at every place, the limits
+        size_t positions = 0, low = 0, off = 0;
+        CHECK(fhs_regex_info("(error|warn).*timeout", 21, FHS_REGEX_IGNORE_CASE, &positions, &low, &off) == FHS_OK && positions == 17 && low == 11);
+        CHECK(fhs_regex_info("a{64}", 5, 0, &positions, &low, nullptr) == FHS_OK && positions == 64 && low == 64);
+        CHECK(fhs_regex_info("a{64}", 5, FHS_REGEX_SEARCH, &positions, &low, &off) == FHS_ERR_LIMIT);
+        CHECK(fhs_regex_info(nullptr, 0, FHS_REGEX_SEARCH, &positions, nullptr, nullptr) == FHS_OK && positions == 2);
+        CHECK(fhs_regex_info("(a|b", 4, 0, nullptr, nullptr, &off) == FHS_ERR_ARG && off == 0);
+        CHECK(fhs_regex_info("ab[c-", 5, 0, nullptr, nullptr, &off) == FHS_ERR_ARG && off == 2);
+        CHECK(fhs_regex_info("ab\\", 3, 0, nullptr, nullptr, &off) == FHS_ERR_ARG && off == 2);
+        CHECK(fhs_regex_info("a{1,", 4, 0, nullptr, nullptr, &off) == FHS_ERR_ARG && off == 1);
+        CHECK(fhs_regex_info("a{99999999999999999999}", 23, 0, nullptr, nullptr, nullptr) == FHS_ERR_LIMIT);
+        // long patterns whose trees would be deep: refused by the written-size limit before anything walks them
+        for (const char *unit : {"|", "a", "()", "a|", "(?:)|", "a?"})
+            for (size_t bytes : {(size_t)4096, (size_t)200000}) {
+                std::string big;
+                while (big.size() < bytes) big += unit;
+                CHECK(fhs_regex_info(big.data(), big.size(), FHS_REGEX_SEARCH, &positions, &low, &off) == FHS_ERR_LIMIT && off == 0);
+            }
+        {
+            const std::string nested = std::string(65, '(') + "a" + std::string(65, ')');
+            CHECK(fhs_regex_info(nested.data(), nested.size(), 0, nullptr, nullptr, nullptr) == FHS_ERR_LIMIT);
+            const std::string bars(1000, '|');                           // within the limit: 1001 empty branches
+            CHECK(fhs_regex_info(bars.data(), bars.size(), 0, &positions, &low, nullptr) == FHS_OK && positions == 0 && low == 0);
+        }
+        const char *full = "x(?:a|[^b-d\\x41\\d]){2,3}\\.\\x4a+|(y*)?";
+        for (size_t cut = 0; cut <= std::strlen(full); cut++)            // every prefix: accepted or refused, never read past
+            for (uint32_t fl = 0; fl < 4; fl++) {
+                std::vector<char> exact(full, full + cut);               // (a buffer of exactly `cut` bytes)
+                const int rc = fhs_regex_info(exact.data(), cut, fl, &positions, &low, &off);
+                CHECK(rc == FHS_OK || (rc == FHS_ERR_ARG && off <= cut));
+            }
+    }
     for (int variant = 0; variant < 5; variant++)
     for (int mode = 0; mode < 2; mode++) {
         if (variant >= 3 && mode == 0) continue;                 // long strings: the re-associated DAGs only (as written is O(n^2) nodes)
@@ -250,6 +282,16 @@ int main() {
         CHECK(fhs_str_like_clear(c, s.data(), s.size(), "ab", 2, '%', 0, &r) == FHS_ERR_ARG);
         CHECK(fhs_str_like_clear(c, s.data(), s.size(), "ab", 2, -1, 2, &r) == FHS_ERR_ARG);
         CHECK(fhs_str_like_clear(c, s.data(), s.size(), "ab", 2, -1, 0, nullptr) == FHS_ERR_ARG);
+        // regular expressions: every construct, every flag combination; patterns the parser decides alone; the refused ones
+        for (const char *pat : {"", "ab c", "a.*c", "(ab| c)+a?", "[a-c ]{2,3}.*", "[^b]+", "\\w+\\s\\S*", "(a|b|c| |ab|bc|c a|abc)*", ".*",
+                                "a{0}(b{2,}|[\\x61-\\x63]?)*", "(ab c){3}ab.*", "\\0?a.*"})
+            for (uint32_t fl = 0; fl < 4; fl++)
+                CHECK(fhs_str_regex_clear(c, s.data(), s.size(), pat, std::strlen(pat), fl, &r) == FHS_OK && r);
+        CHECK(fhs_str_regex_clear(c, s.data(), s.size(), "a\0b", 3, 0, &r) == FHS_ERR_ARG);
+        CHECK(fhs_str_regex_clear(c, s.data(), s.size(), "(ab", 3, 0, &r) == FHS_ERR_ARG);
+        CHECK(fhs_str_regex_clear(c, s.data(), s.size(), "a{65}", 5, 0, &r) == FHS_ERR_LIMIT);
+        CHECK(fhs_str_regex_clear(c, s.data(), s.size(), "ab", 2, 4, &r) == FHS_ERR_ARG);
+        CHECK(fhs_str_regex_clear(c, s.data(), s.size(), "ab", 2, 0, nullptr) == FHS_ERR_ARG);
         CHECK(fhs_str_starts_with(c, s.data(), s.size(), p.data(), p.size(), &r) == FHS_OK);
         CHECK(fhs_str_ends_with(c, s.data(), s.size(), p.data(), p.size(), &r) == FHS_OK);
         CHECK(fhs_str_find(c, s.data(), s.size(), p.data(), p.size(), &r) == FHS_OK);
