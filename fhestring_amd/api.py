@@ -208,7 +208,8 @@ class Context:
                 "fft4_ms": narrow[0], "n_fft4": narrow[1], "pbs_in_fft4": narrow[2]}
 
     def kernel_timing_kind(self, kind):
-        """(average ms, launches, PBS) of one kernel class: 0 wide blind rotation, 1 keyswitch, 2 4-wavefront FFT."""
+        """(average ms, launches, PBS) of one kernel class: 0 wide blind rotation, 1 keyswitch, 2 4-wavefront FFT,
+        3 the launches of class 0 that ran the shifted-accumulator instantiation of the 2-wavefront FFT kernel."""
         ms, n, u = C.c_double(), C.c_uint64(), C.c_uint64()
         self._check(self._L.fhs_kernel_timing_kind(self._h, int(kind), C.byref(ms), C.byref(n), C.byref(u)))
         return ms.value, n.value, u.value

@@ -282,7 +282,7 @@ int fhs_kernel_timing(fhs_ctx *ctx, int reset, double *blind_rotate_ms, double *
 }
 
 int fhs_kernel_timing_kind(fhs_ctx *ctx, int kind, double *avg_ms, uint64_t *launches, uint64_t *pbs_in_launches) {
-    if (!ctx || kind < 0 || kind > 2) return FHS_ERR_ARG;
+    if (!ctx || kind < 0 || kind >= fhs::KernelTimer::KINDS) return FHS_ERR_ARG;
     auto &t = ctx->eng.ctx.timer;
     t.resolve();
     if (avg_ms) *avg_ms = t.n[kind] ? t.ms[kind] / (double)t.n[kind] : 0.0;

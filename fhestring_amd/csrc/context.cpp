@@ -27,10 +27,10 @@ Event KernelTimer::get() {
     pool.pop_back();
     return e;
 }
-void KernelTimer::begin(int kind, uint64_t u, hipStream_t s) {
+void KernelTimer::begin(int kind, uint64_t u, hipStream_t s, bool shifted_acc) {
     if (!enabled) return;
     if (pending.size() > 4096) resolve();
-    Pending p{get(), get(), kind, u, 1};
+    Pending p{get(), get(), kind, u, 1, shifted_acc};
     (void)hipEventRecord(p.e0.get(), s);
     pending.push_back(std::move(p));
 }
@@ -44,9 +44,12 @@ void KernelTimer::resolve() {
         (void)hipEventSynchronize(p.e1.peek());
         float t = 0;
         if (hipEventElapsedTime(&t, p.e0.peek(), p.e1.peek()) == hipSuccess) {
-            ms[p.kind] += t;
-            n[p.kind] += p.launches;
-            units[p.kind] += p.units;
+            for (int k : {p.kind, 3}) {
+                ms[k] += t;
+                n[k] += p.launches;
+                units[k] += p.units;
+                if (!p.shifted_acc) break;
+            }
         }
         pool.push_back(std::move(p.e0));
         pool.push_back(std::move(p.e1));
@@ -55,7 +58,7 @@ void KernelTimer::resolve() {
 }
 void KernelTimer::reset() {
     resolve();
-    for (int k = 0; k < 3; k++) { ms[k] = 0; n[k] = 0; units[k] = 0; }
+    for (int k = 0; k < KINDS; k++) { ms[k] = 0; n[k] = 0; units[k] = 0; }
 }
 int Context::hip_fail(hipError_t e, const char *what) {
     err = std::string(what) + ": " + hipGetErrorString(e);
@@ -344,7 +347,13 @@ int Context::load_rekey_key(const uint64_t *key) {
                               prepare_device_for_rekey);
 }
 
-int Context::blind_rotate(const uint64_t *d_ks, const uint32_t *d_lut_idx, const uint64_t *d_luts, uint64_t *d_out,
+bool Context::luts_low_bytes_clear(const uint64_t *luts, size_t n_words) {
+    uint64_t any = 0;
+    for (size_t k = 0; k < n_words; k++) any |= luts[k];
+    return (any & 0xFF) == 0;
+}
+
+int Context::blind_rotate(const uint64_t *d_ks, const uint32_t *d_lut_idx, const uint64_t *d_luts, bool luts_clean, uint64_t *d_out,
                           uint64_t *const *d_out_ptrs, size_t B, hipStream_t s, uint64_t *const *d_body_ptrs) {
     hipError_t e = hipSuccess;
     const bool four = arith == FHS_ARITH_F64_FFT && B <= (size_t)fft4_max_batch;
@@ -352,7 +361,8 @@ int Context::blind_rotate(const uint64_t *d_ks, const uint32_t *d_lut_idx, const
     if (arith == FHS_ARITH_EXACT_NTT_MB2 && !d_bsk_ntt_mb)
         return fail(-3, "pair key not loaded in the exact arithmetic (fhs_load_multibit_key)");
     if (arith == FHS_ARITH_F64_FFT && !d_bsk_fft) return fail(-3, "Fourier-domain key not loaded");
-    timer.begin(four ? 2 : 0, B, s);
+    const bool shifted_acc = arith == FHS_ARITH_F64_FFT && !four && luts_clean;
+    timer.begin(four ? 2 : 0, B, s, shifted_acc);
     // A launch is cut into chunks of launch_chunk[arith] ciphertexts (0 = whole batch): every chunk starts all workgroups on
     // the first key element together again.  The kernels whose key does not fit the L2 window of a drifting launch need
     // that (two-bit f64 kernel: 185 k PBS/s in launches of 3 072 - 4 096 rows, 144 k in one launch of 13 400).
@@ -392,7 +402,7 @@ int Context::blind_rotate(const uint64_t *d_ks, const uint32_t *d_lut_idx, const
             p.work_counter = d_work_counter.as<uint32_t>();
             p.slots = wg_slots;
             p.out = out; p.out_ptrs = outp; p.body_ptrs = bodyp; p.B = (int)n;
-            e = four ? launch_blind_rotate_fft4(p, s) : launch_blind_rotate_fft(p, s);
+            e = four ? launch_blind_rotate_fft4(p, s) : launch_blind_rotate_fft(p, s, shifted_acc);
         } else {
             BlindRotateParams p{};
             p.ks = ks; p.lut_idx = li; p.luts = d_luts;
@@ -407,13 +417,13 @@ int Context::blind_rotate(const uint64_t *d_ks, const uint32_t *d_lut_idx, const
 }
 
 int Context::pbs_batch_device(const uint64_t *d_in, const uint32_t *d_lut_idx, const uint64_t *d_luts,
-                              uint64_t *d_out, size_t B, hipStream_t s) {
+                              uint64_t *d_out, size_t B, hipStream_t s, bool luts_clean) {
     if (!key_loaded) return fail(-3, "server key not loaded");
     if (B == 0) return 0;
     if (B > (size_t)1 << 24) return fail(-1, "batch too large");
     HIP_TRY(ks_buf.reserve(B * SMALL_CT * sizeof(uint64_t)), "hipMalloc ks");
     if (int rc = keyswitch(d_in, B, s)) return rc;
-    if (int rc = blind_rotate(ks_buf.as<uint64_t>(), d_lut_idx, d_luts, d_out, nullptr, B, s)) return rc;
+    if (int rc = blind_rotate(ks_buf.as<uint64_t>(), d_lut_idx, d_luts, luts_clean, d_out, nullptr, B, s)) return rc;
     return 0;
 }
 
@@ -432,7 +442,7 @@ int Context::pbs_batch_host(const uint64_t *in, const uint32_t *lut_idx, const u
     HIP_TRY(hipMemcpyAsync(lutidx_buf.ptr, lut_idx, B * 4, hipMemcpyHostToDevice, stream), "H2D");
     HIP_TRY(hipMemcpyAsync(luts_buf.ptr, luts, n_luts * POLY_N * 8, hipMemcpyHostToDevice, stream), "H2D");
     int rc = pbs_batch_device(in_buf.as<uint64_t>(), lutidx_buf.as<uint32_t>(), luts_buf.as<uint64_t>(),
-                              out_buf.as<uint64_t>(), B, stream);
+                              out_buf.as<uint64_t>(), B, stream, luts_low_bytes_clear(luts, n_luts * POLY_N));
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, out_buf.ptr, B * BIG_CT * 8, hipMemcpyDeviceToHost, stream), "D2H");
     HIP_TRY(hipStreamSynchronize(stream), "sync");
@@ -478,8 +488,8 @@ int Context::pbs_batch_shifted_host(const uint64_t *in, const uint32_t *lut_idx,
     HIP_TRY(hipStreamSynchronize(stream), "sync");                       // the host vectors above are pageable
     if (int rc = keyswitch(in_buf.as<uint64_t>(), B, stream)) return rc;
     uint64_t *const *d_ptrs = tab.as<uint64_t *>();
-    if (int rc = blind_rotate(ks_buf.as<uint64_t>(), lutidx_buf.as<uint32_t>(), luts_buf.as<uint64_t>(), nullptr, d_ptrs, B, stream,
-                              d_ptrs + B))
+    if (int rc = blind_rotate(ks_buf.as<uint64_t>(), lutidx_buf.as<uint32_t>(), luts_buf.as<uint64_t>(),
+                              luts_low_bytes_clear(luts, n_luts * POLY_N), nullptr, d_ptrs, B, stream, d_ptrs + B))
         return rc;
     HIP_TRY(launch_extract_shift(reinterpret_cast<const ExtractDesc *>(tab.as<uint8_t>() + ptrs.size() * sizeof(uint64_t *)),
                                  (int)(B * S), stream), "extract launch");
@@ -506,7 +516,7 @@ int Context::blind_rotate_host(const uint64_t *ks, const uint32_t *lut_idx, cons
     HIP_TRY(hipMemcpyAsync(lutidx_buf.ptr, lut_idx, B * 4, hipMemcpyHostToDevice, stream), "H2D");
     HIP_TRY(hipMemcpyAsync(luts_buf.ptr, luts, n_luts * POLY_N * 8, hipMemcpyHostToDevice, stream), "H2D");
     if (int rc = blind_rotate(ks_buf.as<uint64_t>(), lutidx_buf.as<uint32_t>(), luts_buf.as<uint64_t>(),
-                              out_buf.as<uint64_t>(), nullptr, B, stream))
+                              luts_low_bytes_clear(luts, n_luts * POLY_N), out_buf.as<uint64_t>(), nullptr, B, stream))
         return rc;
     HIP_TRY(hipMemcpyAsync(out, out_buf.ptr, B * BIG_CT * 8, hipMemcpyDeviceToHost, stream), "D2H");
     HIP_TRY(hipStreamSynchronize(stream), "sync");

@@ -29,18 +29,20 @@ struct FftTablePtrs {
 
 // HIP-event timing of the two PBS kernels on the stream they are launched on
 struct KernelTimer {
-    struct Pending { Event e0, e1; int kind; uint64_t units; uint32_t launches; };
+    struct Pending { Event e0, e1; int kind; uint64_t units; uint32_t launches; bool shifted_acc; };
     std::vector<Pending> pending;
     std::vector<Event> pool;         // resolved events wait here for the next launch; they go with the timer
     // 0 = blind rotation (exact NTT kernel, or the 2-wavefront FFT kernel), 1 = keyswitch,
-    // 2 = blind rotation on the 4-wavefront FFT kernel (batches <= fft4_max_batch)
-    double ms[3] = {0, 0, 0};
-    uint64_t n[3] = {0, 0, 0};       // KERNEL launches covered (a blind rotation cut into one-round launches counts each of them:
+    // 2 = blind rotation on the 4-wavefront FFT kernel (batches <= fft4_max_batch),
+    // 3 = the part of kind 0 that ran the shifted-accumulator instantiation of the 2-wavefront FFT kernel (counted twice)
+    static constexpr int KINDS = 4;
+    double ms[KINDS] = {};
+    uint64_t n[KINDS] = {};          // KERNEL launches covered (a blind rotation cut into one-round launches counts each of them:
                                      // the per-launch average then is what `rocprofv3 --kernel-trace --stats` reports per kernel)
-    uint64_t units[3] = {0, 0, 0};   // PBS covered by the timed launches
+    uint64_t units[KINDS] = {};      // PBS covered by the timed launches
     bool enabled = true;
     Event get();
-    void begin(int kind, uint64_t units, hipStream_t s);
+    void begin(int kind, uint64_t units, hipStream_t s, bool shifted_acc = false);
     void end(hipStream_t s, uint32_t kernel_launches = 1);
     void resolve();   // synchronises pending events and accumulates
     void reset();
@@ -91,8 +93,12 @@ class Context {
     // keyswitch of a dense batch into ks_buf (timed as kernel kind 1); ks_buf must hold B rows
     int keyswitch(const uint64_t *d_in, size_t B, hipStream_t s);
     // blind rotation in the selected arithmetic (timed as kernel kind 0)
-    int blind_rotate(const uint64_t *d_ks, const uint32_t *d_lut_idx, const uint64_t *d_luts, uint64_t *d_out,
+    // luts_clean: the low 8 bits of every word of the tables under d_luts are zero (luts_low_bytes_clear, taken when the
+    // tables were uploaded; false where nobody looked, e.g. a caller's device pointer): the 2-wavefront FFT kernel then runs
+    // its shifted-accumulator instantiation, timed as kernel kind 3 beside kind 0
+    int blind_rotate(const uint64_t *d_ks, const uint32_t *d_lut_idx, const uint64_t *d_luts, bool luts_clean, uint64_t *d_out,
                      uint64_t *const *d_out_ptrs, size_t B, hipStream_t s, uint64_t *const *d_body_ptrs = nullptr);
+    static bool luts_low_bytes_clear(const uint64_t *luts, size_t n_words);
 
     // multi-GPU exchange (fhs_dist_init): RCCL communicator of this context, or a host transport
     Dist dist;
@@ -114,9 +120,10 @@ class Context {
     int load_compressed_server_key(const uint32_t seed[8], const uint64_t *bsk_bodies, const uint64_t *ksk_bodies);
     int install_server_key(const uint64_t *bsk, const uint64_t *d_ksk);
     int build_fft_key();
-    // all device pointers; enqueues KS+MS then blind rotation on `s`
+    // all device pointers; enqueues KS+MS then blind rotation on `s`.  luts_clean as for blind_rotate: nobody has looked at
+    // a caller's device tables, so the C entry point leaves it false
     int pbs_batch_device(const uint64_t *d_in, const uint32_t *d_lut_idx, const uint64_t *d_luts,
-                         uint64_t *d_out, size_t B, hipStream_t s);
+                         uint64_t *d_out, size_t B, hipStream_t s, bool luts_clean = false);
     int pbs_batch_shifted_host(const uint64_t *in, const uint32_t *lut_idx, const uint64_t *luts, size_t n_luts,
                                const uint32_t *shifts, size_t S, uint64_t *out, size_t B);
     int pbs_batch_host(const uint64_t *in, const uint32_t *lut_idx, const uint64_t *luts, size_t n_luts,

@@ -13,6 +13,7 @@ int Engine::on_key_loaded() {
     if (!d_luts_) {
         std::vector<uint64_t> host((size_t)LUT_COUNT * POLY_N);
         for (int id = 0; id < LUT_COUNT; id++) make_lut_poly(id, host.data() + (size_t)id * POLY_N);
+        luts_clean_ = Context::luts_low_bytes_clear(host.data(), host.size());
         hipError_t e = d_luts_.reserve_exact(host.size() * 8);
         if (e != hipSuccess) return ctx.hip_fail(e, "hipMalloc luts");
         e = hipMemcpy(d_luts_.ptr, host.data(), host.size() * 8, hipMemcpyHostToDevice);
@@ -976,7 +977,7 @@ int Engine::launch_rows(const GroupView &v, size_t lo, size_t cnt, uint64_t *den
         row0 += w;
     }
     if (int rc = ctx.keyswitch(batch_in_.as<uint64_t>(), cnt, ctx.stream)) return rc;
-    return ctx.blind_rotate(ctx.ks_buf.as<uint64_t>(), d_lut + lo, d_luts_.as<uint64_t>(), dense_out, dense_out ? nullptr : d_out + lo, cnt,
+    return ctx.blind_rotate(ctx.ks_buf.as<uint64_t>(), d_lut + lo, d_luts_.as<uint64_t>(), luts_clean_, dense_out, dense_out ? nullptr : d_out + lo, cnt,
                             ctx.stream, v.n_ext && !dense_out ? d_body + lo : nullptr);
 }
 

@@ -272,6 +272,9 @@ class Engine {
     // the address it was launched with; a scheduled one (sched_, planned_) holds table ids and gets its slots and the
     // array's address when it is uploaded.
     DevBuf d_luts_;
+    // every word of the array has its low 8 bits clear (Context::blind_rotate's luts_clean): taken over the catalogue when it
+    // is uploaded; a user table is 16 values << 59 and their negations (expand_user_luts_kernel) and cannot change it
+    bool luts_clean_ = false;
     size_t lut_slots_ = LUT_COUNT, lut_cap_ = LUT_COUNT;      // polynomials written / room
     std::unordered_map<uint32_t, uint32_t> lut_slot_;         // user table id -> its slot
     uint32_t lut_slot(uint32_t id) const { return id < LUT_COUNT ? id : lut_slot_.at(id); }

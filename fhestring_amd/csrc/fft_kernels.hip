@@ -28,8 +28,56 @@ namespace fhs {
 namespace {
 using namespace fftdev;
 
+// The accumulator of blind_rotate_fft_kernel in its two forms.  General: acc = x - 1 (fft_device.h, rot_sub_hi_compl).
+// SHIFTED: A = (x - 1) >> 8 in the low 56 bits of the word, the top 8 bits carry no meaning.  It needs every look-up table
+// word to be a multiple of 2^8: every increment is a multiple of 2^12, so x stays one and the low byte of x - 1 is 0xFF for
+// the whole loop.  That byte is what the shift drops.  In the rotate-and-subtract it would borrow exactly where the value
+// is not flipped (0xFF - 0xFF - 1) and not where it is (0xFF - 0x00 - 0), which IS the borrow-in rot_sub_hi_compl takes:
+// its five operations are used unchanged and return bits 63..40 of the complemented difference in bits 23..0.  Every operation
+// of the loop lets bit k depend on bits <= k only, so the top byte never reaches a bit that is used.
+template <bool SHIFTED> __device__ __forceinline__ uint64_t acc_from_torus(uint64_t x) {
+    return SHIFTED ? (x - 1) >> 8 : x - 1;
+}
+template <bool SHIFTED> __device__ __forceinline__ uint64_t acc_to_torus(uint64_t a) {
+    return SHIFTED ? (a + 1) << 8 : a + 1;
+}
+// Rotate-and-subtract and the rounded 23-bit digit (hi(x) + 0x100) >> 9 of the difference x.  General: from hi(~x) as
+// fft_device.h has it.  SHIFTED: rot_sub_hi_compl's five operations leave bits 63..40 of ~x in bits 23..0; 0 - n = ~n + 1
+// adds the rounding bit at bit 40, and the signed field 23..1 of that is the digit (same wrap at +-2^22).  One asm block
+// for all seven: the compiler spells the bit-field extract as shift, negate, shift, and it puts a hazard s_nop behind
+// every asm block.
+template <bool SHIFTED> __device__ __forceinline__ int32_t rot_sub_digit(uint64_t vm, uint64_t am, uint64_t keepmask) {
+    if (!SHIFTED) return (int32_t)(0xFFu - rot_sub_hi_compl(vm, am, keepmask)) >> 9;
+    const uint32_t vl = (uint32_t)vm, vh = (uint32_t)(vm >> 32), al = (uint32_t)am, ah = (uint32_t)(am >> 32);
+    uint32_t m, tl;
+    int32_t dig;
+    asm("v_cndmask_b32 %0, -1, 0, %7\n\t"
+        "v_xor_b32 %1, %3, %0\n\t"
+        "v_xor_b32 %2, %4, %0\n\t"
+        "v_subb_co_u32 %1, vcc, %5, %1, %7\n\t"
+        "v_subb_co_u32 %2, vcc, %6, %2, vcc\n\t"
+        "v_sub_u32 %2, 0, %2\n\t"
+        "v_bfe_i32 %2, %2, 1, 23"
+        : "=&v"(m), "=&v"(tl), "=&v"(dig)
+        : "v"(vl), "v"(vh), "v"(al), "v"(ah), "s"(keepmask)
+        : "vcc");
+    (void)m; (void)tl;
+    return dig;
+}
+// acc += fract(t) * 2^64 (to_torus).  SHIFTED: the 52 mantissa bits of 1 + fract(t) go to bits 55..4 in one shift-and-add
+// (v_lshl_add_u64), the exponent bits land in the top byte
+template <bool SHIFTED> __device__ __forceinline__ uint64_t acc_add(uint64_t a, double t) {
+    if (!SHIFTED) return a + to_torus(t);
+    const double g = 1.0 + __builtin_amdgcn_fract(t);
+    return a + (__builtin_bit_cast(uint64_t, g) << 4);
+}
+
 }  // namespace
 
+// SHIFTED = false works for any look-up table; SHIFTED = true (64 fewer VALU instructions per wavefront and iteration)
+// needs tables whose words have their low 8 bits clear -- the catalogue and the user tables are multiples of 2^59.  Same
+// FP64 stream, same LDS, same launch bounds, same bits out.
+template <bool SHIFTED>
 __global__ __launch_bounds__(128, 2) void blind_rotate_fft_kernel(BlindRotateFftParams P) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int lane = threadIdx.x & 63;
@@ -53,7 +101,8 @@ __global__ __launch_bounds__(128, 2) void blind_rotate_fft_kernel(BlindRotateFft
     const uint64_t *ks = P.ks + (size_t)ct * SMALL_CT;
 
     // acc[r] = coefficient (lane + 64 r) of polynomial j (u64 torus) MINUS ONE -- the offset makes the rotate-and-
-    // subtract exact in five operations (rot_sub_hi_compl); registers r and r+16 form one complex point
+    // subtract exact in five operations (rot_sub_hi_compl) --, SHIFTED: and shifted right by 8 (acc_from_torus);
+    // registers r and r+16 form one complex point
     uint64_t acc[32];
     {
         const uint32_t b = fft_mod_switch(ks[LWE_N]);
@@ -69,7 +118,7 @@ __global__ __launch_bounds__(128, 2) void blind_rotate_fft_kernel(BlindRotateFft
                 v = lut[(n - s) & (POLY_N - 1)];
                 if ((n < s) != neg) v = (uint64_t)0 - v;
             }
-            acc[r] = v - 1;
+            acc[r] = acc_from_torus<SHIFTED>(v);
         }
     }
 
@@ -132,8 +181,7 @@ __global__ __launch_bounds__(128, 2) void blind_rotate_fft_kernel(BlindRotateFft
                 vq[r % RW] = pb[64];
             }
             const uint64_t wrapmask = __builtin_amdgcn_ballot_w64(64 * r < thr);
-            const uint32_t nhi = rot_sub_hi_compl(v, acc[r], wrapmask ^ keep_unless_wrapped);
-            const int32_t dig = (int32_t)(0xFFu - nhi) >> 9;
+            const int32_t dig = rot_sub_digit<SHIFTED>(v, acc[r], wrapmask ^ keep_unless_wrapped);
             if (r < 16) z[r].r = (double)dig; else z[r - 16].i = (double)dig;
             __builtin_amdgcn_sched_barrier(0);        // keep the reads of rows r + RW - 1, r + RW behind the use of row r
         }
@@ -188,9 +236,9 @@ __global__ __launch_bounds__(128, 2) void blind_rotate_fft_kernel(BlindRotateFft
         // burst overlaps the conversions instead of stalling the start of the next iteration)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            acc[r] += to_torus(z[r].r);
+            acc[r] = acc_add<SHIFTED>(acc[r], z[r].r);
             my_u[64 + lane + 64 * r] = acc[r];
-            acc[r + 16] += to_torus(z[r].i);
+            acc[r + 16] = acc_add<SHIFTED>(acc[r + 16], z[r].i);
             my_u[64 + lane + 64 * (r + 16)] = acc[r + 16];
             if (r == 0) my_u[64 + lane + 64 * 32] = acc[0];
             if (r == 15) my_u[lane] = acc[31];
@@ -202,15 +250,15 @@ __global__ __launch_bounds__(128, 2) void blind_rotate_fft_kernel(BlindRotateFft
 #pragma unroll
         for (int r = 0; r < 32; r++) {
             const int n = lane + 64 * r;
-            if (n == 0) out[0] = acc[r] + 1;
-            else out[POLY_N - n] = (uint64_t)0 - (acc[r] + 1);
+            if (n == 0) out[0] = acc_to_torus<SHIFTED>(acc[r]);
+            else out[POLY_N - n] = (uint64_t)0 - acc_to_torus<SHIFTED>(acc[r]);
         }
     } else {
-        if (lane == 0) out[BIG_N] = acc[0] + 1;
+        if (lane == 0) out[BIG_N] = acc_to_torus<SHIFTED>(acc[0]);
         uint64_t *body = P.body_ptrs ? P.body_ptrs[ct] : nullptr;      // rotation sharing: the whole body polynomial
         if (body) {
 #pragma unroll
-            for (int r = 0; r < 32; r++) body[lane + 64 * r] = acc[r] + 1;
+            for (int r = 0; r < 32; r++) body[lane + 64 * r] = acc_to_torus<SHIFTED>(acc[r]);
         }
     }
     }   // persistent loop
@@ -250,13 +298,14 @@ void fft_uniform_consts(double *w_re, double *w_im, double *u_re, double *u_im) 
     for (int k = 0; k < 3; k++) { u_re[k] = FU_RE[k]; u_im[k] = FU_IM[k]; }
 }
 
-hipError_t launch_blind_rotate_fft(const BlindRotateFftParams &p, hipStream_t s) {
+hipError_t launch_blind_rotate_fft(const BlindRotateFftParams &p, hipStream_t s, bool shifted_acc) {
     if (p.B <= 0) return hipSuccess;
     const size_t lds = (size_t)2 * FFT_LDS_DOUBLES * sizeof(double) + 16;
     hipError_t e = hipMemsetAsync(p.work_counter, 0, sizeof(uint32_t), s);
     if (e != hipSuccess) return e;
     const int grid = p.B < p.slots ? p.B : p.slots;
-    hipLaunchKernelGGL(blind_rotate_fft_kernel, dim3(grid), dim3(128), lds, s, p);
+    if (shifted_acc) hipLaunchKernelGGL(blind_rotate_fft_kernel<true>, dim3(grid), dim3(128), lds, s, p);
+    else hipLaunchKernelGGL(blind_rotate_fft_kernel<false>, dim3(grid), dim3(128), lds, s, p);
     return hipGetLastError();
 }
 

@@ -112,7 +112,9 @@ size_t blind_rotate_lds_bytes();
 hipError_t prepare_device_for_kernels();
 hipError_t read_device_ntt_consts(double *fwd_uni /*[64]*/, double *inv_uni /*[128]*/, double *crt);
 hipError_t launch_blind_rotate(const BlindRotateParams &p, hipStream_t s);
-hipError_t launch_blind_rotate_fft(const BlindRotateFftParams &p, hipStream_t s);    // 2 wavefronts per ciphertext
+// 2 wavefronts per ciphertext.  shifted_acc: the instantiation that keeps the accumulator shifted right by 8 (fft_kernels.hip);
+// the caller vouches that every word of every table under p.luts has its low 8 bits clear (luts_low_bytes_clear)
+hipError_t launch_blind_rotate_fft(const BlindRotateFftParams &p, hipStream_t s, bool shifted_acc);
 hipError_t launch_blind_rotate_fft4(const BlindRotateFftParams &p, hipStream_t s);   // 4 wavefronts per ciphertext
 // standard-domain key [n_polys][2048] u64 -> Fourier-domain key, with the device's own forward transform
 hipError_t launch_bsk_to_fft(const uint64_t *d_bsk_std, double *d_out, const double *d_lanetab, hipStream_t s,

@@ -65,25 +65,6 @@ INV6 = {
          "        }\n")],
 }
 
-# ---- TIMING ONLY: 52-bit accumulator in the low bits of a u64 (one's-complement flip, no shifts in the update) ----
-ACC52 = {
-    D: [("__device__ __forceinline__ uint64_t to_torus(double t) {\n"
-         "    const double g = 1.0 + __builtin_amdgcn_fract(t);\n"
-         "    const uint64_t b = __builtin_bit_cast(uint64_t, g);\n",
-         "__device__ __forceinline__ uint64_t to_torus(double t) {\n"
-         "    const double g = 1.0 + __builtin_amdgcn_fract(t);\n"
-         "    const uint64_t b = __builtin_bit_cast(uint64_t, g);\n"
-         "    return b;\n")],
-    K: [("            const uint32_t dhi = rot_sub_hi(v, acc[r], wrapmask ^ negmask);\n"
-         "            const int32_t dig = (int32_t)(dhi + 0x100u) >> 9;\n",
-         "            uint32_t mm;\n"
-         "            asm(\"v_cndmask_b32 %0, -1, 0, %1\" : \"=v\"(mm) : \"s\"(wrapmask ^ negmask));\n"
-         "            const uint64_t e = (v ^ (((uint64_t)mm << 32) | mm)) + acc[r];\n"
-         "            const uint32_t al = __builtin_amdgcn_alignbit((uint32_t)(e >> 32), (uint32_t)e, 28) + 1u;\n"
-         "            const int32_t dig = __builtin_amdgcn_sbfe(al, 1, 23);\n")],
-}
-
-
 # ---- TIMING ONLY (round 4): one LDS transpose per transform replaced by gfx950's permlane swaps ----
 # The stages on index bits 5 and 4 stay in layout A: v_permlane32_swap_b32 / v_permlane16_swap_b32 exchange lane bit 5 / 4
 # with a register bit (2 x 32 instructions per transform: 16 points x 4 dwords, two registers per instruction), so only
@@ -195,12 +176,9 @@ FLAGS = {"sched_default": [], "sched_memclause": ["-mllvm", "-amdgpu-sched-strat
 VARIANTS = {
     "base": {},
     "inv6c": INV6C,
-    "inv6c_acc52": merge(INV6C, ACC52),
     "one_barrier": ONE_BARRIER,
     "inv6": INV6,
-    "acc52": ACC52,
-    "inv6_acc52": merge(INV6, ACC52),
-    "all3": merge(ONE_BARRIER, INV6, ACC52),
+    "all3": merge(ONE_BARRIER, INV6),
     "permlane": PERMLANE,
     "permlane_half": PERMLANE_HALF,
     "permlane_free": PERMLANE_FREE,

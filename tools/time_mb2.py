@@ -27,7 +27,10 @@ for arith in (ARITHS or ((2,) if PROFILE else (1, 2))):
     if CHUNK:
         ctx.set_launch_chunk(arith, CHUNK[0])
     rng = np.random.default_rng(0)
-    luts = rng.integers(0, 2**64, (2, 2048), dtype=np.uint64)
+    # words like the catalogue's (multiples of 2^59): the classic f64 kernel then runs the instantiation the engine runs,
+    # the shifted accumulator; --general-luts: random words, its general instantiation
+    luts = rng.integers(0, 2**64, (2, 2048), dtype=np.uint64) if "--general-luts" in sys.argv else \
+        rng.integers(0, 32, (2, 2048)).astype(np.uint64) << np.uint64(59)
     for B in sizes:
         cts = rng.integers(0, 2**64, (B, 2049), dtype=np.uint64)
         idx = (np.arange(B) % 2).astype(np.uint32)
