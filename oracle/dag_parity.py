@@ -14,7 +14,8 @@ follower extracted from the wrong leader, a sum that read a block one launch ear
 `upload(array [n, 4, 2049])` places a string; `inputs` are the ciphertexts (made once) and the clear parameters.  A script
 must not branch on the kind of context.  What it wants to tell the test goes into inputs["facts"], a dict.
 
-tests/test_dag_parity.py (no GPU), tests/test_dag_parity_device.py and smoke() of __graft_entry__.py use this.
+tests/test_dag_parity.py (no GPU), tests/test_dag_parity_device.py, tests/test_sched_parity_device.py and smoke() of
+__graft_entry__.py use this.
 """
 import os
 import time
@@ -52,11 +53,12 @@ def _chars(v):
 
 class Outcome:
     """words: {result name: [n_chars, 4, 2049] u64}; plan: what the guard compares; seconds: the script and the reading
-    of its results (replay: the oracle's bootstraps included)"""
+    of its results (replay: the oracle's bootstraps included); user_tables (replay only): per launch group the
+    user-table ids its rows name (PlanRun.user_tables)"""
 
-    def __init__(self, words, plan, seconds, facts, rotations=None, extractions=None):
+    def __init__(self, words, plan, seconds, facts, rotations=None, extractions=None, user_tables=None):
         self.words, self.plan, self.seconds, self.facts = words, plan, seconds, facts
-        self.rotations, self.extractions = rotations, extractions
+        self.rotations, self.extractions, self.user_tables = rotations, extractions, user_tables
 
 
 def replay(script, inputs, oracle_sk, mode, string_mode=1, sharing=True, exact=True):
@@ -76,7 +78,7 @@ def replay(script, inputs, oracle_sk, mode, string_mode=1, sharing=True, exact=T
         ext = run.extractions if exact else plan["stats"]["pbs_extracted"]
         assert (rot, ext) == (plan["stats"]["pbs_executed"], plan["stats"]["pbs_extracted"]) and run.pbs == rot + ext
         del res
-        return Outcome(words, plan, dt, inputs["facts"], rot, ext)
+        return Outcome(words, plan, dt, inputs["facts"], rot, ext, run.user_tables)
     finally:
         run.close()
 
@@ -137,7 +139,7 @@ def check(script, inputs, want, sk, what, **kw):
 
 # ---- the cases: script, string mode, inputs (characters from a seeded generator, one NUL of padding each) ----------
 def case(name, keys):
-    """-> (script, string_mode, inputs) of case A .. G or "small" (the shape smoke() uses: `zama!\\0` / `ma`)"""
+    """-> (script, string_mode, inputs) of case A .. L or "small" (the shape smoke() uses: `zama!\\0` / `ma`)"""
     rng = np.random.default_rng(0xDA6 + sum(name.encode()))
     put = lambda text, at, pat: text[:at] + pat + text[at + len(pat):]
     if name == "small":
@@ -163,6 +165,29 @@ def case(name, keys):
         return (le_and_eq_ignore_case if name == "D" else two_jobs), 1, inp
     if name == "G":
         return eq_as_written, 0, {"a": encrypt(keys, b"fhe\0"), "b": encrypt(keys, b"fhf\0")}
+    # H .. L, the scheduler's hazards: wherever it could confuse two strings they hold the same clear message under
+    # fresh encryptions, so that only the words tell them apart
+    if name == "H":                                          # 0 = 2 and 1 = 3 in the clear; the pattern in 0, 2 and 4
+        hit, miss, hit4, miss5 = (printable(rng, 16) for _ in range(4))
+        clear = [put(hit, 6, b"Qz7#"), miss, put(hit, 6, b"Qz7#"), miss, put(hit4, 11, b"Qz7#"), miss5]
+        return skewed_requests, 1, {"texts": [encrypt(keys, t) for t in clear], "pattern": "Qz7#", "slots": 0, "clear": clear}
+    if name == "I":
+        a, d = printable(rng, 4, pad=0), printable(rng, 4, pad=0)
+        return freed_under_a_scheduled_tick, 1, {"a": encrypt(keys, a), "d1": encrypt(keys, d), "d2": encrypt(keys, d),
+                                                 "b": encrypt(keys, d), "c": encrypt(keys, d), "clear": (a, d)}
+    if name == "J":
+        a, b = b"hello world\0", b"HELLO WORLD\0"
+        return job_consuming_an_unfinished_job, 1, {"a": encrypt(keys, a), "b": encrypt(keys, b), "pattern": "wor",
+                                                    "clear": (a, b)}
+    if name == "K":
+        text, frm, to = b"ab~fcd~fgh\0\0", b"~f", b"[]"
+        return auto_flush_peels, 1, {"text": encrypt(keys, text), "from": encrypt(keys, frm), "to": encrypt(keys, to),
+                                     "threshold": 16, "clear": (text, frm, to)}
+    if name == "L":                                          # 2 jobs: tests/test_dag_parity.py asserts that they suffice
+        chars = [printable(rng, 1, pad=0) for _ in range(2)]
+        tables = [bytes(int(v) for v in rng.integers(0, 256, 256)) for _ in chars]
+        return tables_grow_under_scheduled_jobs, 1, {"chars": [encrypt(keys, c) for c in chars], "tables": tables,
+                                                     "clear": chars}
     raise KeyError(name)
 
 
@@ -237,3 +262,137 @@ def eq_as_written(sk, upload, inp):
     res = sk.eq(a, b)
     sk.flush()
     return {"eq": res}
+
+
+def skewed_requests(sk, upload, inp):
+    """H, the benchmark's schedule in small: one request per tick -- contains_clear and to_upper of a string that the
+    caller drops before the tick that reads it is enqueued -- drained by an asynchronous flush; the downloads
+    synchronise.  to_upper's result keeps sharing the input's untouched blocks; contains_clear's inputs go back to the
+    pool under scheduled ticks.  inp["slots"]: the tick balance (0: launch groups of up to three jobs' levels as they
+    come; otherwise every first level is cut to whole rounds and its excess runs one tick later with its consumers)."""
+    sk.set_tick_balance(inp["slots"])
+    try:
+        res = {}
+        for k, text in enumerate(inp["texts"]):
+            s = upload(text)
+            res["contains_%d" % k], res["upper_%d" % k] = sk.contains_clear(s, inp["pattern"]), sk.to_upper(s)
+            sk.submit()
+            del s
+            sk.pump(1)
+        sk.flush(wait=False)
+    finally:
+        sk.set_tick_balance(0)
+    return res
+
+
+def freed_under_a_scheduled_tick(sk, upload, inp):
+    """I: the inputs of a submitted job are released before any tick is enqueued, and two more strings are uploaded
+    behind them: they must not get the blocks that the scheduled eq still has to read (BlockPool::free defers them).
+    d1, d2, b and c hold one message, so both flags decrypt to 1 whichever blocks were read.  to_upper's result still
+    refers to a's blocks, so dropping a returns nothing: facts["blocks_returned"] are d1's and d2's."""
+    a, d1, d2 = upload(inp["a"]), upload(inp["d1"]), upload(inp["d2"])
+    up, same_d = sk.to_upper(a), sk.eq(d1, d2)
+    sk.submit()
+    live = sk.stats()["blocks_live"]
+    del a, d1, d2
+    inp["facts"]["blocks_returned"] = live - sk.stats()["blocks_live"]
+    b, c = upload(inp["b"]), upload(inp["c"])
+    same = sk.eq(b, c)
+    sk.submit()
+    sk.flush()
+    return {"up": up, "same_d": same_d, "same": same, "b": b, "c": c}
+
+
+def job_consuming_an_unfinished_job(sk, upload, inp):
+    """J: three jobs scheduled before anything is enqueued -- the second consumes every character of the first, the
+    third is independent -- two ticks pumped, then an operation flushed in between, which drains what is scheduled"""
+    a, b = upload(inp["a"]), upload(inp["b"])
+    low = sk.to_lower(b)
+    sk.submit()
+    same = sk.eq(a, low)
+    sk.submit()
+    other = sk.contains_clear(a, inp["pattern"])
+    sk.submit()
+    sk.pump(2)
+    mid = sk.len(a)
+    sk.flush()
+    return {"to_lower": low, "eq": same, "contains_clear": other, "len": mid}
+
+
+AUTO_FLUSH_DEFAULT = 8192                                    # Engine::auto_flush_pending as a context is created
+
+
+def auto_flush_peels(sk, upload, inp):
+    """K: with fhs_set_auto_flush(inp["threshold"]) the ready level is peeled again and again while the DAGs are still
+    being recorded: released pending nodes whose slots are reused, and an intermediate that is recorded, partly run and
+    dropped.  Only a context that has never been driven with submit flushes on its own."""
+    sk.set_auto_flush(inp["threshold"])
+    try:
+        text, frm, to = upload(inp["text"]), upload(inp["from"]), upload(inp["to"])
+        rep = sk.replace(text, frm, to)
+        tmp = sk.to_upper(text)
+        del tmp
+        pos = sk.rfind(text, frm.chars)
+        sk.flush()
+    finally:
+        sk.set_auto_flush(AUTO_FLUSH_DEFAULT)
+    return {"replace": rep, "rfind": pos}
+
+
+def tables_grow_under_scheduled_jobs(sk, upload, inp):
+    """L: map_clear of one character per job, each with a random 256-entry table of its own (about 64 user tables), one
+    job per tick: the device array of table polynomials has to grow -- wait for the stream, move -- in front of a tick
+    that has earlier ticks in the stream before it and scheduled ticks, which name their tables by id, behind it"""
+    res = {}
+    for k, (ch, table) in enumerate(zip(inp["chars"], inp["tables"])):
+        s = upload(ch)
+        res["map_%d" % k] = sk.map_clear(s, table)
+        sk.submit()
+        sk.pump(1)
+    sk.flush()
+    return res
+
+
+# ---- reading a plan ---------------------------------------------------------------------------------------------------
+def plan(script, inputs, string_mode=1, sharing=True):
+    """what a planner context plans for the script (plan_of), nothing executed: the structural facts of a configuration
+    whose words are not needed"""
+    run = PlanRun(None, 1, string_mode=string_mode)
+    try:
+        run.sk.ctx.set_rotation_sharing(sharing)
+        run.sk.stats(reset=True)
+        res = script(run.sk, run.upload_string, dict(inputs, facts={}))
+        out = plan_of(run.sk)
+        del res
+        return out
+    finally:
+        run.close()
+
+
+def levels_by_group(plan):
+    """the level widths of a plan, split by launch group: statistics note a tick's levels, then its group, so each group is
+    the sum of the next few widths"""
+    widths, out, i = plan["level_widths"], [], 0
+    for g in plan["launch_groups"]:
+        j = i
+        while sum(widths[i:j]) < g and j < len(widths):
+            j += 1
+        assert sum(widths[i:j]) == g and j > i, (widths, plan["launch_groups"])
+        out.append(widths[i:j])
+        i = j
+    assert i == len(widths), (widths, plan["launch_groups"])
+    return out
+
+
+def table_array_growth(user_tables, n_catalogue):
+    """Engine::ensure_luts' rule over the launch groups of a replay (PlanRun.user_tables): the device array starts with
+    room for the catalogue and grows, when a group names user tables it has no room for, to max(need, twice the room,
+    catalogue + 64).  -> [(group, user tables resident before it, after it)] of every group at which it grows."""
+    cap, seen, out = n_catalogue, set(), []
+    for g, ids in enumerate(user_tables):
+        need = n_catalogue + len(seen | ids)
+        if need > cap:
+            out.append((g, len(seen), len(seen | ids)))
+            cap = max(need, 2 * cap, n_catalogue + 64)
+        seen |= ids
+    return out

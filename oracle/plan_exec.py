@@ -45,6 +45,7 @@ class PlanRun:
         self.pbs = self.groups = 0
         self.rotations = self.extractions = 0        # exact_extractions only: blind rotations run, rows taken from a leader's
         self.pbs_seconds = 0.0
+        self.user_tables = []                        # per launch group run so far: the user-table ids its rows name
 
     def close(self):
         self.sk.close()
@@ -70,6 +71,28 @@ class PlanRun:
         self.sk.ctx._check(self.L.fhs_debug_plan_read(self.h, buf.ctypes.data, n.value, C.byref(n)))
         return buf[:n.value]
 
+    def user_tables_by_group(self, t):
+        """per launch group (TR_GROUP_END) of the trace words `t`, the set of user-table ids -- those from the catalogue's
+        count up -- that its rows name: what Engine::ensure_luts has to make resident in front of that group"""
+        n_cat, out, ids, i = self.L.fhs_lut_catalogue_count(), [], set(), 0
+        while i < len(t):
+            tag = t[i]
+            if tag == TR_UPLOAD:
+                i += 2
+            elif tag == TR_ROW:
+                if t[i + 2] >= n_cat:
+                    ids.add(t[i + 2])
+                i += 5 + 2 * t[i + 4]
+            elif tag == TR_EXT:                       # (a follower shares its leader's table)
+                i += 4
+            elif tag == TR_GROUP_END:
+                out.append(ids)
+                ids = set()
+                i += 2
+            else:
+                raise ValueError("bad plan trace word %d at %d" % (tag, i))
+        return out
+
     def _lin(self, konst, terms):
         acc = np.zeros(BIG_CT, np.uint64)
         for tok, coef in terms:
@@ -80,6 +103,7 @@ class PlanRun:
     def run(self):
         """execute everything recorded since the last run() (the planner flushes inside fhs_debug_plan_read)"""
         t = self._read_trace().tolist()
+        self.user_tables.extend(self.user_tables_by_group(t))
         if self.exact:
             return self._run_exact(t)
         i, rows, by_out = 0, [], {}
