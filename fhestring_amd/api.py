@@ -13,6 +13,8 @@ POLY_N = _K["FHS_POLY_N"]
 PACK_GROUP = _K["FHS_PACK_GROUP"]             # blocks per packed GLWE
 PACK_KEY_WORDS = _K["FHS_PACK_KEY_WORDS"]
 REKEY_KEY_WORDS = _K["FHS_REKEY_KEY_WORDS"]
+SELECT_QUERY_BIT_WORDS = _K["FHS_SELECT_QUERY_BIT_WORDS"]       # u64 words of one index bit's GGSW
+SELECT_REKEY_COST = _K["FHS_SELECT_REKEY_COST"]
 
 
 def _ptr(a):
@@ -145,6 +147,15 @@ class Context:
         body32 = np.ascontiguousarray(body32, np.uint32).reshape(n_blocks)
         m_out, b_out = np.zeros((g, POLY_N), np.uint32), np.zeros(n_blocks, np.uint32)
         self._check(self._L.fhs_debug_rekey_device(self._h, _ptr(mask32), _ptr(body32), n_blocks, _ptr(m_out), _ptr(b_out)))
+        return m_out, b_out
+
+    def select_device(self, query, mask32, body32, n_blocks, row_chars):
+        """fhs_debug_select_device: the select's kernels on the raw words of a whole entry -> (mask32[2048],
+        body32[4 row_chars]), the arguments and results of select_host."""
+        query, bits, mask32, body32 = _select_args(query, mask32, body32, n_blocks)
+        m_out, b_out = np.zeros(POLY_N, np.uint32), np.zeros(4 * row_chars, np.uint32)
+        self._check(self._L.fhs_debug_select_device(self._h, _ptr(query), bits, _ptr(mask32), _ptr(body32), n_blocks, row_chars,
+                                                    _ptr(m_out), _ptr(b_out)))
         return m_out, b_out
 
     def rekey_packed_device(self, mask64, body64, n_blocks):
@@ -376,6 +387,17 @@ class MyClientKey:
         if self._L.fhs_client_rekey_key(self._h, to._h, _ptr(key)) != 0:
             raise FhsError("fhs_client_rekey_key failed")
         return key
+
+    def select_query(self, index, n_chars, row_chars):
+        """fhs_client_select_query: the bits of row `index` of a table of n_chars characters in rows of row_chars, as GGSW
+        ciphertexts under this client's key -> (query[bits][4][mask, body][2048] u64, bits); a fresh query per call."""
+        bits = select_bits(n_chars, row_chars)
+        if bits == 0:
+            raise ValueError("no table of %d characters in rows of %d can be selected from" % (n_chars, row_chars))
+        query = np.empty((bits, 4, 2, POLY_N), np.uint64)
+        if self._L.fhs_client_select_query(self._h, int(index), bits, _ptr(query)) != 0:
+            raise FhsError("fhs_client_select_query failed")
+        return query, bits
 
     def save_rekey_key(self, to, path):
         """fhs_client_save_rekey_key: kind 7 key file with a fresh re-key key from this client to `to`."""
@@ -874,6 +896,34 @@ def rekey_host(key, mask32, body32=None, n_blocks=None):
     return CompactFheString(n_blocks // 4, m_out, b_out) if compact is not None else (m_out, b_out)
 
 
+def select_bits(n_chars, row_chars):
+    """fhs_store_select_bits: index bits of a table of n_chars characters in rows of row_chars, 0 for a refused shape."""
+    return int(lib().fhs_store_select_bits(int(n_chars), int(row_chars)))
+
+
+def _select_args(query, mask32, body32, n_blocks):
+    query = np.ascontiguousarray(query, np.uint64)
+    assert query.size % SELECT_QUERY_BIT_WORDS == 0
+    g = (n_blocks + PACK_GROUP - 1) // PACK_GROUP
+    return (query, query.size // SELECT_QUERY_BIT_WORDS, np.ascontiguousarray(mask32, np.uint32).reshape(g, POLY_N),
+            np.ascontiguousarray(body32, np.uint32).reshape(n_blocks))
+
+
+def select_host(query, mask32, body32=None, n_blocks=None, row_chars=None):
+    """fhs_store_select_host: host reference of StoredString.select.  select_host(query, compact, row_chars=r) ->
+    CompactFheString of the selected row; select_host(query, mask32, body32, n_blocks, row_chars) -> the raw
+    (mask32[2048], body32[4 row_chars])."""
+    compact = mask32 if isinstance(mask32, CompactFheString) else None
+    if compact is not None:
+        mask32, body32, n_blocks = compact.mask32, compact.body32, 4 * len(compact)
+    query, bits, mask32, body32 = _select_args(query, mask32, body32, n_blocks)
+    m_out, b_out = np.zeros((1, POLY_N), np.uint32), np.zeros(4 * row_chars, np.uint32)
+    rc = lib().fhs_store_select_host(_ptr(query), bits, _ptr(mask32), _ptr(body32), n_blocks, row_chars, _ptr(m_out), _ptr(b_out))
+    if rc != 0:
+        raise FhsError("fhs_store_select_host failed (%d)" % rc)
+    return CompactFheString(row_chars, m_out, b_out) if compact is not None else (m_out[0], b_out)
+
+
 def rekey_packed_host(key, mask64, body64, n_blocks):
     """fhs_rekey_packed_host: host reference of the packed download for a recipient.  The 64-bit GLWEs of pack_host (or of
     download_packed(wide=True)) -> PackedFheString under the recipient's key (n_blocks a multiple of 4) or, for any other
@@ -981,6 +1031,16 @@ class StoredString:
             return self
         eid = C.c_uint64(0)
         self.sk.ctx._check(self.sk.ctx._L.fhs_store_rekey(self.sk.ctx._h, self.id, C.byref(eid)))
+        return StoredString(self.sk, eid.value)
+
+    def select(self, query, row_chars):
+        """fhs_store_select: the row named by the encrypted index `query` (MyClientKey.select_query) of this entry read as
+        rows of row_chars characters -> a new StoredString of row_chars characters; this one is only read."""
+        query = np.ascontiguousarray(query, np.uint64)
+        assert query.size % SELECT_QUERY_BIT_WORDS == 0
+        eid = C.c_uint64(0)
+        self.sk.ctx._check(self.sk.ctx._L.fhs_store_select(self.sk.ctx._h, self.id, int(row_chars), _ptr(query),
+                                                           query.size // SELECT_QUERY_BIT_WORDS, C.byref(eid)))
         return StoredString(self.sk, eid.value)
 
     @property

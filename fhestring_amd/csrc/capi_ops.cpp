@@ -343,6 +343,19 @@ int fhs_debug_rekey_device(fhs_ctx *c, const void *mask32, const void *body32, s
     return c->eng.debug_rekey(static_cast<const uint32_t *>(mask32), static_cast<const uint32_t *>(body32), n_blocks,
                               static_cast<uint32_t *>(mask32_out), static_cast<uint32_t *>(body32_out));
 }
+// ---- string store: select by encrypted index ----
+int fhs_store_select(fhs_ctx *c, uint64_t id, size_t row_chars, const uint64_t *query, int bits, uint64_t *id_out) {
+    if (!c || !id_out) return bad(c);
+    *id_out = 0;
+    if (!query) return bad(c);
+    return c->eng.store_select(id, row_chars, query, bits, id_out);
+}
+int fhs_debug_select_device(fhs_ctx *c, const uint64_t *query, int bits, const void *mask32, const void *body32, size_t n_blocks,
+                            size_t row_chars, void *mask32_out, void *body32_out) {
+    if (!c || !query || !mask32 || !body32 || !mask32_out || !body32_out) return bad(c);
+    return c->eng.debug_select(query, bits, static_cast<const uint32_t *>(mask32), static_cast<const uint32_t *>(body32), n_blocks,
+                               row_chars, static_cast<uint32_t *>(mask32_out), static_cast<uint32_t *>(body32_out));
+}
 // ---- packed result download under a recipient's key ----
 int fhs_download_string_packed_for(fhs_ctx *c, const fhs_char_t *chars, size_t n, void *mask16, void *body16, uint64_t *mask64,
                                    uint64_t *body64) {

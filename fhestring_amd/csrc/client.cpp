@@ -51,6 +51,7 @@ struct fhs_client {
     std::vector<uint64_t> pk_body;
     std::mutex pk_mu;
     std::atomic<uint64_t> rekey_calls{0};   // re-key keys made INTO this client (fhs_client_rekey_key): one ChaCha key each
+    std::atomic<uint64_t> select_calls{0};  // select queries made by this client (fhs_client_select_query): one ChaCha key each
 };
 
 namespace {
@@ -637,6 +638,43 @@ int fhs_client_save_rekey_key(fhs_client *from, fhs_client *to, const char *path
     std::vector<uint64_t> k(FHS_REKEY_KEY_WORDS);
     if (!rekey_key(from, to, k.data())) return FHS_ERR_STATE;
     return KeyFileWriter(path, 7).put(k.data(), FHS_REKEY_KEY_WORDS * 8).close();
+}
+
+}  // extern "C"
+
+// ---- string store: select queries (select_host.cpp, select_kernels.hip) -----------------------------------------------
+namespace {
+
+// GGSW(bit) per index bit under the client's own GLWE key, four rows of keyswitch_key_row on the 58-bit grid: rows 0, 1
+// carry bit (-S) 2^(64 - 16 (l + 1)) and meet the digits of a mask difference, rows 2, 3 carry bit 2^(64 - 16 (l + 1)) at
+// coefficient 0 and meet the digits of a body difference.  Masks and noise come from a ChaCha key of this call alone,
+// streams 4 k + row of DOM_MASK / DOM_NOISE: OS entropy, or for an insecure seeded client its seed, the tag below and the
+// number of queries it has made so far.
+constexpr uint64_t SEED_TAG_SELECT = 0x5345454453454c31ull;
+bool select_query(fhs_client *ck, uint64_t index, int bits, uint64_t *out) {
+    ChaKey key;
+    if (!public_seed(ck, SEED_TAG_SELECT, ck->select_calls.fetch_add(1), key)) return false;
+    std::vector<uint64_t> msg(POLY_N);
+    for (int k = 0; k < bits; k++) {
+        const uint64_t bit = (index >> k) & 1;
+        for (int row = 0; row < 4; row++) {
+            for (int n = 0; n < POLY_N; n++)
+                msg[n] = row < 2 ? (uint64_t)0 - bit * ck->glwe_sk[n] : (n == 0 ? bit : 0);
+            Rng gm(key, 4 * k + row, DOM_MASK), e(key, 4 * k + row, DOM_NOISE);
+            uint64_t *mask = out + ((size_t)k * 4 + row) * 2 * POLY_N;
+            keyswitch_key_row(gm, e, ck->glwe_sk.data(), msg.data(), 64 - 16 * ((row & 1) + 1), mask, mask + POLY_N);
+        }
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fhs_client_select_query(fhs_client *ck, uint64_t index, int bits, uint64_t *query_out) {
+    if (!ck || !query_out || bits < 1 || bits > 24) return FHS_ERR_ARG;
+    return select_query(ck, index, bits, query_out) ? FHS_OK : FHS_ERR_STATE;
 }
 
 }  // extern "C"

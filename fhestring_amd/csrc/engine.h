@@ -20,6 +20,7 @@
 #include "context.h"
 #include "engine_resources.h"
 #include "luts.h"
+#include "select_kernels.h"
 
 namespace fhs {
 
@@ -202,6 +203,15 @@ class Engine {
     // body16[4 count].  One launch on the context's stream (store_switch16_kernel / rekey_entry_packed_kernel), two copies,
     // one sync; no pool block, no node, no packing key, and the entry stays as it is.
     int store_read_packed(uint64_t id, size_t first_char, size_t count, bool recipient, uint16_t *mask16, uint16_t *body16);
+    // Fetches one row of entry `id`, read as rows of row_chars characters, by the encrypted index in `query` (`bits` GGSWs,
+    // fhs_client_select_query) into a NEW entry of row_chars characters (select_kernels.hip): one
+    // launch per tree level and per rotate bit on the context's stream, no bootstrap, no pool block, no key.  The result's
+    // blocks take the maxima of figure and cycles over the rows, one fresh rotation group if any candidate has one, and
+    // rekeys + SELECT_REKEY_COST per launch.  A planner does the bookkeeping only.
+    int store_select(uint64_t id, size_t row_chars, const uint64_t *query, int bits, uint64_t *id_out);
+    // diagnostic: the same launches on host words, the arguments of fhs_store_select_host
+    int debug_select(const uint64_t *query, int bits, const uint32_t *mask32, const uint32_t *body32, size_t n_blocks,
+                     size_t row_chars, uint32_t *mask_out, uint32_t *body_out);
     // diagnostic: the kernel on host words of any block count; the outputs may be the inputs
     int debug_rekey(const uint32_t *mask32, const uint32_t *body32, size_t n_blocks, uint32_t *mask_out, uint32_t *body_out);
     // diagnostic: the recipient download's kernel alone on host words, mask64 / body64 [ceil(n_blocks / 2048)][2048]
@@ -374,6 +384,9 @@ class Engine {
                            size_t n_blocks);
     // one launch of the recipient download's kernel: level-11 GLWEs [groups][2][2048] -> 16-bit words under the new key
     hipError_t rekey_packed_words(const uint64_t *d_glwe, uint16_t *d_mask16, uint16_t *d_body16, size_t n_blocks);
+    // the select's launches from device words of the entry layout into d_mask_out[2048] | d_body_out[4 row_chars]
+    hipError_t select_words(const uint64_t *query, const uint32_t *d_mask, const uint32_t *d_body, size_t n_blocks,
+                            const SelectShape &sh, uint32_t *d_mask_out, uint32_t *d_body_out);
     hipError_t pack_tree_pass(const Bid *b, size_t n, size_t groups);
     std::map<uint64_t, StoreEntry> store_;
     uint64_t store_ids_ = 0;             // ids handed out: never reused inside a context

@@ -7,6 +7,7 @@
 #include "pk_kernels.h"
 #include "rekey_kernels.h"
 #include "seeded_kernels.h"
+#include "select_kernels.h"
 #include "store_kernels.h"
 
 #include <algorithm>
@@ -682,6 +683,125 @@ int Engine::debug_rekey(const uint32_t *mask32, const uint32_t *body32, size_t n
     hipError_t es = hipStreamSynchronize(ctx.stream);            // before buf goes, on every path
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return ctx.hip_fail(e, "re-key (diagnostic)");
+    return 0;
+}
+
+// ---- string store: select by encrypted index ---------------------------------------------------------------------------
+// The query goes to the transform domain on the host (convert_polys_to_ntt writes straight into the pinned staging
+// buffer), crosses the bus as one table pass and lands in ctx.sel_query; then one launch per tree level and per rotate
+// bit.  Launch k reads the entry (k = 0) or ctx.sel_ws[(k - 1) & 1] and writes ctx.sel_ws[k & 1] or, the last one, the
+// caller's destination: never in place.  The three context buffers only grow, behind a drained stream (queued launches
+// of an earlier select still read them).
+hipError_t Engine::select_words(const uint64_t *query, const uint32_t *d_mask, const uint32_t *d_body, size_t n_blocks,
+                                const SelectShape &sh, uint32_t *d_mask_out, uint32_t *d_body_out) {
+    const size_t n_polys = (size_t)sh.bits * SELECT_BIT_POLYS, q_words = n_polys * 2 * POLY_N;
+    const size_t ws_nodes[2] = {std::max<size_t>(1, (sh.groups + 1) / 2), std::max<size_t>(1, (sh.groups + 3) / 4)};
+    const size_t glwe_bytes = (size_t)2 * POLY_N * sizeof(uint32_t);
+    if (ctx.sel_query.cap < q_words * 8 || ctx.sel_ws[0].cap < ws_nodes[0] * glwe_bytes || ctx.sel_ws[1].cap < ws_nodes[1] * glwe_bytes) {
+        hipError_t e = hipStreamSynchronize(ctx.stream);
+        if (e == hipSuccess) e = ctx.sel_query.reserve(q_words * 8);
+        for (int k = 0; k < 2 && e == hipSuccess; k++) e = ctx.sel_ws[k].reserve(ws_nodes[k] * glwe_bytes);
+        if (e != hipSuccess) return e;
+    }
+    if (!ctx.select_prepared) {
+        if (hipError_t e = prepare_device_for_select()) return e;
+        ctx.select_prepared = true;
+    }
+    size_t at = 0;
+    if (!xfer_.ensure((q_words + BIG_CT) / (BIG_CT + 1), ctx.stream) || !xfer_.begin_table_pass(q_words, at, ctx.stream))
+        return hipErrorOutOfMemory;
+    convert_polys_to_ntt(query, reinterpret_cast<double *>(xfer_.pin() + at), n_polys, BSK_QUANT_BITS);
+    hipError_t e = xfer_.copy_up(at, q_words, ctx.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx.sel_query.ptr, xfer_.dev() + at, q_words * 8, hipMemcpyDeviceToDevice, ctx.stream);
+
+    SelectCmuxParams p{};
+    p.query_ntt = ctx.sel_query.as<double>(); p.tw = ctx.tw;
+    p.src_mask = d_mask; p.src_body = d_body; p.src_nodes = (uint32_t)sh.groups; p.src_body_total = (uint32_t)n_blocks;
+    const int launches = sh.tree_levels + sh.rot_bits;
+    for (int k = 0; k < launches && e == hipSuccess; k++) {
+        const bool tree = k < sh.tree_levels, last = k == launches - 1;
+        const uint32_t out_nodes = tree ? (p.src_nodes + 1) / 2 : 1u;
+        p.bit = tree ? sh.rot_bits + k : k - sh.tree_levels;
+        p.rotate = tree ? 0u : (uint32_t)(sh.row_blocks << p.bit);
+        p.dst_mask = last ? d_mask_out : ctx.sel_ws[k & 1].as<uint32_t>();
+        p.dst_body = last ? d_body_out : p.dst_mask + (size_t)out_nodes * POLY_N;
+        p.store_body = last ? (uint32_t)sh.row_blocks : (uint32_t)SELECT_GROUP;
+        e = launch_select_cmux(p, ctx.stream);
+        p.src_mask = p.dst_mask; p.src_body = p.dst_body; p.src_nodes = out_nodes; p.src_body_total = out_nodes * SELECT_GROUP;
+    }
+    return e;
+}
+
+int Engine::store_select(uint64_t id, size_t row_chars, const uint64_t *query, int bits, uint64_t *id_out) {
+    auto it = store_.find(id);
+    if (it == store_.end()) return ctx.fail(-1, "string store: unknown entry id");
+    const StoreEntry &src = it->second;
+    SelectShape sh;
+    if ((src.n_blocks & 3) || !select_shape(src.n_blocks / 4, row_chars, sh))
+        return ctx.fail(-1, "string store: select needs rows of a power of two of 1..512 characters, a whole number of them, at least two");
+    if (bits != sh.bits) return ctx.fail(-1, "string store: the query's bit count is not fhs_store_select_bits of this shape");
+    if (!planner && !ctx.d_tables)
+        return ctx.fail(-3, "string store: select needs the transform tables that the first fhs_load_server_key uploads");
+    const int rekeys = src.rekeys + SELECT_REKEY_COST * (sh.tree_levels + sh.rot_bits);
+    if (rekeys > STORE_MAX_REKEYS)
+        return ctx.fail(-4, "string store: the selected entry would exceed FHS_STORE_MAX_REKEYS re-keys' worth of noise");
+    // block j of the result: the maxima over block j of every row; one fresh rotation group if any candidate has one
+    StoreEntry dst;
+    dst.n_blocks = sh.row_blocks;
+    dst.var.assign(sh.row_blocks, 1); dst.cycles.assign(sh.row_blocks, 0); dst.rot.assign(sh.row_blocks, 0);
+    dst.rekeys = (uint8_t)rekeys;
+    std::vector<uint8_t> grouped(sh.row_blocks, 0);
+    bool any = false;
+    for (size_t row = 0; row < sh.rows; row++)
+        for (size_t j = 0; j < sh.row_blocks; j++) {
+            const size_t t = row * sh.row_blocks + j;
+            dst.var[j] = std::max(dst.var[j], src.var[t]);
+            dst.cycles[j] = std::max(dst.cycles[j], src.cycles[t]);
+            if (src.rot[t]) grouped[j] = 1, any = true;
+        }
+    if (!planner) {
+        (void)hipSetDevice(ctx.device);
+        hipError_t e = dst.buf.reserve_exact(dst.bytes());
+        if (e == hipSuccess)
+            e = select_words(query, src.buf.as<uint32_t>(), src.buf.as<uint32_t>() + src.groups() * POLY_N, src.n_blocks, sh,
+                             dst.buf.as<uint32_t>(), dst.buf.as<uint32_t>() + POLY_N);
+        if (e != hipSuccess) {
+            (void)hipStreamSynchronize(ctx.stream);                  // before dst.buf goes: a launch may be queued
+            return ctx.hip_fail(e, "string store: select");
+        }
+    }
+    if (any) {
+        const uint32_t fresh = ++rot_counter_ ? rot_counter_ : ++rot_counter_;
+        for (size_t j = 0; j < sh.row_blocks; j++)
+            if (grouped[j]) dst.rot[j] = fresh;
+    }
+    const uint64_t nid = ++store_ids_;
+    store_.emplace(nid, std::move(dst));
+    *id_out = nid;
+    return 0;
+}
+
+// Diagnostic: the same launches on raw host words, through a scratch allocation of the entry layout.
+int Engine::debug_select(const uint64_t *query, int bits, const uint32_t *mask32, const uint32_t *body32, size_t n_blocks,
+                         size_t row_chars, uint32_t *mask_out, uint32_t *body_out) {
+    if (planner) return ctx.fail(-3, "planner context: nothing is computed");
+    SelectShape sh;
+    if ((n_blocks & 3) || !select_shape(n_blocks / 4, row_chars, sh) || bits != sh.bits)
+        return ctx.fail(-1, "select (diagnostic): a refused shape or bit count");
+    if (!ctx.d_tables) return ctx.fail(-3, "select needs the transform tables that the first fhs_load_server_key uploads");
+    (void)hipSetDevice(ctx.device);
+    const size_t mask_words = sh.groups * POLY_N;
+    DevBuf buf;
+    hipError_t e = buf.reserve_exact((mask_words + n_blocks + POLY_N + sh.row_blocks) * 4);
+    uint32_t *d_mask = buf.as<uint32_t>(), *d_body = d_mask + mask_words, *d_mask_out = d_body + n_blocks, *d_body_out = d_mask_out + POLY_N;
+    if (e == hipSuccess) e = hipMemcpyAsync(d_mask, mask32, mask_words * 4, hipMemcpyHostToDevice, ctx.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_body, body32, n_blocks * 4, hipMemcpyHostToDevice, ctx.stream);
+    if (e == hipSuccess) e = select_words(query, d_mask, d_body, n_blocks, sh, d_mask_out, d_body_out);
+    if (e == hipSuccess) e = hipMemcpyAsync(mask_out, d_mask_out, POLY_N * 4, hipMemcpyDeviceToHost, ctx.stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(body_out, d_body_out, sh.row_blocks * 4, hipMemcpyDeviceToHost, ctx.stream);
+    hipError_t es = hipStreamSynchronize(ctx.stream);            // before buf goes, on every path
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return ctx.hip_fail(e, "select (diagnostic)");
     return 0;
 }
 

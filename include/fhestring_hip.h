@@ -946,6 +946,71 @@ int fhs_store_download_packed(fhs_ctx *ctx, uint64_t id, size_t first_char, size
 int fhs_store_packed_host(const uint64_t *rekey_key /*[FHS_REKEY_KEY_WORDS], or NULL*/, const void *mask32, const void *body32,
                           size_t n_blocks_entry, size_t first_char, size_t count, void *mask16, void *body16);
 
+/* ---- string store: fetching a row by encrypted index --------------------------------------------------------
+ * Every read above names its window in the clear: the server learns which row of a parked table a client fetches.  Here
+ * the client sends the bits of its row index as GGSW ciphertexts under its own GLWE key and the server selects the row
+ * with CMuxes on the entry's GLWEs: no bootstrap, no pool block, no server key, no auxiliary key.
+ * GEOMETRY.  Entry `id` of n characters is read as R = n / row_chars rows; row_chars is a power of two in
+ * 1..FHS_SELECT_MAX_ROW_CHARS, n a multiple of it and R >= 2, otherwise FHS_ERR_ARG (rows longer than a group are not
+ * built).  A row is 4 row_chars consecutive blocks, so a group of 2048 blocks holds 2^r rows, r = log2(512 / row_chars).
+ * The index p has bits = ceil(log2 R) bits, bit 0 least significant: with G = ceil(4n / 2048) > 1 groups the low r bits
+ * rotate inside a group and the bits - r = ceil(log2 G) bits above them pick the group; with one group only the
+ * ceil(log2 R) rotate bits exist.  fhs_store_select_bits returns `bits`, or 0 for a refused shape.
+ * ORDER OF WORK (fixed).  1. The tree: level t = 0, 1, .. pairs nodes (2i, 2i + 1) of the level below (level 0: the
+ * entry's groups) under bit r + t, node i of the next level = CMux(bit, node 2i, node 2i + 1); a missing right sibling is
+ * the zero GLWE.  2. Then for k = 0 .. (rotate bits) - 1:  G <- CMux(bit k, G, X^(-4 row_chars 2^k) G), where
+ * (X^-s G)_n = G_(n + s) for n + s < 2048 and -G_(n + s - 2048) otherwise.
+ * ONE CMux of 32-bit GLWEs a, b (mask32[2048], body32[2048]; body words an entry does not store -- the tail of a partial
+ * last group -- count as 0), exact in wrapping words in R = Z_2^64[X]/(X^2048 + 1):
+ *   D = (b - a) mod 2^32 word by word, mask and body;  D << 32 = d_0 2^48 + d_1 2^32 with the balanced 16-bit digits of
+ *   the re-key section (no rounding on the way in);  with the four digit polynomials l = 0..3 = mask d_0, mask d_1,
+ *   body d_0, body d_1 and the four rows of the bit's GGSW,
+ *   out_col = ((a_col << 32) + sum_l d_l * GGSW[l].col + 2^31) >> 32      for col = mask, body.
+ * Every level stores 32-bit words, so every level is the same operation.
+ * RESULT: a NEW entry of row_chars characters -- one group, mask32[2048] and body32[4 row_chars] = coefficients
+ * 0 .. 4 row_chars - 1 of the last CMux; fhs_store_get / _rekey / _download_packed (own key or recipient) / _export take it
+ * unchanged.  The source entry is only read.
+ * AN INDEX p >= R is the caller's error and is not detected: the words are still deterministic and equal to the host
+ * reference's; where whole tree nodes are missing the characters are NUL, inside a partial last group they are
+ * unspecified.  As everywhere, a context CANNOT TELL which key an entry or a query is under: a query made by another
+ * client, or for another shape, gives garbage without any error.
+ * THE QUERY is `bits` GGSW ciphertexts, [bit][row: mask d_0, mask d_1, body d_0, body d_1][mask, body][2048] u64 words.
+ * A row is (mask, body = mask * S + e + m) on the bootstrapping key's 58-bit grid with the GLWE noise, as the re-key key:
+ *   mask-digit row l = 0, 1:  m = bit x (-S) x 2^(64 - 16 (l + 1));     body-digit row l:  m = bit x 2^(64 - 16 (l + 1)).
+ * 128 KB per bit.  Randomness follows the re-key key's rule: a ChaCha20 key drawn from getrandom(2) for that call alone
+ * (streams = the row number, domains 2 = masks / 3 = noise); an insecure seeded client derives it from its seed, a tag of
+ * its own and the number of queries it has made so far (tests only).  Two queries, also for the same index, never share
+ * a mask or noise.
+ * NOISE AND BOOKKEEPING (host side; a planner context does all of it and allocates nothing).  One CMux adds the external
+ * product's sigma 2^33.1 and a 32-bit rounding's 2^35.2: variance 1.03 x one re-key's, charged as FHS_SELECT_REKEY_COST
+ * re-keys.  The result's re-key counter is the source's + FHS_SELECT_REKEY_COST x (tree levels + rotate bits); a result
+ * past FHS_STORE_MAX_REKEYS is refused with FHS_ERR_LIMIT before anything is allocated.  Block j of the result takes the
+ * maximum figure and the maximum `cycles` of block j over all R rows; its rotation group is 0 if no candidate block of
+ * any row has one, otherwise ONE fresh group shared by all such result blocks (fully correlated: the upper bound). */
+#define FHS_SELECT_MAX_ROW_CHARS 512
+#define FHS_SELECT_QUERY_BIT_WORDS ((size_t)4 * 2 * 2048)        /* u64 words of one index bit's GGSW */
+#define FHS_SELECT_QUERY_WORDS(bits) ((size_t)(bits) * FHS_SELECT_QUERY_BIT_WORDS)
+#define FHS_SELECT_REKEY_COST 2
+/* ceil(log2(n_chars / row_chars)), or 0 for a shape fhs_store_select refuses. */
+int fhs_store_select_bits(size_t n_chars, size_t row_chars);
+/* A fresh query for row `index` (bit k of it goes into GGSW k; bits of index above `bits` are ignored).  bits 1..24. */
+int fhs_client_select_query(fhs_client *ck, uint64_t index, int bits, uint64_t *query_out /*[FHS_SELECT_QUERY_WORDS(bits)]*/);
+/* Selects the row.  The query crosses the bus through the pinned staging buffer and is converted to the transform
+ * domain on the host; one kernel launch per tree level and per rotate bit on the context's stream, behind every queued
+ * fhs_store_get / fhs_store_rekey of the entry; *id_out receives the new entry.  Needs no server key loaded at the time
+ * of the call, but the transform tables that the FIRST fhs_load_server_key of a context uploads: FHS_ERR_STATE before
+ * that on a device context (a later server-key reload changes nothing).  FHS_ERR_ARG: unknown id, a refused shape, bits
+ * != fhs_store_select_bits.  FHS_ERR_LIMIT: see above. */
+int fhs_store_select(fhs_ctx *ctx, uint64_t id, size_t row_chars, const uint64_t *query, int bits, uint64_t *id_out);
+/* Host reference (public data only, no GPU): the same words as the device.  mask32 / body32: the WHOLE entry as
+ * fhs_store_export gives it, n_blocks_entry = 4 x its characters; mask32_out[2048], body32_out[4 row_chars]. */
+int fhs_store_select_host(const uint64_t *query, int bits, const void *mask32, const void *body32, size_t n_blocks_entry,
+                          size_t row_chars, void *mask32_out, void *body32_out);
+/* Diagnostic: the device kernels on raw words, the arguments of fhs_store_select_host.  FHS_ERR_STATE on a planner
+ * context or before the first server key. */
+int fhs_debug_select_device(fhs_ctx *ctx, const uint64_t *query, int bits, const void *mask32, const void *body32,
+                            size_t n_blocks, size_t row_chars, void *mask32_out, void *body32_out);
+
 /* ---- block pool: what it holds, and giving it back ---------------------------------------------------------
  * Ciphertext blocks are carved from chunks of 2048 blocks (2048 x 2050 x 8 = 33 587 200 B each).  A released block goes
  * back to the context's free list, its chunk stays: without a trim a context sits on the high-water mark of its blocks

@@ -71,6 +71,26 @@ int main() {
         char pbuf[16];
         size_t pn = 0;
         CHECK(fhs_client_decrypt_str(ck, win.data(), 10, pbuf, &pn) == FHS_OK && pn == 8 && !std::memcmp(pbuf, "ssssssss", 8));
+        {   // a row fetched by encrypted index on the host (select_host.cpp): 640 characters in rows of 128 -- two groups, the
+            // second partial, one tree level and two rotates -- and the refusals
+            std::string table;
+            for (int r = 0; r < 5; r++) table += std::string(128, (char)('a' + r));
+            std::vector<uint32_t> tm(2 * 2048), tb(4 * 640), rm(2048), rb(4 * 128);
+            CHECK(fhs_public_encrypt_str(pk, table.data(), table.size(), 0, tm.data(), tb.data()) == FHS_OK);
+            const int bits = fhs_store_select_bits(640, 128);
+            CHECK(bits == 3 && fhs_store_select_bits(640, 96) == 0 && fhs_store_select_bits(128, 128) == 0);
+            std::vector<uint64_t> q(FHS_SELECT_QUERY_WORDS(bits));
+            CHECK(fhs_client_select_query(ck, 4, bits, q.data()) == FHS_OK && fhs_client_select_query(ck, 4, 0, q.data()) == FHS_ERR_ARG);
+            CHECK(fhs_store_select_host(q.data(), bits, tm.data(), tb.data(), 4 * 640, 128, rm.data(), rb.data()) == FHS_OK);
+            std::vector<uint64_t> row((size_t)128 * FHS_CHAR_WORDS);
+            std::vector<char> rbuf(129);
+            CHECK(fhs_expand_public_str(rm.data(), rb.data(), 128, 0, 128, row.data()) == FHS_OK);
+            CHECK(fhs_client_decrypt_str(ck, row.data(), 128, rbuf.data(), &pn) == FHS_OK && pn == 128 &&
+                  std::string(rbuf.data(), 128) == std::string(128, 'e'));
+            CHECK(fhs_store_select_host(q.data(), 2, tm.data(), tb.data(), 4 * 640, 128, rm.data(), rb.data()) == FHS_ERR_ARG);
+            CHECK(fhs_store_select_host(q.data(), bits, tm.data(), tb.data(), 4 * 640, 1024, rm.data(), rb.data()) == FHS_ERR_ARG);
+            CHECK(fhs_store_select_host(nullptr, bits, tm.data(), tb.data(), 4 * 640, 128, rm.data(), rb.data()) == FHS_ERR_ARG);
+        }
         {   // that compact string re-keyed to a second client, in place (rekey_host.cpp); the re-key key and its kind 7 file
             fhs_client *to = nullptr;
             CHECK(fhs_client_create_insecure_seeded(43, &to) == FHS_OK);
@@ -448,6 +468,15 @@ int main() {
         CHECK(fhs_char_sum_c2(c, hs[0], &c2) == FHS_OK && c2 == 1);
         CHECK(fhs_release(c, hs[0]) == FHS_OK);
         CHECK(fhs_store_stats(c, &n, nullptr, &bytes) == FHS_OK && n == 1 && bytes == 2 * 8192 + 16 * 600);
+        // select by encrypted index on the planner: 600 characters in rows of 8 (75 rows, 7 bits), bookkeeping only
+        std::vector<uint64_t> q(FHS_SELECT_QUERY_WORDS(7), 0);
+        uint64_t sel = 0;
+        uint32_t nk = 0;
+        CHECK(fhs_store_select(c, id2, 8, q.data(), 7, &sel) == FHS_OK && sel != 0 && sel != id2);
+        CHECK(fhs_store_info(c, sel, &n, &bytes) == FHS_OK && n == 8 && bytes == 8192 + 16 * 8);
+        CHECK(fhs_store_rekey_count(c, sel, &nk) == FHS_OK && nk == FHS_SELECT_REKEY_COST * 7);
+        CHECK(fhs_store_select(c, id2, 8, q.data(), 6, &sel) == FHS_ERR_ARG && sel == 0);
+        CHECK(fhs_store_select(c, id2, 7, q.data(), 7, &sel) == FHS_ERR_ARG && fhs_store_select(c, id2, 8, nullptr, 7, &sel) == FHS_ERR_ARG);
     }
     for (int r = 0; r < 2; r++) {
         // a compressed upload on the planner (handles only), then the all-at-once plan walked as rank r of 2 would:
