@@ -8,7 +8,8 @@ import random
 import numpy as np
 import pytest
 
-from ring_util import digits, glwe_phases, negacyclic
+from pack_model import node_dense as _node_schoolbook      # the schoolbook node, the key rounded to its grid first
+from ring_util import glwe_phases
 
 N = 2048
 GLWE_NOISE = 2.9403601535432533e-16          # client.cpp: GLWE noise as a fraction of the torus (packing key, fresh blocks)
@@ -27,32 +28,6 @@ def ck():
 
 def _ascii(rng, n):
     return "".join(chr(rng.randrange(1, 128)) for _ in range(n))
-
-
-def _automorphism(a, g):
-    idx = (np.arange(N, dtype=np.int64) * g) % (2 * N)
-    out = np.zeros(N, np.uint64)
-    out[idx % N] = np.where(idx >= N, np.uint64(0) - a, a)
-    return out
-
-
-def _node_schoolbook(key, lv, e, o):
-    """out = P + AutoKS_g(M): T = X^t O, P = E + T, M = E - T, g = 2^lv + 1, t = N >> lv; GLWEs as [2][N] (mask, body)"""
-    t, g = N >> lv, (1 << lv) + 1
-    kg = key.reshape(11, PACK_LEVELS, 2, N)[lv - 1]
-    T = np.empty_like(o)
-    for c in range(2):
-        T[c, t:] = o[c, :N - t]
-        T[c, :t] = np.uint64(0) - o[c, N - t:]
-    P, M = e + T, e - T
-    a1, b1 = _automorphism(M[0], g), _automorphism(M[1], g)
-    dig = digits(a1, PACK_LEVELS)
-    assert all(int(d.min()) >= -(1 << 15) and int(d.max()) < (1 << 15) for d in dig)
-    sm, sb = np.zeros(N, np.uint64), np.zeros(N, np.uint64)
-    for l in range(PACK_LEVELS):
-        sm += negacyclic(dig[l], kg[l, 0])
-        sb += negacyclic(dig[l], kg[l, 1])
-    return np.stack([P[0] - sm, P[1] + b1 - sb])
 
 
 def _predicted_pack_sigma():

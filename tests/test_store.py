@@ -78,11 +78,14 @@ def test_switch32_equals_numpy_in_every_word():
         m64 = rng.integers(0, 1 << 64, (g, N), dtype=np.uint64)
         b64 = rng.integers(0, 1 << 64, (g, N), dtype=np.uint64)
         m64[0, :4] = [0, (1 << 31) - 1, 1 << 31, (1 << 64) - 1]                  # the rounding's edges, the wrap to 0 included
+        m64[-1, 4:6] = [0xFFFFFFFF7FFFFFFF, 0xFFFFFFFF80000000]                  # ... and both sides of the wrap, in the last group
+        b64[-1, :4] = [0x000000007FFFFFFF, 0x0000000080000000, 0xFFFFFFFF7FFFFFFF, 0xFFFFFFFF80000000]   # the bodies' too
         c = pack_switch32(m64, b64, n_blocks)
         assert isinstance(c, CompactFheString) and len(c) == n_blocks // 4
         assert c.mask32.shape == (g, N) and c.body32.shape == (n_blocks,)
         assert np.array_equal(c.mask32, round32(m64)), n_blocks
-        assert list(c.mask32[0, :4]) == [0, 0, 1, 0]
+        assert list(c.mask32[0, :4]) == [0, 0, 1, 0] and list(c.mask32[-1, 4:6]) == [0xFFFFFFFF, 0]
+        assert list(c.body32[(g - 1) * N:(g - 1) * N + 4]) == [0, 1, 0xFFFFFFFF, 0]
         assert np.array_equal(c.body32, round32(b64).reshape(-1)[:n_blocks]), n_blocks   # group g's bodies start at 2048 g
     m32, b32 = pack_switch32(m64[:1], b64[:1], 3)                               # not whole characters: the raw arrays
     assert np.array_equal(m32, round32(m64[:1])) and np.array_equal(b32, round32(b64[0, :3]))
