@@ -15,6 +15,10 @@ PACK_KEY_WORDS = _K["FHS_PACK_KEY_WORDS"]
 REKEY_KEY_WORDS = _K["FHS_REKEY_KEY_WORDS"]
 SELECT_QUERY_BIT_WORDS = _K["FHS_SELECT_QUERY_BIT_WORDS"]       # u64 words of one index bit's GGSW
 SELECT_REKEY_COST = _K["FHS_SELECT_REKEY_COST"]
+SELECT_SEEDED_BIT_WORDS = _K["FHS_SELECT_SEEDED_BIT_WORDS"]     # body words of one index bit of a seeded query
+SELECT_FORM_FULL, SELECT_FORM_SEEDED = _K["FHS_SELECT_FORM_FULL"], _K["FHS_SELECT_FORM_SEEDED"]
+SELECT_MAX_BATCH = _K["FHS_SELECT_MAX_BATCH"]
+SELECT_BATCH_MAX_BYTES = _K["FHS_SELECT_BATCH_MAX_BYTES"]
 
 
 def _ptr(a):
@@ -157,6 +161,29 @@ class Context:
         self._check(self._L.fhs_debug_select_device(self._h, _ptr(query), bits, _ptr(mask32), _ptr(body32), n_blocks, row_chars,
                                                     _ptr(m_out), _ptr(b_out)))
         return m_out, b_out
+
+    def select_seeded_device(self, q, mask32, body32, n_blocks, row_chars):
+        """fhs_debug_select_seeded_device: select_device with a SeededSelectQuery."""
+        g = (n_blocks + PACK_GROUP - 1) // PACK_GROUP
+        mask32 = np.ascontiguousarray(mask32, np.uint32).reshape(g, POLY_N)
+        body32 = np.ascontiguousarray(body32, np.uint32).reshape(n_blocks)
+        m_out, b_out = np.zeros(POLY_N, np.uint32), np.zeros(4 * row_chars, np.uint32)
+        self._check(self._L.fhs_debug_select_seeded_device(self._h, _ptr(q.seed), _ptr(q.bodies), q.bits, _ptr(mask32),
+                                                           _ptr(body32), n_blocks, row_chars, _ptr(m_out), _ptr(b_out)))
+        return m_out, b_out
+
+    def select_query_device(self, query):
+        """fhs_debug_select_query_device: the conversion kernel alone on a full-form query (an array) or a
+        SeededSelectQuery -> the transform-domain doubles [bits][8][2 primes][2048]."""
+        if isinstance(query, SeededSelectQuery):
+            form, seed, words, bits = SELECT_FORM_SEEDED, _ptr(query.seed), query.bodies, query.bits
+        else:
+            words = np.ascontiguousarray(query, np.uint64)
+            assert words.size % SELECT_QUERY_BIT_WORDS == 0
+            form, seed, bits = SELECT_FORM_FULL, None, words.size // SELECT_QUERY_BIT_WORDS
+        out = np.zeros((bits, 8, 2, POLY_N), np.float64)
+        self._check(self._L.fhs_debug_select_query_device(self._h, form, seed, _ptr(words), bits, _ptr(out)))
+        return out
 
     def rekey_packed_device(self, mask64, body64, n_blocks):
         """fhs_debug_rekey_packed_device: the recipient download's kernel on raw 64-bit GLWEs of any block count ->
@@ -388,12 +415,18 @@ class MyClientKey:
             raise FhsError("fhs_client_rekey_key failed")
         return key
 
-    def select_query(self, index, n_chars, row_chars):
+    def select_query(self, index, n_chars, row_chars, seeded=False):
         """fhs_client_select_query: the bits of row `index` of a table of n_chars characters in rows of row_chars, as GGSW
-        ciphertexts under this client's key -> (query[bits][4][mask, body][2048] u64, bits); a fresh query per call."""
+        ciphertexts under this client's key -> (query[bits][4][mask, body][2048] u64, bits); a fresh query per call.
+        seeded=True: fhs_client_select_query_seeded -> SeededSelectQuery(seed, bodies[bits][4][2048], bits), half the size."""
         bits = select_bits(n_chars, row_chars)
         if bits == 0:
             raise ValueError("no table of %d characters in rows of %d can be selected from" % (n_chars, row_chars))
+        if seeded:
+            seed, bodies = np.zeros(8, np.uint32), np.empty((bits, 4, POLY_N), np.uint64)
+            if self._L.fhs_client_select_query_seeded(self._h, int(index), bits, _ptr(seed), _ptr(bodies)) != 0:
+                raise FhsError("fhs_client_select_query_seeded failed")
+            return SeededSelectQuery(seed, bodies, bits)
         query = np.empty((bits, 4, 2, POLY_N), np.uint64)
         if self._L.fhs_client_select_query(self._h, int(index), bits, _ptr(query)) != 0:
             raise FhsError("fhs_client_select_query failed")
@@ -901,6 +934,40 @@ def select_bits(n_chars, row_chars):
     return int(lib().fhs_store_select_bits(int(n_chars), int(row_chars)))
 
 
+class SeededSelectQuery:
+    """A select query in its seeded form: the public seed (8 u32 words) of the masks and bodies[bits][4][2048]."""
+
+    def __init__(self, seed, bodies, bits):
+        self.seed = np.ascontiguousarray(seed, np.uint32).reshape(8)
+        self.bodies = np.ascontiguousarray(bodies, np.uint64).reshape(int(bits), 4, POLY_N)
+        self.bits = int(bits)
+
+
+def expand_select_query(q):
+    """fhs_expand_select_query: the full form [bits][4][mask, body][2048] of a SeededSelectQuery (public data only)."""
+    out = np.empty((q.bits, 4, 2, POLY_N), np.uint64)
+    if lib().fhs_expand_select_query(_ptr(q.seed), _ptr(q.bodies), q.bits, _ptr(out)) != 0:
+        raise FhsError("fhs_expand_select_query failed")
+    return out
+
+
+def select_query_ntt_host(query):
+    """fhs_select_query_ntt_host: the host's conversion of a full-form query to the transform domain, the doubles
+    [bits][8][2 primes][2048] that Context.select_query_device must reproduce bit for bit."""
+    query = np.ascontiguousarray(query, np.uint64)
+    assert query.size % SELECT_QUERY_BIT_WORDS == 0
+    bits = query.size // SELECT_QUERY_BIT_WORDS
+    out = np.zeros((bits, 8, 2, POLY_N), np.float64)
+    if lib().fhs_select_query_ntt_host(_ptr(query), bits, _ptr(out)) != 0:
+        raise FhsError("fhs_select_query_ntt_host failed")
+    return out
+
+
+def select_batch_bytes(n_chars, row_chars, n):
+    """fhs_store_select_batch_bytes: workspace of a batch of n queries, 0 for a refused shape or n."""
+    return int(lib().fhs_store_select_batch_bytes(int(n_chars), int(row_chars), int(n)))
+
+
 def _select_args(query, mask32, body32, n_blocks):
     query = np.ascontiguousarray(query, np.uint64)
     assert query.size % SELECT_QUERY_BIT_WORDS == 0
@@ -1035,13 +1102,45 @@ class StoredString:
 
     def select(self, query, row_chars):
         """fhs_store_select: the row named by the encrypted index `query` (MyClientKey.select_query) of this entry read as
-        rows of row_chars characters -> a new StoredString of row_chars characters; this one is only read."""
+        rows of row_chars characters -> a new StoredString of row_chars characters; this one is only read.  A
+        SeededSelectQuery goes through fhs_store_select_seeded."""
+        eid = C.c_uint64(0)
+        ctx = self.sk.ctx
+        if isinstance(query, SeededSelectQuery):
+            ctx._check(ctx._L.fhs_store_select_seeded(ctx._h, self.id, int(row_chars), _ptr(query.seed), _ptr(query.bodies),
+                                                      query.bits, C.byref(eid)))
+            return StoredString(self.sk, eid.value)
         query = np.ascontiguousarray(query, np.uint64)
         assert query.size % SELECT_QUERY_BIT_WORDS == 0
-        eid = C.c_uint64(0)
-        self.sk.ctx._check(self.sk.ctx._L.fhs_store_select(self.sk.ctx._h, self.id, int(row_chars), _ptr(query),
-                                                           query.size // SELECT_QUERY_BIT_WORDS, C.byref(eid)))
+        ctx._check(ctx._L.fhs_store_select(ctx._h, self.id, int(row_chars), _ptr(query),
+                                           query.size // SELECT_QUERY_BIT_WORDS, C.byref(eid)))
         return StoredString(self.sk, eid.value)
+
+    def select_many(self, queries, row_chars):
+        """fhs_store_select_batch: one row per query (all full-form arrays, or all SeededSelectQuery) from one conversion
+        launch and one CMux launch per tree level and rotate bit -> a list of new StoredStrings, in the queries' order."""
+        queries = list(queries)
+        n = len(queries)
+        seeded = n > 0 and isinstance(queries[0], SeededSelectQuery)
+        if any(isinstance(q, SeededSelectQuery) != seeded for q in queries):
+            raise ValueError("select_many: the queries of one call have one form")
+        if seeded:
+            words = [q.bodies for q in queries]
+            bits = {q.bits for q in queries}
+            seeds = np.ascontiguousarray(np.stack([q.seed for q in queries]), np.uint32)
+        else:
+            words = [np.ascontiguousarray(q, np.uint64) for q in queries]
+            assert all(w.size % SELECT_QUERY_BIT_WORDS == 0 for w in words)
+            bits = {w.size // SELECT_QUERY_BIT_WORDS for w in words}
+            seeds = None
+        if len(bits) > 1:
+            raise ValueError("select_many: the queries of one call have one bit count")
+        table = (C.c_void_p * max(1, n))(*[w.ctypes.data for w in words])
+        ids = (C.c_uint64 * max(1, n))()
+        ctx = self.sk.ctx
+        ctx._check(ctx._L.fhs_store_select_batch(ctx._h, self.id, int(row_chars), SELECT_FORM_SEEDED if seeded else SELECT_FORM_FULL,
+                                                 None if seeds is None else _ptr(seeds), table, n, bits.pop() if bits else 0, ids))
+        return [StoredString(self.sk, ids[i]) for i in range(n)]
 
     @property
     def rekeys(self):

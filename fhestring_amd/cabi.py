@@ -34,7 +34,7 @@ def parse_type(words, stars, known):
 
 
 def parse_param(p, known):
-    p = p.strip()
+    p = re.sub(r"\*\s*const\s*\*", "**", p.strip())          # `const T *const *x`: an array of pointers that is only read
     m = re.match(r"^(.*?)(\**)\s*([A-Za-z_]\w*)\s*((?:\[[^\]]*\])*)$", p.replace(" *", "*").replace("* ", "*"))
     _need(m, p)
     stars = len(m.group(2)) + (1 if m.group(4) else 0)       # `uint32_t key[8]` decays to a pointer

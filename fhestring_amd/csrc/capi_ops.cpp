@@ -344,17 +344,64 @@ int fhs_debug_rekey_device(fhs_ctx *c, const void *mask32, const void *body32, s
                               static_cast<uint32_t *>(mask32_out), static_cast<uint32_t *>(body32_out));
 }
 // ---- string store: select by encrypted index ----
+namespace {
+using SelectQueries = Engine::SelectQueries;
+// what fhs_store_select_batch refuses before the engine sees it: a form, a count or a pointer
+bool batch_args_ok(int form, const uint32_t *seeds, const uint64_t *const *queries, size_t n) {
+    if (form != FHS_SELECT_FORM_FULL && form != FHS_SELECT_FORM_SEEDED) return false;
+    if (!queries || n == 0 || n > (size_t)FHS_SELECT_MAX_BATCH || (form == FHS_SELECT_FORM_SEEDED && !seeds)) return false;
+    for (size_t i = 0; i < n; i++)
+        if (!queries[i]) return false;
+    return true;
+}
+}  // namespace
 int fhs_store_select(fhs_ctx *c, uint64_t id, size_t row_chars, const uint64_t *query, int bits, uint64_t *id_out) {
     if (!c || !id_out) return bad(c);
     *id_out = 0;
     if (!query) return bad(c);
-    return c->eng.store_select(id, row_chars, query, bits, id_out);
+    return c->eng.store_select(id, row_chars, SelectQueries{FHS_SELECT_FORM_FULL, nullptr, &query, 1}, bits, false, id_out);
+}
+int fhs_store_select_seeded(fhs_ctx *c, uint64_t id, size_t row_chars, const uint32_t seed[8], const uint64_t *bodies, int bits,
+                            uint64_t *id_out) {
+    if (!c || !id_out) return bad(c);
+    *id_out = 0;
+    if (!seed || !bodies) return bad(c);
+    return c->eng.store_select(id, row_chars, SelectQueries{FHS_SELECT_FORM_SEEDED, seed, &bodies, 1}, bits, false, id_out);
+}
+int fhs_store_select_batch(fhs_ctx *c, uint64_t id, size_t row_chars, int form, const uint32_t *seeds,
+                           const uint64_t *const *queries, size_t n, int bits, uint64_t *ids_out) {
+    if (!c || !ids_out) return bad(c);
+    for (size_t i = 0; i < n && i < (size_t)FHS_SELECT_MAX_BATCH; i++) ids_out[i] = 0;
+    if (!batch_args_ok(form, seeds, queries, n)) return bad(c);
+    return c->eng.store_select(id, row_chars, SelectQueries{form, seeds, queries, n}, bits, true, ids_out);
+}
+size_t fhs_store_select_batch_bytes(size_t n_chars, size_t row_chars, size_t n) {
+    return Engine::select_batch_bytes(n_chars, row_chars, n);
 }
 int fhs_debug_select_device(fhs_ctx *c, const uint64_t *query, int bits, const void *mask32, const void *body32, size_t n_blocks,
                             size_t row_chars, void *mask32_out, void *body32_out) {
     if (!c || !query || !mask32 || !body32 || !mask32_out || !body32_out) return bad(c);
-    return c->eng.debug_select(query, bits, static_cast<const uint32_t *>(mask32), static_cast<const uint32_t *>(body32), n_blocks,
-                               row_chars, static_cast<uint32_t *>(mask32_out), static_cast<uint32_t *>(body32_out));
+    return c->eng.debug_select(SelectQueries{FHS_SELECT_FORM_FULL, nullptr, &query, 1}, bits, static_cast<const uint32_t *>(mask32),
+                               static_cast<const uint32_t *>(body32), n_blocks, row_chars, static_cast<uint32_t *>(mask32_out),
+                               static_cast<uint32_t *>(body32_out));
+}
+int fhs_debug_select_seeded_device(fhs_ctx *c, const uint32_t seed[8], const uint64_t *bodies, int bits, const void *mask32,
+                                   const void *body32, size_t n_blocks, size_t row_chars, void *mask32_out, void *body32_out) {
+    if (!c || !seed || !bodies || !mask32 || !body32 || !mask32_out || !body32_out) return bad(c);
+    return c->eng.debug_select(SelectQueries{FHS_SELECT_FORM_SEEDED, seed, &bodies, 1}, bits, static_cast<const uint32_t *>(mask32),
+                               static_cast<const uint32_t *>(body32), n_blocks, row_chars, static_cast<uint32_t *>(mask32_out),
+                               static_cast<uint32_t *>(body32_out));
+}
+int fhs_debug_select_query_device(fhs_ctx *c, int form, const uint32_t seed[8], const uint64_t *words, int bits, double *out) {
+    if (!c || !words || !out || (form != FHS_SELECT_FORM_FULL && form != FHS_SELECT_FORM_SEEDED) ||
+        (form == FHS_SELECT_FORM_SEEDED && !seed))
+        return bad(c);
+    return c->eng.debug_select_query(SelectQueries{form, form == FHS_SELECT_FORM_SEEDED ? seed : nullptr, &words, 1}, bits, out);
+}
+int fhs_select_query_ntt_host(const uint64_t *query, int bits, double *out) {
+    if (!query || !out || bits < 1 || bits > 24) return FHS_ERR_ARG;
+    convert_polys_to_ntt(query, out, (size_t)bits * SELECT_BIT_POLYS, BSK_QUANT_BITS);
+    return FHS_OK;
 }
 // ---- packed result download under a recipient's key ----
 int fhs_download_string_packed_for(fhs_ctx *c, const fhs_char_t *chars, size_t n, void *mask16, void *body16, uint64_t *mask64,

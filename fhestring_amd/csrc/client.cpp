@@ -52,6 +52,7 @@ struct fhs_client {
     std::mutex pk_mu;
     std::atomic<uint64_t> rekey_calls{0};   // re-key keys made INTO this client (fhs_client_rekey_key): one ChaCha key each
     std::atomic<uint64_t> select_calls{0};  // select queries made by this client (fhs_client_select_query): one ChaCha key each
+    std::atomic<uint64_t> sselect_calls{0}; // seeded select queries (fhs_client_select_query_seeded): a seed and noise streams each
 };
 
 namespace {
@@ -333,8 +334,10 @@ constexpr uint64_t SEED_TAG_STR = 0x5345454453545231ull, SEED_TAG_KEY = 0x534545
 // Secret noise streams (DOM_NOISE) of compressed objects, disjoint from every other range of the client:
 //   7 (encrypt_char), 1000 + i (BSK), 100000 + i (KSK), 2000000 + g (pair key), STR_STREAM_BASE + (call << 24) + i
 //   (classic strings, [2^62, 2^63)).  Compressed strings: CSTR_STREAM_BASE + (call << 24) + character, [2^63, 2^63 + 2^62)
-//   for call < 2^38; the compressed server key: 4000000 + i (BSK, key bit i), 5000000 + i (KSK, row i).
+//   for call < 2^38; the compressed server key: 4000000 + i (BSK, key bit i), 5000000 + i (KSK, row i).  Seeded select
+//   queries: SSEL_NOISE_BASE + (call << 7) + 4 bit + row, [2^63 + 2^62, 2^64) for call < 2^55.
 constexpr uint64_t CSTR_STREAM_BASE = 1ull << 63;
+constexpr uint64_t SSEL_NOISE_BASE = (1ull << 63) + (1ull << 62);
 constexpr uint64_t CBSK_NOISE_BASE = 4000000, CKSK_NOISE_BASE = 5000000;
 
 // sum_j draw_j * s_j over n draws of `mask`, s binary; the draws are streamed through a small buffer, never stored whole
@@ -668,6 +671,31 @@ bool select_query(fhs_client *ck, uint64_t index, int bits, uint64_t *out) {
     return true;
 }
 
+// The seeded form: the same rows with the masks drawn from the PUBLIC seed (domain FHS_DOM_SEEDED_SELECT, stream 4 k +
+// row) and only the bodies kept.  The seed is public, so the noise must not come from it: it is drawn from the client's
+// secret key, streams SSEL_NOISE_BASE + (call << 7) + 4 k + row (4 k + row < 96), a range of its own beside those listed
+// above keygen_compressed.  The call counter is this form's own: select_calls, and with it every full-form query of an
+// insecure seeded client, stays where it was.
+constexpr uint64_t SEED_TAG_SELECT_SEEDED = 0x5345454453454c32ull;
+bool select_query_seeded(fhs_client *ck, uint64_t index, int bits, uint32_t seed_out[8], uint64_t *bodies) {
+    const uint64_t call = ck->sselect_calls.fetch_add(1);
+    ChaKey seed;
+    if (!public_seed(ck, SEED_TAG_SELECT_SEEDED, call, seed)) return false;
+    std::vector<uint64_t> msg(POLY_N), mask(POLY_N);
+    for (int k = 0; k < bits; k++) {
+        const uint64_t bit = (index >> k) & 1;
+        for (int row = 0; row < 4; row++) {
+            for (int n = 0; n < POLY_N; n++)
+                msg[n] = row < 2 ? (uint64_t)0 - bit * ck->glwe_sk[n] : (n == 0 ? bit : 0);
+            Rng gm(seed, 4 * k + row, FHS_DOM_SEEDED_SELECT), e(ck->key, SSEL_NOISE_BASE + (call << 7) + 4 * k + row, DOM_NOISE);
+            keyswitch_key_row(gm, e, ck->glwe_sk.data(), msg.data(), 64 - 16 * ((row & 1) + 1), mask.data(),
+                              bodies + ((size_t)k * 4 + row) * POLY_N);
+        }
+    }
+    for (int i = 0; i < 8; i++) seed_out[i] = seed.w[i];
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -675,6 +703,23 @@ extern "C" {
 int fhs_client_select_query(fhs_client *ck, uint64_t index, int bits, uint64_t *query_out) {
     if (!ck || !query_out || bits < 1 || bits > 24) return FHS_ERR_ARG;
     return select_query(ck, index, bits, query_out) ? FHS_OK : FHS_ERR_STATE;
+}
+
+int fhs_client_select_query_seeded(fhs_client *ck, uint64_t index, int bits, uint32_t seed_out[8], uint64_t *bodies) {
+    if (!ck || !seed_out || !bodies || bits < 1 || bits > 24) return FHS_ERR_ARG;
+    return select_query_seeded(ck, index, bits, seed_out, bodies) ? FHS_OK : FHS_ERR_STATE;
+}
+
+int fhs_expand_select_query(const uint32_t seed[8], const uint64_t *bodies, int bits, uint64_t *query_out) {
+    if (!seed || !bodies || !query_out || bits < 1 || bits > 24) return FHS_ERR_ARG;
+    const ChaKey k = seed_key(seed);
+    for (int r = 0; r < 4 * bits; r++) {                          // GGSW row r = 4 bit + row
+        uint64_t *mask = query_out + (size_t)r * 2 * POLY_N;
+        Rng g(k, (uint64_t)r, FHS_DOM_SEEDED_SELECT);
+        for (int n = 0; n < POLY_N; n++) mask[n] = g.next() & GRID_MASK;
+        std::memcpy(mask + POLY_N, bodies + (size_t)r * POLY_N, POLY_N * 8);
+    }
+    return FHS_OK;
 }
 
 }  // extern "C"

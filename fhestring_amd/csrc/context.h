@@ -108,9 +108,10 @@ class Context {
     DevBuf dig_buf;                  // keyswitch digits of the current batch
     DevBuf ks_buf, ms_buf, in_buf, out_buf, lutidx_buf, luts_buf, tab_buf;
     DevBuf pack_ws[2], pack_tab, pack_out;   // packing: ping-pong tree levels, leaf table, u16 result (allocated on first use, kept)
-    // select by encrypted index (select_kernels.hip), allocated on first use and kept, grow-only: the query as residues
-    // [bits][4][2 cols][2 primes][2048] and the two buffers the tree's levels alternate between, ceil(G / 2) and
-    // ceil(G / 4) GLWEs of 32-bit words for the largest entry of G groups so far
+    // select by encrypted index (select_kernels.hip), allocated on first use and kept, grow-only: the queries of a call
+    // as residues [queries][bits][4][2 cols][2 primes][2048], written by select_query_to_ntt_kernel, and the two buffers
+    // the tree's levels alternate between, ceil(G / 2) and ceil(G / 4) GLWEs of 32-bit words per query for the largest
+    // (queries x entry of G groups) so far
     DevBuf sel_query, sel_ws[2];
     bool select_prepared = false;    // prepare_device_for_select has run on this device
     KernelTimer timer;

@@ -208,10 +208,23 @@ class Engine {
     // launch per tree level and per rotate bit on the context's stream, no bootstrap, no pool block, no key.  The result's
     // blocks take the maxima of figure and cycles over the rows, one fresh rotation group if any candidate has one, and
     // rekeys + SELECT_REKEY_COST per launch.  A planner does the bookkeeping only.
-    int store_select(uint64_t id, size_t row_chars, const uint64_t *query, int bits, uint64_t *id_out);
-    // diagnostic: the same launches on host words, the arguments of fhs_store_select_host
-    int debug_select(const uint64_t *query, int bits, const uint32_t *mask32, const uint32_t *body32, size_t n_blocks,
+    // q holds n queries of one form: n new entries with consecutive ids in ids_out[n], each with
+    // bookkeeping of its own, from one conversion launch and one CMux launch per level and bit.  Atomic: an error creates
+    // nothing.  batch: the call is fhs_store_select_batch, whose workspace is limited (FHS_SELECT_BATCH_MAX_BYTES).
+    struct SelectQueries {
+        int form;                        // FHS_SELECT_FORM_*
+        const uint32_t *seeds;           // SEEDED: [n][8]
+        const uint64_t *const *queries;  // n pointers: full words, or bodies
+        size_t n;
+    };
+    int store_select(uint64_t id, size_t row_chars, const SelectQueries &q, int bits, bool batch, uint64_t *ids_out);
+    // converted queries plus both level buffers of n queries, bytes; 0 for a refused shape or n
+    static size_t select_batch_bytes(size_t n_chars, size_t row_chars, size_t n);
+    // diagnostic: the same launches on host words, the arguments of fhs_store_select_host (one query)
+    int debug_select(const SelectQueries &q, int bits, const uint32_t *mask32, const uint32_t *body32, size_t n_blocks,
                      size_t row_chars, uint32_t *mask_out, uint32_t *body_out);
+    // diagnostic: the conversion kernel alone on one query
+    int debug_select_query(const SelectQueries &q, int bits, double *out);
     // diagnostic: the kernel on host words of any block count; the outputs may be the inputs
     int debug_rekey(const uint32_t *mask32, const uint32_t *body32, size_t n_blocks, uint32_t *mask_out, uint32_t *body_out);
     // diagnostic: the recipient download's kernel alone on host words, mask64 / body64 [ceil(n_blocks / 2048)][2048]
@@ -384,9 +397,12 @@ class Engine {
                            size_t n_blocks);
     // one launch of the recipient download's kernel: level-11 GLWEs [groups][2][2048] -> 16-bit words under the new key
     hipError_t rekey_packed_words(const uint64_t *d_glwe, uint16_t *d_mask16, uint16_t *d_body16, size_t n_blocks);
-    // the select's launches from device words of the entry layout into d_mask_out[2048] | d_body_out[4 row_chars]
-    hipError_t select_words(const uint64_t *query, const uint32_t *d_mask, const uint32_t *d_body, size_t n_blocks,
-                            const SelectShape &sh, uint32_t *d_mask_out, uint32_t *d_body_out);
+    // the select's launches from device words of the entry layout, all queries of q per launch
+    // dst[y] (host array of device pointers): mask[2048] | body[4 row_chars] of query y's result
+    hipError_t select_words(const SelectQueries &q, const uint32_t *d_mask, const uint32_t *d_body, size_t n_blocks,
+                            const SelectShape &sh, uint32_t *const *dst);
+    // upload and conversion into ctx.sel_query; dst (may be null) travels along, *d_table is its place on the device
+    hipError_t select_queries_to_ntt(const SelectQueries &q, int bits, uint32_t *const *dst, uint32_t *const **d_table);
     hipError_t pack_tree_pass(const Bid *b, size_t n, size_t groups);
     std::map<uint64_t, StoreEntry> store_;
     uint64_t store_ids_ = 0;             // ids handed out: never reused inside a context

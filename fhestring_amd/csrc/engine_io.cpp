@@ -687,20 +687,17 @@ int Engine::debug_rekey(const uint32_t *mask32, const uint32_t *body32, size_t n
 }
 
 // ---- string store: select by encrypted index ---------------------------------------------------------------------------
-// The query goes to the transform domain on the host (convert_polys_to_ntt writes straight into the pinned staging
-// buffer), crosses the bus as one table pass and lands in ctx.sel_query; then one launch per tree level and per rotate
-// bit.  Launch k reads the entry (k = 0) or ctx.sel_ws[(k - 1) & 1] and writes ctx.sel_ws[k & 1] or, the last one, the
-// caller's destination: never in place.  The three context buffers only grow, behind a drained stream (queued launches
-// of an earlier select still read them).
-hipError_t Engine::select_words(const uint64_t *query, const uint32_t *d_mask, const uint32_t *d_body, size_t n_blocks,
-                                const SelectShape &sh, uint32_t *d_mask_out, uint32_t *d_body_out) {
-    const size_t n_polys = (size_t)sh.bits * SELECT_BIT_POLYS, q_words = n_polys * 2 * POLY_N;
-    const size_t ws_nodes[2] = {std::max<size_t>(1, (sh.groups + 1) / 2), std::max<size_t>(1, (sh.groups + 3) / 4)};
-    const size_t glwe_bytes = (size_t)2 * POLY_N * sizeof(uint32_t);
-    if (ctx.sel_query.cap < q_words * 8 || ctx.sel_ws[0].cap < ws_nodes[0] * glwe_bytes || ctx.sel_ws[1].cap < ws_nodes[1] * glwe_bytes) {
+// The queries of a call cross the bus as they are -- full words, or seeds and bodies -- in one table pass of the pinned
+// staging buffer, the pointer table of the destinations behind them; select_query_to_ntt_kernel reads the mirror and
+// writes ctx.sel_query (stream order keeps the mirror until then: every later pass copies on the same stream).
+hipError_t Engine::select_queries_to_ntt(const SelectQueries &q, int bits, uint32_t *const *dst, uint32_t *const **d_table) {
+    const size_t polys = (size_t)bits * SELECT_BIT_POLYS, n_polys = q.n * polys;
+    const size_t per_query = (q.form == FHS_SELECT_FORM_SEEDED ? polys / 2 : polys) * POLY_N;
+    const size_t seed_words = q.form == FHS_SELECT_FORM_SEEDED ? q.n * 4 : 0, table_words = dst ? q.n : 0;
+    const size_t total = q.n * per_query + seed_words + table_words;
+    if (ctx.sel_query.cap < n_polys * 2 * POLY_N * 8) {
         hipError_t e = hipStreamSynchronize(ctx.stream);
-        if (e == hipSuccess) e = ctx.sel_query.reserve(q_words * 8);
-        for (int k = 0; k < 2 && e == hipSuccess; k++) e = ctx.sel_ws[k].reserve(ws_nodes[k] * glwe_bytes);
+        if (e == hipSuccess) e = ctx.sel_query.reserve(n_polys * 2 * POLY_N * 8);
         if (e != hipSuccess) return e;
     }
     if (!ctx.select_prepared) {
@@ -708,31 +705,71 @@ hipError_t Engine::select_words(const uint64_t *query, const uint32_t *d_mask, c
         ctx.select_prepared = true;
     }
     size_t at = 0;
-    if (!xfer_.ensure((q_words + BIG_CT) / (BIG_CT + 1), ctx.stream) || !xfer_.begin_table_pass(q_words, at, ctx.stream))
+    if (!xfer_.ensure((total + BIG_CT) / (BIG_CT + 1), ctx.stream) || !xfer_.begin_table_pass(total, at, ctx.stream))
         return hipErrorOutOfMemory;
-    convert_polys_to_ntt(query, reinterpret_cast<double *>(xfer_.pin() + at), n_polys, BSK_QUANT_BITS);
-    hipError_t e = xfer_.copy_up(at, q_words, ctx.stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx.sel_query.ptr, xfer_.dev() + at, q_words * 8, hipMemcpyDeviceToDevice, ctx.stream);
+    uint64_t *pin = xfer_.pin() + at;
+    for (size_t i = 0; i < q.n; i++) std::memcpy(pin + i * per_query, q.queries[i], per_query * 8);
+    if (seed_words) std::memcpy(pin + q.n * per_query, q.seeds, seed_words * 8);
+    if (table_words) std::memcpy(pin + q.n * per_query + seed_words, dst, table_words * 8);
+    hipError_t e = xfer_.copy_up(at, total, ctx.stream);
+    if (e != hipSuccess) return e;
+    uint64_t *dev = xfer_.dev() + at;
+    SelectQueryParams p{};
+    p.words = dev;
+    p.seeds = seed_words ? reinterpret_cast<const uint32_t *>(dev + q.n * per_query) : nullptr;
+    p.n_polys = (uint32_t)n_polys; p.query_polys = (uint32_t)polys; p.quant_bits = BSK_QUANT_BITS;
+    p.out = ctx.sel_query.as<double>(); p.tw = ctx.tw;
+    if (d_table) *d_table = reinterpret_cast<uint32_t *const *>(dev + q.n * per_query + seed_words);
+    return launch_select_query_to_ntt(p, ctx.stream);
+}
+
+// Then one launch per tree level and per rotate bit, every one over all q.n queries.  Launch k reads the entry (k = 0,
+// every query the same words) or ctx.sel_ws[(k - 1) & 1] and writes ctx.sel_ws[k & 1] -- query y's nodes at y x (the
+// level's nodes) GLWEs -- or, the last one, the destinations dst[y] = mask[2048] | body: never in place.  The three
+// context buffers only grow, behind a drained stream (queued launches of an earlier select still read them).
+hipError_t Engine::select_words(const SelectQueries &q, const uint32_t *d_mask, const uint32_t *d_body, size_t n_blocks,
+                                const SelectShape &sh, uint32_t *const *dst) {
+    const size_t ws_nodes[2] = {q.n * select_ws_nodes(sh, 0), q.n * select_ws_nodes(sh, 1)};
+    const size_t glwe_bytes = (size_t)2 * POLY_N * sizeof(uint32_t);
+    if (ctx.sel_ws[0].cap < ws_nodes[0] * glwe_bytes || ctx.sel_ws[1].cap < ws_nodes[1] * glwe_bytes) {
+        hipError_t e = hipStreamSynchronize(ctx.stream);
+        for (int k = 0; k < 2 && e == hipSuccess; k++) e = ctx.sel_ws[k].reserve(ws_nodes[k] * glwe_bytes);
+        if (e != hipSuccess) return e;
+    }
+    uint32_t *const *d_table = nullptr;
+    hipError_t e = select_queries_to_ntt(q, sh.bits, dst, &d_table);
 
     SelectCmuxParams p{};
     p.query_ntt = ctx.sel_query.as<double>(); p.tw = ctx.tw;
+    p.queries = (uint32_t)q.n; p.query_stride = (size_t)sh.bits * SELECT_BIT_POLYS * 2 * POLY_N;
     p.src_mask = d_mask; p.src_body = d_body; p.src_nodes = (uint32_t)sh.groups; p.src_body_total = (uint32_t)n_blocks;
+    p.src_stride = 0;
     const int launches = sh.tree_levels + sh.rot_bits;
     for (int k = 0; k < launches && e == hipSuccess; k++) {
         const bool tree = k < sh.tree_levels, last = k == launches - 1;
         const uint32_t out_nodes = tree ? (p.src_nodes + 1) / 2 : 1u;
         p.bit = tree ? sh.rot_bits + k : k - sh.tree_levels;
         p.rotate = tree ? 0u : (uint32_t)(sh.row_blocks << p.bit);
-        p.dst_mask = last ? d_mask_out : ctx.sel_ws[k & 1].as<uint32_t>();
-        p.dst_body = last ? d_body_out : p.dst_mask + (size_t)out_nodes * POLY_N;
+        p.dst_table = last ? d_table : nullptr;
+        p.dst_mask = last ? nullptr : ctx.sel_ws[k & 1].as<uint32_t>();
+        p.dst_body = last ? nullptr : p.dst_mask + (size_t)out_nodes * POLY_N;
+        p.dst_stride = last ? 0 : (size_t)out_nodes * 2 * POLY_N;
         p.store_body = last ? (uint32_t)sh.row_blocks : (uint32_t)SELECT_GROUP;
         e = launch_select_cmux(p, ctx.stream);
-        p.src_mask = p.dst_mask; p.src_body = p.dst_body; p.src_nodes = out_nodes; p.src_body_total = out_nodes * SELECT_GROUP;
+        p.src_mask = p.dst_mask; p.src_body = p.dst_body; p.src_stride = p.dst_stride;
+        p.src_nodes = out_nodes; p.src_body_total = out_nodes * SELECT_GROUP;
     }
     return e;
 }
 
-int Engine::store_select(uint64_t id, size_t row_chars, const uint64_t *query, int bits, uint64_t *id_out) {
+size_t Engine::select_batch_bytes(size_t n_chars, size_t row_chars, size_t n) {
+    SelectShape sh;
+    if (n == 0 || n > (size_t)FHS_SELECT_MAX_BATCH || !select_shape(n_chars, row_chars, sh)) return 0;
+    return n * ((size_t)sh.bits * SELECT_BIT_POLYS * 2 * POLY_N * sizeof(double) +
+                (select_ws_nodes(sh, 0) + select_ws_nodes(sh, 1)) * 2 * POLY_N * sizeof(uint32_t));
+}
+
+int Engine::store_select(uint64_t id, size_t row_chars, const SelectQueries &q, int bits, bool batch, uint64_t *ids_out) {
     auto it = store_.find(id);
     if (it == store_.end()) return ctx.fail(-1, "string store: unknown entry id");
     const StoreEntry &src = it->second;
@@ -740,53 +777,67 @@ int Engine::store_select(uint64_t id, size_t row_chars, const uint64_t *query, i
     if ((src.n_blocks & 3) || !select_shape(src.n_blocks / 4, row_chars, sh))
         return ctx.fail(-1, "string store: select needs rows of a power of two of 1..512 characters, a whole number of them, at least two");
     if (bits != sh.bits) return ctx.fail(-1, "string store: the query's bit count is not fhs_store_select_bits of this shape");
+    if (q.n == 0 || q.n > (size_t)FHS_SELECT_MAX_BATCH) return ctx.fail(-1, "string store: a batch is 1..FHS_SELECT_MAX_BATCH queries");
     if (!planner && !ctx.d_tables)
         return ctx.fail(-3, "string store: select needs the transform tables that the first fhs_load_server_key uploads");
     const int rekeys = src.rekeys + SELECT_REKEY_COST * (sh.tree_levels + sh.rot_bits);
     if (rekeys > STORE_MAX_REKEYS)
         return ctx.fail(-4, "string store: the selected entry would exceed FHS_STORE_MAX_REKEYS re-keys' worth of noise");
-    // block j of the result: the maxima over block j of every row; one fresh rotation group if any candidate has one
-    StoreEntry dst;
-    dst.n_blocks = sh.row_blocks;
-    dst.var.assign(sh.row_blocks, 1); dst.cycles.assign(sh.row_blocks, 0); dst.rot.assign(sh.row_blocks, 0);
-    dst.rekeys = (uint8_t)rekeys;
+    if (batch && select_batch_bytes(src.n_blocks / 4, row_chars, q.n) > FHS_SELECT_BATCH_MAX_BYTES)
+        return ctx.fail(-4, "string store: the batch's workspace would exceed FHS_SELECT_BATCH_MAX_BYTES");
+    // block j of a result: the maxima over block j of every row; one fresh rotation group if any candidate has one
+    std::vector<StoreEntry> dst(q.n);
+    StoreEntry &first = dst[0];
+    first.n_blocks = sh.row_blocks;
+    first.var.assign(sh.row_blocks, 1); first.cycles.assign(sh.row_blocks, 0); first.rot.assign(sh.row_blocks, 0);
+    first.rekeys = (uint8_t)rekeys;
     std::vector<uint8_t> grouped(sh.row_blocks, 0);
     bool any = false;
     for (size_t row = 0; row < sh.rows; row++)
         for (size_t j = 0; j < sh.row_blocks; j++) {
             const size_t t = row * sh.row_blocks + j;
-            dst.var[j] = std::max(dst.var[j], src.var[t]);
-            dst.cycles[j] = std::max(dst.cycles[j], src.cycles[t]);
+            first.var[j] = std::max(first.var[j], src.var[t]);
+            first.cycles[j] = std::max(first.cycles[j], src.cycles[t]);
             if (src.rot[t]) grouped[j] = 1, any = true;
         }
+    for (size_t i = 1; i < q.n; i++) {
+        dst[i].n_blocks = first.n_blocks; dst[i].var = first.var; dst[i].cycles = first.cycles; dst[i].rot = first.rot;
+        dst[i].rekeys = first.rekeys;
+    }
     if (!planner) {
         (void)hipSetDevice(ctx.device);
-        hipError_t e = dst.buf.reserve_exact(dst.bytes());
+        hipError_t e = hipSuccess;
+        std::vector<uint32_t *> out(q.n);
+        for (size_t i = 0; i < q.n && e == hipSuccess; i++) {
+            e = dst[i].buf.reserve_exact(dst[i].bytes());
+            out[i] = dst[i].buf.as<uint32_t>();
+        }
         if (e == hipSuccess)
-            e = select_words(query, src.buf.as<uint32_t>(), src.buf.as<uint32_t>() + src.groups() * POLY_N, src.n_blocks, sh,
-                             dst.buf.as<uint32_t>(), dst.buf.as<uint32_t>() + POLY_N);
+            e = select_words(q, src.buf.as<uint32_t>(), src.buf.as<uint32_t>() + src.groups() * POLY_N, src.n_blocks, sh, out.data());
         if (e != hipSuccess) {
-            (void)hipStreamSynchronize(ctx.stream);                  // before dst.buf goes: a launch may be queued
+            (void)hipStreamSynchronize(ctx.stream);                  // before the new buffers go: a launch may be queued
             return ctx.hip_fail(e, "string store: select");
         }
     }
-    if (any) {
-        const uint32_t fresh = ++rot_counter_ ? rot_counter_ : ++rot_counter_;
-        for (size_t j = 0; j < sh.row_blocks; j++)
-            if (grouped[j]) dst.rot[j] = fresh;
+    for (size_t i = 0; i < q.n; i++) {
+        if (any) {                                                   // every result its own group: they are not correlated
+            const uint32_t fresh = ++rot_counter_ ? rot_counter_ : ++rot_counter_;
+            for (size_t j = 0; j < sh.row_blocks; j++)
+                if (grouped[j]) dst[i].rot[j] = fresh;
+        }
+        const uint64_t nid = ++store_ids_;
+        store_.emplace(nid, std::move(dst[i]));
+        ids_out[i] = nid;
     }
-    const uint64_t nid = ++store_ids_;
-    store_.emplace(nid, std::move(dst));
-    *id_out = nid;
     return 0;
 }
 
 // Diagnostic: the same launches on raw host words, through a scratch allocation of the entry layout.
-int Engine::debug_select(const uint64_t *query, int bits, const uint32_t *mask32, const uint32_t *body32, size_t n_blocks,
+int Engine::debug_select(const SelectQueries &q, int bits, const uint32_t *mask32, const uint32_t *body32, size_t n_blocks,
                          size_t row_chars, uint32_t *mask_out, uint32_t *body_out) {
     if (planner) return ctx.fail(-3, "planner context: nothing is computed");
     SelectShape sh;
-    if ((n_blocks & 3) || !select_shape(n_blocks / 4, row_chars, sh) || bits != sh.bits)
+    if ((n_blocks & 3) || !select_shape(n_blocks / 4, row_chars, sh) || bits != sh.bits || q.n != 1)
         return ctx.fail(-1, "select (diagnostic): a refused shape or bit count");
     if (!ctx.d_tables) return ctx.fail(-3, "select needs the transform tables that the first fhs_load_server_key uploads");
     (void)hipSetDevice(ctx.device);
@@ -796,12 +847,27 @@ int Engine::debug_select(const uint64_t *query, int bits, const uint32_t *mask32
     uint32_t *d_mask = buf.as<uint32_t>(), *d_body = d_mask + mask_words, *d_mask_out = d_body + n_blocks, *d_body_out = d_mask_out + POLY_N;
     if (e == hipSuccess) e = hipMemcpyAsync(d_mask, mask32, mask_words * 4, hipMemcpyHostToDevice, ctx.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_body, body32, n_blocks * 4, hipMemcpyHostToDevice, ctx.stream);
-    if (e == hipSuccess) e = select_words(query, d_mask, d_body, n_blocks, sh, d_mask_out, d_body_out);
+    if (e == hipSuccess) e = select_words(q, d_mask, d_body, n_blocks, sh, &d_mask_out);
     if (e == hipSuccess) e = hipMemcpyAsync(mask_out, d_mask_out, POLY_N * 4, hipMemcpyDeviceToHost, ctx.stream);
     if (e == hipSuccess) e = hipMemcpyAsync(body_out, d_body_out, sh.row_blocks * 4, hipMemcpyDeviceToHost, ctx.stream);
     hipError_t es = hipStreamSynchronize(ctx.stream);            // before buf goes, on every path
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return ctx.hip_fail(e, "select (diagnostic)");
+    return 0;
+}
+
+// Diagnostic: the conversion kernel alone, out[bits][8][2 primes][2048] doubles.
+int Engine::debug_select_query(const SelectQueries &q, int bits, double *out) {
+    if (planner) return ctx.fail(-3, "planner context: nothing is computed");
+    if (bits < 1 || bits > 24 || q.n != 1) return ctx.fail(-1, "select query (diagnostic): 1..24 bits");
+    if (!ctx.d_tables) return ctx.fail(-3, "select needs the transform tables that the first fhs_load_server_key uploads");
+    (void)hipSetDevice(ctx.device);
+    const size_t bytes = (size_t)bits * SELECT_BIT_POLYS * 2 * POLY_N * sizeof(double);
+    hipError_t e = select_queries_to_ntt(q, bits, nullptr, nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, ctx.sel_query.ptr, bytes, hipMemcpyDeviceToHost, ctx.stream);
+    hipError_t es = hipStreamSynchronize(ctx.stream);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return ctx.hip_fail(e, "select query (diagnostic)");
     return 0;
 }
 

@@ -38,6 +38,11 @@ inline bool select_shape(size_t n_chars, size_t row_chars, SelectShape &s) {
     return true;
 }
 
+// GLWEs of one query in the level buffer `which` (0: launches 0, 2, ..; 1: launches 1, 3, ..)
+inline size_t select_ws_nodes(const SelectShape &s, int which) {
+    return which ? (s.groups + 3) / 4 > 1 ? (s.groups + 3) / 4 : 1 : (s.groups + 1) / 2 > 1 ? (s.groups + 1) / 2 : 1;
+}
+
 // One launch: a tree level (rotate == 0: workgroup i is the CMux of source nodes 2i and 2i + 1 under GGSW `bit`; a node
 // past src_nodes is the zero GLWE) or a rotate bit (rotate = s > 0: workgroup i is CMux(a, X^-s a) of source node i).
 // Source and destination have the entry's layout, mask[nodes][2048] and body[nodes][2048]: node k of the source has
@@ -53,9 +58,31 @@ struct SelectCmuxParams {
     const double *query_ntt;   // [bits][4][col 2][prime 2][16][64 lanes][2], pre-scaled by N^-1 (convert_polys_to_ntt)
     int bit;
     NttTables tw;
+    // Several queries in one launch: query y (blockIdx.y) reads src_mask / src_body + y src_stride (0 while every query
+    // reads the entry itself), writes dst_mask / dst_body + y dst_stride and uses query_ntt + y query_stride.  With a
+    // dst_table (one destination node only) it writes mask[2048] | body at dst_table[y] instead: the new entries.
+    uint32_t queries;          // > 0
+    size_t src_stride, dst_stride;   // 32-bit words
+    size_t query_stride;             // doubles
+    uint32_t *const *dst_table;      // device array [queries], or null
 };
 
-hipError_t prepare_device_for_select();   // dynamic LDS above 64 KB, per device
+// select_query_to_ntt_kernel: n_polys polynomials to query_ntt's layout, out[poly][prime][16][64 lanes][2], the doubles
+// of convert_polys_to_ntt(words, out, n_polys, quant_bits) bit for bit.  seeds == null: words[n_polys][2048].  Otherwise
+// the seeded form of queries of query_polys polynomials each (8 per index bit): polynomial 2 r of query i is the mask of
+// GGSW row r, drawn in the kernel from seeds[i][8] (domain FHS_DOM_SEEDED_SELECT, stream r), polynomial 2 r + 1 its body,
+// words[i][query_polys / 2][2048].
+struct SelectQueryParams {
+    const uint64_t *words;
+    const uint32_t *seeds;
+    uint32_t n_polys, query_polys;
+    int quant_bits;            // 1..32
+    double *out;
+    NttTables tw;
+};
+
+hipError_t prepare_device_for_select();   // dynamic LDS above 64 KB, per device, both kernels
 hipError_t launch_select_cmux(const SelectCmuxParams &p, hipStream_t s);
+hipError_t launch_select_query_to_ntt(const SelectQueryParams &p, hipStream_t s);
 
 }  // namespace fhs

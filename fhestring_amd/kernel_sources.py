@@ -22,7 +22,8 @@ KERNEL_SOURCES = {
     "rekey_glwe_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _KS,
     "rekey_packed_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _KS,
     "rekey_entry_packed_kernel": ["rekey_kernels.hip", "rekey_kernels.h"] + _KS,
-    "select_cmux_kernel": ["select_kernels.hip", "select_kernels.h"] + _KS,
+    "select_cmux_kernel": ["select_kernels.hip", "select_kernels.h", "chacha_device.h"] + _KS,
+    "select_query_to_ntt_kernel": ["select_kernels.hip", "select_kernels.h", "chacha_device.h"] + _KS,
     "store_switch16_kernel": ["store_kernels.hip", "store_kernels.h", "storage_words.h", FLAGS],
     "pack_switch16_kernel": ["pack_kernels.hip", "pack_kernels.h", "storage_words.h", FLAGS],
     "keyswitch_mfma_kernel": ["ks_kernels.hip", FLAGS],

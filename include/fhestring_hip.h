@@ -995,8 +995,8 @@ int fhs_store_packed_host(const uint64_t *rekey_key /*[FHS_REKEY_KEY_WORDS], or 
 int fhs_store_select_bits(size_t n_chars, size_t row_chars);
 /* A fresh query for row `index` (bit k of it goes into GGSW k; bits of index above `bits` are ignored).  bits 1..24. */
 int fhs_client_select_query(fhs_client *ck, uint64_t index, int bits, uint64_t *query_out /*[FHS_SELECT_QUERY_WORDS(bits)]*/);
-/* Selects the row.  The query crosses the bus through the pinned staging buffer and is converted to the transform
- * domain on the host; one kernel launch per tree level and per rotate bit on the context's stream, behind every queued
+/* Selects the row.  The query crosses the bus as it is through the pinned staging buffer and is converted to the
+ * transform domain on the device (one launch); one kernel launch per tree level and per rotate bit on the context's stream, behind every queued
  * fhs_store_get / fhs_store_rekey of the entry; *id_out receives the new entry.  Needs no server key loaded at the time
  * of the call, but the transform tables that the FIRST fhs_load_server_key of a context uploads: FHS_ERR_STATE before
  * that on a device context (a later server-key reload changes nothing).  FHS_ERR_ARG: unknown id, a refused shape, bits
@@ -1010,6 +1010,68 @@ int fhs_store_select_host(const uint64_t *query, int bits, const void *mask32, c
  * context or before the first server key. */
 int fhs_debug_select_device(fhs_ctx *ctx, const uint64_t *query, int bits, const void *mask32, const void *body32,
                             size_t n_blocks, size_t row_chars, void *mask32_out, void *body32_out);
+
+/* ---- string store: seeded queries, queries converted on the GPU, several queries per call -------------------
+ *   Nothing above changes: the full-form query, fhs_store_select and the host reference keep
+ * their words.
+ * THE SEEDED QUERY is the query above with the mask of every GGSW row drawn from a PUBLIC 256-bit seed, so only the
+ * bodies travel: 64 KB per index bit instead of 128 KB, plus 32 bytes.  It follows the seeded-stream convention of
+ * "compressed ciphertexts and server keys":
+ *   select query, index bit k, GGSW row r      domain 8, stream 4k + r   draws 0..2047, each & ~63 (the 58-bit grid)
+ *                                                                        = the row's mask polynomial; the row's body
+ *                                                                        polynomial is sent
+ * Row r of bit k carries the message and the shift of the full form's row.  THE NOISE NEVER COMES FROM THE SEED: the seed
+ * is public, so the noise is drawn from the client's SECRET generator key, noise streams 2^63 + 2^62 + (call << 7) +
+ * 4k + r, a range no other object of the client draws from, distinct per call, bit and row.  The seed is OS entropy; an
+ * insecure seeded client derives it from its 64-bit seed, a tag of its own and the number of SEEDED queries it has made
+ * (a counter of its own: seeded queries do not move what fhs_client_select_query returns next).
+ * fhs_expand_select_query (public data only) rebuilds the full form, [bit][row][mask, body][2048]: everything that
+ * takes a full-form query, fhs_store_select_host included, takes the expansion.
+ * ON THE DEVICE the query -- either form -- crosses the bus as it is and select_query_to_ntt_kernel converts it to the
+ * transform domain; the masks of a seeded query are regenerated inside that kernel.  fhs_store_select_seeded gives word
+ * for word what fhs_store_select gives on the expansion.
+ * SEVERAL QUERIES PER CALL.  fhs_store_select_batch runs n queries (all of one form, all for the same entry and
+ * row_chars) through ONE conversion launch and one CMux launch per tree level and per rotate bit, whatever n is.  Result
+ * i is word for word what fhs_store_select gives for query i alone, with bookkeeping of its own (figures, cycles, its own
+ * fresh rotation group, re-key counter); ids_out are consecutive, in the order of the queries.  The call is ATOMIC: an
+ * unknown id, a refused shape, bits != fhs_store_select_bits, n = 0 or n > FHS_SELECT_MAX_BATCH, a NULL pointer
+ * (FHS_ERR_ARG), the re-key counter limit or a workspace above FHS_SELECT_BATCH_MAX_BYTES (FHS_ERR_LIMIT) create
+ * nothing and write 0 to every ids_out.  The workspace is what the context keeps for the call: the n converted queries
+ * (n x bits x 8 polynomials x 2 primes x 2048 doubles) and the two buffers the tree's levels alternate between
+ * (n x (max(1, ceil(G / 2)) + max(1, ceil(G / 4))) GLWEs of 32-bit words); fhs_store_select_batch_bytes reports it, 0
+ * for a refused shape or n. */
+#define FHS_DOM_SEEDED_SELECT 8
+#define FHS_SELECT_SEEDED_BIT_WORDS ((size_t)4 * 2048)          /* body words of one index bit */
+#define FHS_SELECT_SEEDED_WORDS(bits) ((size_t)(bits) * FHS_SELECT_SEEDED_BIT_WORDS)
+#define FHS_SELECT_FORM_FULL 0
+#define FHS_SELECT_FORM_SEEDED 1
+#define FHS_SELECT_MAX_BATCH 64
+#define FHS_SELECT_BATCH_MAX_BYTES ((size_t)256 * 1024 * 1024)
+/* A fresh seeded query for row `index`: seed_out and bodies[bits][4][2048].  bits 1..24. */
+int fhs_client_select_query_seeded(fhs_client *ck, uint64_t index, int bits, uint32_t seed_out[8],
+                                   uint64_t *bodies /*[FHS_SELECT_SEEDED_WORDS(bits)]*/);
+/* Public data only: the full form of a seeded query. */
+int fhs_expand_select_query(const uint32_t seed[8], const uint64_t *bodies, int bits,
+                            uint64_t *query_out /*[FHS_SELECT_QUERY_WORDS(bits)]*/);
+/* fhs_store_select with a seeded query. */
+int fhs_store_select_seeded(fhs_ctx *ctx, uint64_t id, size_t row_chars, const uint32_t seed[8], const uint64_t *bodies,
+                            int bits, uint64_t *id_out);
+/* n queries of one form: queries[i] points at the full words (FHS_SELECT_FORM_FULL; seeds is NULL) or at the bodies
+ * (FHS_SELECT_FORM_SEEDED; seeds[i][8] is its seed). */
+int fhs_store_select_batch(fhs_ctx *ctx, uint64_t id, size_t row_chars, int form, const uint32_t *seeds,
+                           const uint64_t *const *queries, size_t n, int bits, uint64_t *ids_out /*[n]*/);
+size_t fhs_store_select_batch_bytes(size_t n_chars, size_t row_chars, size_t n);
+/* Diagnostic: select_query_to_ntt_kernel alone.  form FULL: words = the query, seed ignored; form SEEDED: words = the
+ * bodies.  out[bits][8 polynomials][2 primes][2048] doubles, the transform-domain layout of the CMux kernel.
+ * FHS_ERR_STATE on a planner context or before the first server key. */
+int fhs_debug_select_query_device(fhs_ctx *ctx, int form, const uint32_t seed[8], const uint64_t *words, int bits,
+                                  double *out);
+/* Host reference of that conversion (the routine the key loads use): the same doubles, bit for bit. */
+int fhs_select_query_ntt_host(const uint64_t *query, int bits, double *out);
+/* Diagnostic: fhs_debug_select_device with a seeded query. */
+int fhs_debug_select_seeded_device(fhs_ctx *ctx, const uint32_t seed[8], const uint64_t *bodies, int bits,
+                                   const void *mask32, const void *body32, size_t n_blocks, size_t row_chars,
+                                   void *mask32_out, void *body32_out);
 
 /* ---- block pool: what it holds, and giving it back ---------------------------------------------------------
  * Ciphertext blocks are carved from chunks of 2048 blocks (2048 x 2050 x 8 = 33 587 200 B each).  A released block goes

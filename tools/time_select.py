@@ -8,14 +8,20 @@ one select per block per index bit, bootstraps).
     python tools/time_select.py [--reps 10] [--out FILE.json] [--commit HASH] [--machine NAME]
     rocprofv3 --kernel-trace --stats ... -- python tools/time_select.py --kernels-only
 
-select = host call (query conversion on the host, one table pass, the launches) + stream sync; the query itself is made
-by the client beforehand and is not in the figure.  re-key = host call as a copy + stream sync; get = host call + stream
+select = host call (one table pass of the raw query, the conversion launch, the CMux launches) + stream sync; the query
+itself is made by the client beforehand and is not in the figure.  Where the tree has them (run on
+an older tree the tool leaves these legs out, which is how the parent commit is timed in the same session): the seeded
+form of every table, and fhs_store_select_batch on the 256 x 64 table at n = 1, 8, 32 and 64 seeded queries, ms per
+call and per query and the bytes uploaded per query.  re-key = host call as a copy + stream sync; get = host call + stream
 sync.  Medians after a warm-up round, all legs in one process.  No threshold is applied to any figure: the tool reports,
 and the per-CMux time is given as a ratio to one re-key group of the same run (select time / launches against re-key
 time: both are one workgroup deep per launch).
 --kernels-only alternates a select and a re-key of the 256 x 64 table (32 groups: launches of 16, 8, 4, 2, 1 CMuxes and
 three rotates, against one re-key launch of 32 groups) and nothing else: under `rocprofv3 --kernel-trace --stats` the
-averages of select_cmux_kernel and rekey_glwe_kernel are then per launch in the same trace."""
+averages of select_cmux_kernel and rekey_glwe_kernel are then per launch in the same trace.
+--batch-kernels N runs `reps` batch calls of N seeded queries on the 256 x 64 table and nothing else: under the same
+profiler the call counts of select_query_to_ntt_kernel (1 per call) and select_cmux_kernel (8 per call) do not depend
+on N, and their averages are per launch."""
 import argparse
 import json
 import os
@@ -30,7 +36,10 @@ try:
     import torch  # noqa: F401  (one HIP runtime in the process: torch first, like bench.py)
 except ImportError:
     pass
-from fhestring_amd.api import FheString, MyClientKey, MyServerKey, select_bits  # noqa: E402
+from fhestring_amd.api import FheString, MyClientKey, MyServerKey, StoredString, select_bits  # noqa: E402
+
+BATCHED = hasattr(StoredString, "select_many")                       # seeded queries and batches
+BATCH_SIZES = (1, 8, 32, 64)
 
 TABLES = ((2, 512), (256, 64), (64, 64))                             # rows x characters per row
 PAT = "Qz7#"
@@ -52,6 +61,7 @@ def main():
     ap.add_argument("--commit", default="")
     ap.add_argument("--machine", default="")
     ap.add_argument("--kernels-only", action="store_true", help="only the alternating select / re-key of the 256 x 64 table")
+    ap.add_argument("--batch-kernels", type=int, default=0, metavar="N", help="only batch calls of N seeded queries, 256 x 64")
     a = ap.parse_args()
     ck, other = MyClientKey(0x5E1EC7), MyClientKey(0x5E1EC8)
     sk = MyServerKey.from_client_key(ck, arith=1)
@@ -66,6 +76,22 @@ def main():
         e = sk.store_put(FheString(chars))
         del chars
         return e, texts
+
+    if a.batch_kernels:
+        rows, row_chars = TABLES[1]
+        e, texts = table(rows, row_chars)
+        picks = [(7 * i + 3) % rows for i in range(a.batch_kernels)]
+        qs = [ck.select_query(p, rows * row_chars, row_chars, seeded=True) for p in picks]
+        for _ in range(a.reps):
+            out = e.select_many(qs, row_chars)
+            sk.stream_sync()
+            for r in out[1:]:
+                r.drop()
+        assert ck.decrypt_packed(out[0].download_packed()) == texts[picks[0]]
+        sk.close()
+        ck.close()
+        other.close()
+        return
 
     if a.kernels_only:
         rows, row_chars = TABLES[1]
@@ -117,6 +143,37 @@ def main():
                "rekey_copy_ms_median": tr[0], "rekey_copy_ms_min": tr[1],
                "get_row_ms_median": tg[0], "get_row_ms_min": tg[1],
                "select_per_launch_over_rekey": ts[0] / bits / tr[0], "select_over_get_row": ts[0] / tg[0]}
+        if BATCHED:
+            qs = ck.select_query(index, n, row_chars, seeded=True)
+            assert ck.decrypt_packed(e.select(qs, row_chars).download_packed()) == texts[index]
+
+            def select_seeded():
+                made.append(e.select(qs, row_chars))
+                sk.stream_sync()
+
+            tss = med(select_seeded, a.reps)
+            row.update({"seeded_query_bytes": int(qs.bodies.nbytes + qs.seed.nbytes),
+                        "select_seeded_ms_median": tss[0], "select_seeded_ms_min": tss[1]})
+        if BATCHED and (rows, row_chars) == TABLES[1]:
+            row["batches"] = []
+            for nq in BATCH_SIZES:
+                picks = [(7 * i + 3) % rows for i in range(nq)]
+                batch = [ck.select_query(p, n, row_chars, seeded=True) for p in picks]
+                out = e.select_many(batch, row_chars)                                          # warm-up, and the results
+                assert [ck.decrypt_packed(r.download_packed()) for r in out[:3]] == [texts[p] for p in picks[:3]]
+                made.extend(out)
+
+                def select_batch():
+                    made.extend(e.select_many(batch, row_chars))
+                    sk.stream_sync()
+
+                tb = med(select_batch, a.reps)
+                row["batches"].append({"n": nq, "form": "seeded", "ms_per_call_median": tb[0], "ms_per_call_min": tb[1],
+                                       "ms_per_query_median": tb[0] / nq,
+                                       "upload_bytes_per_query": int(batch[0].bodies.nbytes + batch[0].seed.nbytes) + 8})
+                for x in made:
+                    x.drop()
+                del made[:]
         res["tables"].append(row)
         print(json.dumps(row), flush=True)
         for x in made + [e]:
