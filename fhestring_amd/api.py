@@ -1588,6 +1588,34 @@ class MyServerKey:
             return {"code": rc, "err_offset": off.value}
         return {"code": 0, "positions": pos.value, "min_len": low.value}
 
+    def regex_find_clear(self, string, pattern, ignore_case=False):
+        """Where the first match of a clear regular expression starts (fhs_str_regex_find_clear):
+        re.search(pattern, text, re.S).start() on the text up to the buffer's first NUL, as find returns a position (255 if
+        there is no match); at most 256 characters.  Syntax and errors are regex_clear's.  pattern: str (ASCII) or bytes."""
+        s = self._chars(string)
+        data, flags = self._regex_args(pattern, ignore_case, False)
+        out = C.c_uint64()
+        self.ctx._check(self.ctx._L.fhs_str_regex_find_clear(self.ctx._h, _harr(s), len(s), data, len(data), flags, C.byref(out)))
+        return FheAsciiChar(self, out.value)
+
+    def regex_find_clear_wide(self, string, pattern, ignore_case=False):
+        """regex_find_clear with a 16-bit position (FheU16; absent = 65535; at most 65536 characters)."""
+        s = self._chars(string)
+        data, flags = self._regex_args(pattern, ignore_case, False)
+        lo, hi = C.c_uint64(), C.c_uint64()
+        self.ctx._check(self.ctx._L.fhs_str_regex_find_clear_wide(self.ctx._h, _harr(s), len(s), data, len(data), flags,
+                                                                  C.byref(lo), C.byref(hi)))
+        return FheU16(FheAsciiChar(self, lo.value), FheAsciiChar(self, hi.value))
+
+    def regex_starts_clear(self, string, pattern, ignore_case=False):
+        """One 0/1 flag char per buffer character (fhs_str_regex_starts_clear): 1 iff re.match(pattern, text, i) succeeds
+        and no NUL stands before index i."""
+        s = self._chars(string)
+        data, flags = self._regex_args(pattern, ignore_case, False)
+        out = (C.c_uint64 * max(1, len(s)))()
+        self.ctx._check(self.ctx._L.fhs_str_regex_starts_clear(self.ctx._h, _harr(s), len(s), data, len(data), flags, out))
+        return FheString([FheAsciiChar(self, out[i]) for i in range(len(s))])
+
     def starts_with(self, string, pattern, public_parameters=None):      # mod.rs:344
         return self._flag_op("starts_with", string, pattern)
 

@@ -517,6 +517,54 @@ int fhs_str_regex_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *p
     *out = store(c->eng, r);
     return FHS_OK;
 }
+// Where a match starts: the flags of all starts (`flags`), or the first start as a position (lo,
+// hi).  The order of fhs_str_regex_clear: the pattern, what it decides alone, the tables, and only then the string.
+namespace {
+int regex_find_op(fhs_ctx *c, const char *name, const fhs_char_t *s, size_t n, const char *pat, size_t m, uint32_t flags,
+                  fhs_char_t *starts, fhs_char_t *lo, fhs_char_t *hi) {
+    if (flags & ~(uint32_t)FHS_REGEX_IGNORE_CASE)
+        return c->eng.ctx.fail(FHS_ERR_ARG, std::string(name) + ": FHS_REGEX_IGNORE_CASE is the only flag bit these calls take");
+    RegexProgram g;
+    const char *why = "";
+    const RegexStatus st = regex_compile(pat, m, (flags & FHS_REGEX_IGNORE_CASE) != 0, false, &g, nullptr, &why);
+    if (st != REGEX_OK) return c->eng.ctx.fail(st == REGEX_LIMIT ? FHS_ERR_LIMIT : FHS_ERR_ARG, why);
+    const size_t halves = hi ? 2 : 1;
+    if (lo && n > ((size_t)1 << (8 * halves))) return c->eng.ctx.fail(FHS_ERR_LIMIT, Strings::LIMIT_MSG);
+    const RegexProgram rev = regex_reverse(g);
+    Strings S(&c->eng);
+    Strings::RegexPlan plan;
+    // decided by the pattern alone: the string is not loaded, the empty one gives the same position; the start flags of
+    // a nullable pattern are "no NUL before i", which the string decides
+    const int known = Strings::regex_find_trivial(rev, n);
+    const bool decided = known == 0 || (known == 1 && !starts);
+    if (!decided && !S.regex_plan(rev, &plan)) return finish(c, S);
+    const FStr text = decided ? FStr() : load_str(c->eng, s, n);
+    if (starts) {
+        FStr r = decided ? FStr(n, ch_trivial(&c->eng, 0)) : S.regex_starts(text, rev, plan);
+        if (int rc = finish(c, S)) return rc;
+        store_str(c->eng, r, starts);
+        return FHS_OK;
+    }
+    Pos r = S.regex_find(text, rev, plan, halves);
+    if (int rc = finish(c, S)) return rc;
+    *lo = store(c->eng, r[0]);
+    if (hi) *hi = store(c->eng, r[1]);
+    return FHS_OK;
+}
+}  // namespace
+int fhs_str_regex_find_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, uint32_t flags, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || (m && !pat) || !out) return bad(c);
+    return regex_find_op(c, "fhs_str_regex_find_clear", s, n, pat, m, flags, nullptr, out, nullptr);
+}
+int fhs_str_regex_find_clear_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, uint32_t flags,
+                                  fhs_char_t *lo, fhs_char_t *hi) {
+    if (!ok_all(c, s, n) || (m && !pat) || !lo || !hi) return bad(c);
+    return regex_find_op(c, "fhs_str_regex_find_clear_wide", s, n, pat, m, flags, nullptr, lo, hi);
+}
+int fhs_str_regex_starts_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, uint32_t flags, fhs_char_t *out) {
+    if (!ok_all(c, s, n) || (m && !pat) || (n && !out)) return bad(c);
+    return regex_find_op(c, "fhs_str_regex_starts_clear", s, n, pat, m, flags, out, nullptr, nullptr);
+}
 int fhs_str_is_empty(fhs_ctx *c, const fhs_char_t *s, size_t n, fhs_char_t *out) {
     if (!ok_all(c, s, n) || !out) return bad(c);
     Strings S(&c->eng);

@@ -409,4 +409,11 @@ RegexStatus regex_compile(const char *pat, size_t m, bool ignore_case, bool sear
     return REGEX_OK;
 }
 
+RegexProgram regex_reverse(const RegexProgram &g) {
+    RegexProgram r = g;
+    std::swap(r.first, r.last);
+    r.follow.swap(r.pred);
+    return r;
+}
+
 }  // namespace fhs

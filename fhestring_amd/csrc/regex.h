@@ -40,4 +40,8 @@ enum RegexStatus { REGEX_OK = 0, REGEX_SYNTAX, REGEX_LIMIT };
 RegexStatus regex_compile(const char *pat, size_t m, bool ignore_case, bool search, RegexProgram *out, size_t *err_offset,
                           const char **err_msg);
 
+// The automaton of the reversed language: first and last change places, and so do follow and
+// pred; classes, the nullable bit and min_len stay.  Run from the right end of a text it says where a match STARTS.
+RegexProgram regex_reverse(const RegexProgram &g);
+
 }  // namespace fhs

@@ -2506,6 +2506,39 @@ Ref Strings::regex_step(std::vector<Ref> in_all, std::vector<Ref> preds_all) {
     }
 }
 
+std::vector<std::vector<std::vector<Ref>>> Strings::regex_class_tests(const FStr &s, const RegexProgram &g, const RegexPlan &plan,
+                                                                      const std::vector<uint64_t> &live, std::vector<Ref> &nz) {
+    const size_t n = s.size(), P = g.positions(), K = g.classes.size();
+    std::vector<std::vector<std::vector<Ref>>> in(K, std::vector<std::vector<Ref>>(n));
+    for (size_t k = 0; k < K; k++) {
+        std::vector<size_t> where;
+        for (size_t i = 0; i < n; i++)
+            for (size_t q = 0; q < P; q++)
+                if (((live[i] >> q) & 1) && (size_t)g.cls[q] == k) { where.push_back(i); break; }
+        if (plan.kind[k] == RegexPlan::TABLE) {
+            FStr sub;
+            for (size_t i : where) sub.push_back(s[i]);
+            const std::vector<Ref> f = f_class_flags(sub, plan.table[k]);
+            for (size_t j = 0; j < where.size(); j++) in[k][where[j]].assign(1, f[j]);
+            continue;
+        }
+        for (size_t i : where) {
+            if (plan.kind[k] == RegexPlan::ANY) {
+                if (!nz[i]) nz[i] = char_zero_test(s[i], false);
+                in[k][i].assign(1, nz[i]);
+                continue;
+            }
+            std::vector<Ref> a = block_eq_flags(s[i], t(plan.byte[k]));
+            if (plan.both_cases[k]) {                        // the other case: the same low-nibble test, the other row
+                const std::vector<Ref> b = block_eq_flags(s[i], t(plan.byte[k] | 0x20));
+                a[1] = lin(e_, {{1, &a[1]}, {1, &b[1]}});
+            }
+            in[k][i] = a;
+        }
+    }
+    return in;
+}
+
 // Fused.  (1) The class tests of all characters stand at the front of the DAG: a class of one byte (or of the two cases
 // of one letter) is the two nibble flags of block_eq_flags -- extractions of the two rotations per character that
 // contains_clear and like_clear run, the other case's high nibble a second extraction summed to the first as in f_like
@@ -2515,7 +2548,7 @@ Ref Strings::regex_step(std::vector<Ref> in_all, std::vector<Ref> preds_all) {
 // costs L steps on any n.  (4) The result is the or_tree over the ends: for j < n one regex_step of end[j] = 1 - nz[j]
 // with the last positions live at j - 1, for j == n those flags themselves; nz[j] is made only where an end can fall.
 FChar Strings::f_regex(const FStr &s, const RegexProgram &g, const RegexPlan &plan) {
-    const size_t n = s.size(), P = g.positions(), K = g.classes.size();
+    const size_t n = s.size(), P = g.positions();
     const Ref one = trivial_block(e_, 1);
     const size_t FAR = (size_t)-1;
     std::vector<size_t> dist(P, FAR);                        // characters from q to the nearest last position
@@ -2543,29 +2576,7 @@ FChar Strings::f_regex(const FStr &s, const RegexProgram &g, const RegexPlan &pl
         return nz[i];
     };
     // (1) class tests: in[k][i] holds one flag, or the two nibble flags of a BYTE class
-    std::vector<std::vector<std::vector<Ref>>> in(K, std::vector<std::vector<Ref>>(n));
-    for (size_t k = 0; k < K; k++) {
-        std::vector<size_t> where;
-        for (size_t i = 0; i < n; i++)
-            for (size_t q = 0; q < P; q++)
-                if (((live[i] >> q) & 1) && (size_t)g.cls[q] == k) { where.push_back(i); break; }
-        if (plan.kind[k] == RegexPlan::TABLE) {
-            FStr sub;
-            for (size_t i : where) sub.push_back(s[i]);
-            const std::vector<Ref> f = f_class_flags(sub, plan.table[k]);
-            for (size_t j = 0; j < where.size(); j++) in[k][where[j]].assign(1, f[j]);
-            continue;
-        }
-        for (size_t i : where) {
-            if (plan.kind[k] == RegexPlan::ANY) { in[k][i].assign(1, nonzero(i)); continue; }
-            std::vector<Ref> a = block_eq_flags(s[i], t(plan.byte[k]));
-            if (plan.both_cases[k]) {                        // the other case: the same low-nibble test, the other row
-                const std::vector<Ref> b = block_eq_flags(s[i], t(plan.byte[k] | 0x20));
-                a[1] = lin(e_, {{1, &a[1]}, {1, &b[1]}});
-            }
-            in[k][i] = a;
-        }
-    }
+    const std::vector<std::vector<std::vector<Ref>>> in = regex_class_tests(s, g, plan, live, nz);
     // (2) the steps; positions with the same live predecessors share the OR (the engine finds the same bootstrap again)
     std::vector<Ref> fin;
     if (g.nullable) {
@@ -2602,6 +2613,190 @@ FChar Strings::f_regex(const FStr &s, const RegexProgram &g, const RegexPlan &pl
     Ref r = or_tree(fin);
     if (e_->sum_c2(r.id()) > 1) r = pbs(r, LUT_NZ);          // a lone class flag or 1 - nz: a linear form
     return ch_flag(e_, r);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Where a match starts: re.match(pat, text, i) for every i at once, and re.search(pat, text).start()
+// as the index of the first one.  The automaton runs BACKWARDS: `rev` = regex_reverse(pattern), read from the right,
+//     back[q][i] = in_q(s[i]) & (q in rev.first  |  OR_{p in rev.pred(q)} back[p][i+1])         back[.][n] = 0
+//     inside[i]  = no NUL among s[0 .. i-1]
+//     start[i]   = inside[i] & OR_{q in rev.last} back[q][i]                  (nullable: start[i] = inside[i])
+// rev.first are the pattern's last positions and rev.pred its follow sets, so back[q][i] says: from index i on, the
+// characters can be read from position q to the end of a match.  No atom matches NUL, so a match that starts inside the
+// text ends inside it: there is no end condition.  One pass, as deep as the string is long.
+// ---------------------------------------------------------------------------------------------
+int Strings::regex_find_trivial(const RegexProgram &rev, size_t n) {
+    if (rev.nullable) return 1;
+    return rev.min_len > n || n == 0 ? 0 : -1;
+}
+
+FStr Strings::regex_starts(const FStr &s, const RegexProgram &rev, const RegexPlan &plan) {
+    if (regex_find_trivial(rev, s.size()) == 0) return FStr(s.size(), t(0));
+    if (!fused()) return regex_starts_as_written(s, rev, plan);
+    FStr r;
+    for (Ref f : f_regex_starts(s, rev, plan)) {
+        if (e_->sum_c2(f.id()) > 1) f = pbs(f, LUT_NZ);      // a lone class flag: a linear form
+        r.push_back(ch_flag(e_, f));
+    }
+    return r;
+}
+
+Pos Strings::regex_find(const FStr &s, const RegexProgram &rev, const RegexPlan &plan, size_t halves) {
+    if (s.size() > ((size_t)1 << (8 * halves))) {             // as find_class: every index has to fit
+        err = {FHS_ERR_LIMIT, LIMIT_MSG};
+        return pos_trivial(0, halves);
+    }
+    const int k = regex_find_trivial(rev, s.size());
+    if (k >= 0) return pos_trivial(k ? 0 : absent_value(halves), halves);
+    if (fused()) return num_pos(f_find_digits(f_regex_starts(s, rev, plan), 4 * halves));
+    Pos pos = pos_trivial(absent_value(halves), halves);
+    const FStr flags = regex_starts_as_written(s, rev, plan);
+    for (size_t i = s.size(); i-- > 0;) pos_set_if(pos, flags[i], i);
+    return pos;
+}
+
+// As written: the three formulas from char operations, in regex_as_written's style -- a class is the OR over its runs of
+// eq, ne 0 or ge & le, tested once per (class, index); trivial flags are not sent through a bitand / bitor, which keeps
+// what cannot end a match in the characters that are left free of charge; inside is a running bitand of ne(s[i], 0).
+FStr Strings::regex_starts_as_written(const FStr &s, const RegexProgram &rev, const RegexPlan &plan) {
+    const size_t n = s.size(), P = rev.positions(), K = rev.classes.size();
+    const FChar zero = t(0), one = t(1);
+    auto konst = [&](const FChar &f) {                       // 0 / 1 for a trivial flag, -1 for an encrypted one
+        int v = 0;
+        for (int k = 0; k < 4; k++) {
+            if (!e_->is_triv(f.b[k].id())) return -1;
+            v |= (e_->triv_val(f.b[k].id()) & 3) << (2 * k);
+        }
+        return v;
+    };
+    auto band = [&](const FChar &a, const FChar &b) {
+        const int ka = konst(a), kb = konst(b);
+        if (ka == 0 || kb == 0) return zero;
+        if (ka == 1) return b;
+        if (kb == 1) return a;
+        return ch_bitand(a, b);
+    };
+    auto bor = [&](const FChar &a, const FChar &b) {
+        const int ka = konst(a), kb = konst(b);
+        if (ka == 1 || kb == 1) return one;
+        if (ka == 0) return b;
+        if (kb == 0) return a;
+        return ch_bitor(a, b);
+    };
+    std::vector<std::vector<FChar>> tests(K, std::vector<FChar>(n));      // [class][index]
+    std::vector<std::vector<char>> tested(K, std::vector<char>(n, 0));
+    auto test = [&](size_t k, size_t i) {
+        if (tested[k][i]) return tests[k][i];
+        FChar f = zero;
+        if (plan.kind[k] != RegexPlan::DEAD) {
+            const RegexClass &c = rev.classes[k];
+            for (int lo = 1; lo < 256; lo++) {
+                if (!c.has(lo)) continue;
+                int hi = lo;
+                while (hi < 255 && c.has(hi + 1)) hi++;
+                FChar run;
+                if (lo == hi) run = ch_eq(s[i], t((uint8_t)lo));
+                else if (lo == 1 && hi == 255) run = ch_ne(s[i], zero);
+                else if (hi == 255) run = ch_ge(s[i], t((uint8_t)lo));
+                else run = band(ch_ge(s[i], t((uint8_t)lo)), ch_le(s[i], t((uint8_t)hi)));
+                f = bor(f, run);
+                lo = hi;
+            }
+        }
+        tested[k][i] = 1;
+        return tests[k][i] = f;
+    };
+    auto any_of = [&](const std::vector<FChar> &back, uint64_t set) {
+        FChar r = zero;
+        for (size_t p = 0; p < P; p++)
+            if ((set >> p) & 1) r = bor(r, back[p]);
+        return r;
+    };
+    FStr matches(n, one);                                    // OR_{q in rev.last} back[q][i]; a nullable pattern: 1
+    std::vector<FChar> next(P, zero), cur(P, zero);
+    for (size_t i = n; i-- > 0 && !rev.nullable;) {
+        for (size_t q = 0; q < P; q++) {
+            const FChar after = ((rev.first >> q) & 1) ? one : any_of(next, rev.pred[q]);
+            cur[q] = konst(after) == 0 ? zero : band(test((size_t)rev.cls[q], i), after);
+        }
+        matches[i] = any_of(cur, rev.last);
+        next.swap(cur);
+    }
+    FStr r(n);
+    FChar inside = one;
+    for (size_t i = 0; i < n; i++) {
+        if (i) inside = band(inside, ch_ne(s[i - 1], zero));
+        r[i] = band(inside, matches[i]);
+    }
+    return r;
+}
+
+// Fused, on f_regex's parts.  (1) The class tests stand at the front (regex_class_tests).  (2) One regex_step per live
+// (q, i), from the right: `in` the class flag(s), `preds` the back flags of rev.pred(q) at i + 1, or the trivial 1 for a
+// q in rev.first, which folds the step to the AND of its class flags.  (3) (q, i) is live iff some position of rev.last
+// (where a match starts) is at most i characters before q and some position of rev.first (where it ends) at most
+// n - 1 - i characters after it, dead classes on neither way.  (4) start[i] is one more regex_step: in = inside[i] = 1 -
+// Z[i], Z the exclusive prefix OR of the zero flags 1 - nz -- it stands beside the recurrence, log_15 n levels deep --
+// preds = the back flags of rev.last at i: what acceptance does with end[j] in f_regex, so the text gate costs no level.
+// The flags come back as they are (a class flag that no step refreshed may be a sum): regex_starts refreshes those,
+// regex_find hands them to f_find_digits as find_class does.
+std::vector<Ref> Strings::f_regex_starts(const FStr &s, const RegexProgram &rev, const RegexPlan &plan) {
+    const size_t n = s.size(), P = rev.positions();
+    const Ref one = trivial_block(e_, 1), zero = trivial_block(e_, 0);
+    const size_t FAR = (size_t)-1;
+    auto alive = [&](size_t q) { return plan.kind[rev.cls[q]] != RegexPlan::DEAD; };
+    // characters from q on to the end of a match (0: q ends one), and from the start of a match up to q (0: q starts one)
+    auto distances = [&](uint64_t from, const std::vector<uint64_t> &towards) {
+        std::vector<size_t> d(P, FAR);
+        for (size_t q = 0; q < P; q++)
+            if (((from >> q) & 1) && alive(q)) d[q] = 0;
+        for (size_t round = 0; round < P; round++)
+            for (size_t q = 0; q < P; q++)
+                for (size_t p = 0; p < P; p++)
+                    if (((towards[q] >> p) & 1) && d[p] != FAR && alive(q)) d[q] = std::min(d[q], d[p] + 1);
+        return d;
+    };
+    const std::vector<size_t> to_end = distances(rev.first, rev.pred), from_start = distances(rev.last, rev.follow);
+    std::vector<uint64_t> live(n, 0);
+    size_t gates = 0;                                        // start flags are made below this index
+    for (size_t i = 0; i < n; i++) {
+        for (size_t q = 0; q < P; q++)
+            if (to_end[q] != FAR && from_start[q] != FAR && from_start[q] <= i && to_end[q] <= n - 1 - i)
+                live[i] |= (uint64_t)1 << q;
+        if (rev.nullable || (live[i] & rev.last)) gates = i + 1;
+    }
+    std::vector<Ref> nz(n);
+    const std::vector<std::vector<std::vector<Ref>>> in = regex_class_tests(s, rev, plan, live, nz);
+    // inside[i] = 1 - Z[i]: the zero flags of the characters before the last gate, one unused flag behind (exclusive)
+    std::vector<Ref> Z;
+    if (gates) {
+        std::vector<Ref> zf(gates, zero);
+        for (size_t i = 0; i + 1 < gates; i++) {
+            if (!nz[i]) nz[i] = char_zero_test(s[i], false);
+            zf[i] = lin(e_, {{1, &one}, {-1, &nz[i]}});
+        }
+        Z = prefix_or(zf);
+    }
+    std::vector<Ref> start(n, zero), next(P), cur(P);
+    for (size_t i = n; i-- > 0 && !err.code;) {
+        std::vector<Ref> begun;
+        for (size_t q = 0; q < P; q++) {
+            cur[q] = Ref();
+            if (!((live[i] >> q) & 1)) continue;
+            std::vector<Ref> preds;
+            if ((rev.first >> q) & 1) preds.push_back(one);
+            for (size_t p = 0; p < P; p++)
+                if (((rev.pred[q] >> p) & 1) && next[p]) preds.push_back(next[p]);
+            cur[q] = regex_step(in[rev.cls[q]][i], preds);
+            if ((rev.last >> q) & 1) begun.push_back(cur[q]);
+        }
+        if (i < gates) {
+            if (rev.nullable) begun.assign(1, one);
+            start[i] = regex_step({lin(e_, {{1, &one}, {-1, &Z[i]}})}, begun);
+        }
+        next.swap(cur);
+    }
+    return start;
 }
 
 }  // namespace fhs

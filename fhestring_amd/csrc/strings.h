@@ -95,6 +95,15 @@ class Strings {
     static int regex_trivial(const RegexProgram &g, size_t n);
     bool regex_plan(const RegexProgram &g, RegexPlan *out);
     FChar regex(const FStr &s, const RegexProgram &g, const RegexPlan &plan);
+    // Where a match of a CLEAR pattern starts.  `rev` is regex_reverse of the pattern compiled
+    // without search, `plan` is regex_plan(rev).  regex_starts: n 0/1 flag chars, out[i] = a match begins at i and no NUL
+    // stands before i.  regex_find: the index of the first set flag as find_class returns it (absent: 255 / 65535; at
+    // most 256 / 65536 characters).  regex_find_trivial: what the pattern alone decides on n characters -- 1: nullable,
+    // find is 0 (starts still depends on the string); 0: not nullable and min_len > n or n == 0, find is absent and every
+    // start flag 0; -1 otherwise.
+    static int regex_find_trivial(const RegexProgram &rev, size_t n);
+    FStr regex_starts(const FStr &s, const RegexProgram &rev, const RegexPlan &plan);
+    Pos regex_find(const FStr &s, const RegexProgram &rev, const RegexPlan &plan, size_t halves = 1);
     FChar eq(const FStr &a, const FStr &b);
     FChar ne(const FStr &a, const FStr &b);
     FChar eq_ignore_case(const FStr &a, const FStr &b);
@@ -182,6 +191,12 @@ class Strings {
     FChar regex_as_written(const FStr &s, const RegexProgram &g, const RegexPlan &plan);
     FChar f_regex(const FStr &s, const RegexProgram &g, const RegexPlan &plan);
     Ref regex_step(std::vector<Ref> in, std::vector<Ref> preds);      // AND of the flags `in` AND (OR of `preds`)
+    // fused class tests of f_regex / f_regex_starts: [class][index] -> one flag, or the two nibble flags of a BYTE class,
+    // where live[index] holds a position of that class; nz[index] = [s[index] != 0] is made on demand and shared
+    std::vector<std::vector<std::vector<Ref>>> regex_class_tests(const FStr &s, const RegexProgram &g, const RegexPlan &plan,
+                                                                 const std::vector<uint64_t> &live, std::vector<Ref> &nz);
+    FStr regex_starts_as_written(const FStr &s, const RegexProgram &rev, const RegexPlan &plan);
+    std::vector<Ref> f_regex_starts(const FStr &s, const RegexProgram &rev, const RegexPlan &plan);
     FChar f_eq(const FStr &a, const FStr &b);
     FChar f_eq_ignore_case(const FStr &a, const FStr &b);
     // lexicographic order as a tree of three-state values s = sign(a - b) in {-1, 0, 1}, most significant first

@@ -367,6 +367,27 @@ int fhs_str_like_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pa
 int fhs_str_regex_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, uint32_t flags, fhs_char_t *out);
 int fhs_regex_info(const char *pat, size_t m, uint32_t flags, size_t *positions, size_t *min_len, size_t *err_offset);
 
+/* ---- regular expressions: where the match is -------------------------------------------
+ * With text = the n characters of s up to the first NUL (all of them if there is none), L = len(text) and
+ *   rx = re.compile(pat, re.S)                       Python, bytes; re.I as well with FHS_REGEX_IGNORE_CASE
+ * regex_starts_clear: out[i] is the 0/1 flag char of "i <= L and rx.match(text, i) is not None" -- a match begins at i,
+ * and i lies inside the text; i == L can hold a 1 only for a nullable pattern (the empty match at the end) and L < n.
+ * regex_find_clear: rx.search(text).start() as find_class returns a position -- the index of the first set start flag,
+ * FHS_MAX_FIND_LENGTH (FHS_WIDE_ABSENT for the wide form) if there is no match; an index equal to that value reads the
+ * same.  A match that exists only beyond the first NUL is not found.  No atom matches NUL, so a match that starts inside
+ * the text ends inside it: any end will do, as under FHS_REGEX_SEARCH.  The syntax, its refusals and its limits are
+ * fhs_str_regex_clear's; FHS_REGEX_IGNORE_CASE is the only flag bit -- the calls are searches by nature, so
+ * FHS_REGEX_SEARCH is FHS_ERR_ARG like every unknown bit.  FHS_ERR_LIMIT above 256 (65536) characters for a position,
+ * as for find_class.  A nullable pattern gives the trivial position 0; a pattern that is not nullable and whose shortest
+ * match is longer than n (or n == 0) the trivial absent value and n trivial zero flags: all with nothing recorded and no
+ * operand loaded.  Every error is raised before anything is recorded; fused mode registers its class and step tables
+ * before the string is loaded (FHS_ERR_LIMIT when the registry is full), as written none is registered.  Both modes;
+ * the automaton runs backwards over the string once, so the fused DAG is as deep as the string is long, plus the levels
+ * of find_class's position for the two find forms. */
+int fhs_str_regex_find_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, uint32_t flags, fhs_char_t *out);
+int fhs_str_regex_find_clear_wide(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, uint32_t flags, fhs_char_t *lo, fhs_char_t *hi);
+int fhs_str_regex_starts_clear(fhs_ctx *c, const fhs_char_t *s, size_t n, const char *pat, size_t m, uint32_t flags, fhs_char_t *out /*[n]*/);
+
 /* ---- user look-up tables; clear tables and sets on strings -----------------------------
  * fhs_user_lut registers a 16-entry table f(v), v in [0, 16), values block values below 32, and returns its id in
  * *lut_id.  The registry is process-wide and interned by content: equal tables get the same id, ids count up from the

@@ -312,6 +312,20 @@ int main() {
         CHECK(fhs_str_regex_clear(c, s.data(), s.size(), "a{65}", 5, 0, &r) == FHS_ERR_LIMIT);
         CHECK(fhs_str_regex_clear(c, s.data(), s.size(), "ab", 2, 4, &r) == FHS_ERR_ARG);
         CHECK(fhs_str_regex_clear(c, s.data(), s.size(), "ab", 2, 0, nullptr) == FHS_ERR_ARG);
+        // ... and where they match: the automaton run backwards, the position in both widths and the flags of all starts
+        for (const char *pat : {"", "ab c", "a.*c", "(ab| c)+a?", "[a-c ]{2,3}.*", "[^b]+", "\\w+\\s\\S*", "(a|b|c| |ab|bc|c a|abc)+",
+                                "a{0}(b{2,}|[\\x61-\\x63]?)*", "(ab c){3}ab.*", "\\0?a.*"})
+            for (uint32_t fl = 0; fl < 2; fl++) {
+                std::vector<fhs_char_t> starts(s.size() + 1, 0);
+                fhs_char_t lo = 0, hi = 0;
+                CHECK(fhs_str_regex_find_clear(c, s.data(), s.size(), pat, std::strlen(pat), fl, &r) == FHS_OK && r);
+                CHECK(fhs_str_regex_find_clear_wide(c, s.data(), s.size(), pat, std::strlen(pat), fl, &lo, &hi) == FHS_OK && lo && hi);
+                CHECK(fhs_str_regex_starts_clear(c, s.data(), s.size(), pat, std::strlen(pat), fl, starts.data()) == FHS_OK && starts[s.size() - 1]);
+                CHECK(starts[s.size()] == 0);
+            }
+        CHECK(fhs_str_regex_find_clear(c, s.data(), s.size(), "ab", 2, FHS_REGEX_SEARCH, &r) == FHS_ERR_ARG);
+        CHECK(fhs_str_regex_starts_clear(c, s.data(), s.size(), "(ab", 3, 0, &r) == FHS_ERR_ARG);
+        CHECK(fhs_str_regex_find_clear_wide(c, s.data(), s.size(), "a{65}", 5, 0, &r, &f) == FHS_ERR_LIMIT);
         CHECK(fhs_str_starts_with(c, s.data(), s.size(), p.data(), p.size(), &r) == FHS_OK);
         CHECK(fhs_str_ends_with(c, s.data(), s.size(), p.data(), p.size(), &r) == FHS_OK);
         CHECK(fhs_str_find(c, s.data(), s.size(), p.data(), p.size(), &r) == FHS_OK);
