@@ -87,6 +87,17 @@ __global__ __launch_bounds__(128, 2) void blind_rotate_fft_kernel(BlindRotateFft
     uint64_t *my_u = reinterpret_cast<uint64_t *>(my);
     int *next_ct = reinterpret_cast<int *>(smem + 2 * FFT_LDS_DOUBLES * sizeof(double));
 
+    // The per-lane twiddles (6 bases and the 8 products a transform makes of them) depend on the lane only: loaded and
+    // multiplied once per kernel and kept in registers (56 VGPRs) for both transforms of every iteration of every
+    // ciphertext.  Reloaded per transform they cost 24 loads and 60 FP64 instructions per iteration.  The key window
+    // below is 4 points wide to pay for the registers: with an 8-point one the loop spilled.
+    LaneTwFull tw;
+    {
+        LaneTw bases;
+        load_lane_tw(bases, P.lanetab, lane);
+        tw.fill(bases);
+    }
+
     // Persistent workgroups: the grid holds at most one workgroup per resident slot (4 per CU) and every workgroup
     // takes ciphertexts from a counter until none is left.  Left to the hardware dispatcher, a launch of an exact
     // multiple of the slot count ended with a few workgroups starting a whole bootstrap late (one XCD had been
@@ -143,11 +154,6 @@ __global__ __launch_bounds__(128, 2) void blind_rotate_fft_kernel(BlindRotateFft
         // measured -4..-10 % kernel time against equal priorities.
         __builtin_amdgcn_s_setprio(1);
 
-        // keep the (loop-invariant) per-lane twiddle loads inside the iteration: 24 registers that are only
-        // live while a transform runs instead of across the whole loop
-        const double *lanetab = P.lanetab;
-        asm volatile("" : "+s"(lanetab));
-
         // rotate, subtract, decompose; fold: z[r] = digit[r] + i * digit[r + 16]
         cplx z[16];
         __builtin_amdgcn_wave_barrier();
@@ -187,23 +193,20 @@ __global__ __launch_bounds__(128, 2) void blind_rotate_fft_kernel(BlindRotateFft
         }
         __builtin_amdgcn_wave_barrier();
 
-        // Key rows for this iteration, column j: own transform's row j, then the partner's row 1-j.  An 8-point window
-        // (32 VGPRs): the own row's first 8 points are requested before the transform; see publish_mul_hook for the rest.
+        // Key rows for this iteration, column j: own transform's row j, then the partner's row 1-j.  A 4-point window
+        // (16 VGPRs): the own row's first 4 points are requested before the transform; see publish_mul_hook for the rest.
         const double2_t *b_own = reinterpret_cast<const double2_t *>(P.bsk_fft) + ((((size_t)i * 2 + j) * 2 + j)) * FM + lane;
         const double2_t *b_par = reinterpret_cast<const double2_t *>(P.bsk_fft) + ((((size_t)i * 2 + (1 - j)) * 2 + j)) * FM + lane;
-        double2_t kb[8];
+        double2_t kb[4];
 #pragma unroll
-        for (int k = 0; k < 8; k++) kb[k] = b_own[k * 64];
+        for (int k = 0; k < 4; k++) kb[k] = b_own[k * 64];
 
-        {
-            LaneTw tw;
-            load_lane_tw(tw, lanetab, lane);
-            fft_forward(z, my, lane, tw);
-            fft_forward_last(z, tw, publish_mul_hook{reinterpret_cast<cplx *>(my) + lane, z, kb, b_own, b_par});
-        }
+        fft_forward(z, my, lane, tw);
+        fft_forward_last(z, tw, publish_mul_hook{reinterpret_cast<cplx *>(my) + lane, z, kb, b_own, b_par});
         __syncthreads();
         __builtin_amdgcn_s_setprio(2);
-        {   // partner row: z[c] += g[c] * kb (the second half of the pointwise product, same operation order as before)
+        {   // partner row: z[c] += g[c] * kb (the second half of the pointwise product, same operation order as before);
+            // the hook left the partner row's points 0..3 in the window, point c + 4 follows into the slot of point c
             const cplx *par = reinterpret_cast<const cplx *>(partner) + lane;
             // PW reads in flight ahead of their use (one at a time, each point waited for its own LDS round trip)
             constexpr int PW = 4;
@@ -214,23 +217,17 @@ __global__ __launch_bounds__(128, 2) void blind_rotate_fft_kernel(BlindRotateFft
             for (int c = 0; c < 16; c++) {
                 const cplx g = gq[c % PW];
                 if (c + PW < 16) gq[c % PW] = par[(c + PW) * 64];
-                const double2_t k = kb[c & 7];
+                const double2_t k = kb[c & 3];
                 double rr = __builtin_fma(g.r, k.x, z[c].r); rr = __builtin_fma(-g.i, k.y, rr);
                 double ii = __builtin_fma(g.r, k.y, z[c].i); ii = __builtin_fma(g.i, k.x, ii);
                 z[c].r = rr; z[c].i = ii;
-                if (c < 8) kb[c] = b_par[(c + 8) * 64];
+                if (c < 12) kb[c & 3] = b_par[(c + 4) * 64];
             }
         }
         __syncthreads();
         __builtin_amdgcn_s_setprio(0);
 
-        {   // reloaded rather than kept live across the pointwise phase
-            const double *lanetab2 = P.lanetab;
-            asm volatile("" : "+s"(lanetab2));
-            LaneTw tw2;
-            load_lane_tw(tw2, lanetab2, lane);
-            fft_inverse(z, my, lane, tw2);
-        }
+        fft_inverse(z, my, lane, tw);
 
         // update, and stage the new accumulator in LDS for the next iteration's rotated read (the store
         // burst overlaps the conversions instead of stalling the start of the next iteration)
@@ -284,7 +281,7 @@ __global__ __launch_bounds__(64) void bsk_to_fft_kernel(const uint64_t *__restri
     LaneTw tw;
     load_lane_tw(tw, lanetab, lane);
     fft_forward(z, reinterpret_cast<double *>(smem), lane, tw);
-    stage_lane<false, 1>(z, tw.re[5], tw.im[5]);
+    stage_lane<false, 1>(z, tw.stage(5));
     double *dst = out + (size_t)blockIdx.x * 2 * FM;
 #pragma unroll
     for (int c = 0; c < 16; c++) {

@@ -26,20 +26,23 @@ struct store_hook {
 // Hook of the LAST forward stage: as a butterfly finishes two points of the transform they are (1) published for the
 // partner wavefront ([c][lane] order), (2) multiplied by this wavefront's own key row (the first half of the pointwise
 // product: rr = fr*kx - fi*ky, ii = fr*ky + fi*kx, same operations in the same order as when the whole product ran
-// after the barrier), and (3) the key slot they used is refilled: own-row points 8..15 first, then the partner row's
-// points 0..7, which are only needed after the workgroup barrier -- their latency hides behind the rest of this stage
-// and the barrier wait.  One 8-point window (32 VGPRs) serves both rows because the two halves no longer overlap.
+// after the barrier), and (3) the key slot they used is refilled: after point p slot p & 3 takes own-row point p + 4
+// (p < 12), then the partner row's point p - 12, which is only needed after the workgroup barrier -- its latency hides
+// behind the rest of this stage and the barrier wait.  One 4-point window (16 VGPRs) serves both rows because the two
+// halves do not overlap; the stage finishes its points in the order 0, 1, .., 15, so a key element is requested four
+// finished points ahead of its use.  (The window was 8 points until the per-lane twiddles became loop-resident: the
+// 16 registers it gave back are what keeps the loop free of spills.)
 typedef double __attribute__((ext_vector_type(2))) double2_t;
 struct publish_mul_hook {
     cplx *pub; cplx *z; double2_t *kb; const double2_t *b_own, *b_par;
     __device__ __forceinline__ void one(int p) const {
         pub[64 * p] = z[p];
         const double fr = z[p].r, fi = z[p].i;
-        const double2_t k = kb[p & 7];
+        const double2_t k = kb[p & 3];
         double rr = fr * k.x; rr = __builtin_fma(-fi, k.y, rr);
         double ii = fr * k.y; ii = __builtin_fma(fi, k.x, ii);
         z[p].r = rr; z[p].i = ii;
-        kb[p & 7] = p < 8 ? b_own[(p + 8) * 64] : b_par[(p - 8) * 64];
+        kb[p & 3] = p < 12 ? b_own[(p + 4) * 64] : b_par[(p - 12) * 64];
     }
     __device__ __forceinline__ void operator()(int a, int b) const {
         one(a);
@@ -68,21 +71,32 @@ template <bool INV, class Hook> __device__ __forceinline__ void stages_uniform(c
     }
 }
 
+// The per-lane twiddles of one in-lane stage: the base and its products with the literal factors U[0..2].  stage_tw_base
+// multiplies where the product is used (a transform that runs once: bsk_to_fft_kernel, and fftmb_kernels.hip, which
+// reloads the bases per transform); stage_tw_ready hands out products made once (LaneTwFull below).  Either way a product
+// is the same cmul on the same operands.
+struct stage_tw_base {
+    double br, bi;
+    __device__ __forceinline__ cplx base() const { cplx b; b.r = br; b.i = bi; return b; }
+    __device__ __forceinline__ cplx times_u(int u) const { return cmul(base(), FU_RE[u], FU_IM[u]); }
+};
+struct stage_tw_ready {
+    cplx w[4];                                            // base, base * U[0], base * U[1], base * U[2]
+    __device__ __forceinline__ cplx base() const { return w[0]; }
+    __device__ __forceinline__ cplx times_u(int u) const { return w[1 + u]; }
+};
+
 // one in-lane stage of layout B or C: register distance TAU, G = 8/TAU twiddle groups,
 // twiddle of group g = per-lane base * U_G[g] (g even), rotated by i for odd g
-template <bool INV, int TAU, class Hook = no_hook>
-__device__ __forceinline__ void stage_lane(cplx (&z)[16], double br, double bi, const Hook &hook = Hook()) {
+template <bool INV, int TAU, class Tw, class Hook = no_hook>
+__device__ __forceinline__ void stage_lane(cplx (&z)[16], const Tw &tw, const Hook &hook = Hook()) {
     constexpr int G = 8 / TAU;
 #pragma unroll
     for (int g = 0; g < G; g += 2) {
-        double wr = br, wi = bi;
-        if (g) {
-            // U_G[g] = exp(i*pi*bitrev(g)/G): G=4: g=2 -> pi/4;  G=8: g=2 -> pi/4, g=4 -> pi/8, g=6 -> 3pi/8
-            const int u = (G == 8 && g == 4) ? 1 : (G == 8 && g == 6) ? 2 : 0;
-            cplx b; b.r = br; b.i = bi;
-            const cplx w = cmul(b, FU_RE[u], FU_IM[u]);
-            wr = w.r; wi = w.i;
-        }
+        // U_G[g] = exp(i*pi*bitrev(g)/G): G=4: g=2 -> pi/4;  G=8: g=2 -> pi/4, g=4 -> pi/8, g=6 -> 3pi/8
+        const int u = (G == 8 && g == 4) ? 1 : (G == 8 && g == 6) ? 2 : 0;
+        const cplx w = g ? tw.times_u(u) : tw.base();
+        const double wr = w.r, wi = w.i;
 #pragma unroll
         for (int c = 2 * g * TAU; c < 2 * g * TAU + TAU; c++) {
             if (INV) bf_inv<false>(z[c], z[c + TAU], wr, wi); else bf_fwd<false>(z[c], z[c + TAU], wr, wi);
@@ -105,7 +119,10 @@ __device__ __forceinline__ cplx *slotB(double *lds, int lane) { return reinterpr
 __device__ __forceinline__ cplx *slotC(double *lds, int lane) { return reinterpret_cast<cplx *>(lds) + 17 * lane; }
 
 // per-lane twiddle bases: rows (re, im) x {B: G=1,2,4,8; C: G=4,8}
-struct LaneTw { double re[6], im[6]; };
+struct LaneTw {
+    double re[6], im[6];
+    __device__ __forceinline__ stage_tw_base stage(int k) const { return stage_tw_base{re[k], im[k]}; }
+};
 __device__ __forceinline__ void load_lane_tw(LaneTw &t, const double *__restrict__ lanetab, int lane) {
     // global address space spelled out: after the opaque asm in the caller the pointer would otherwise be generic
     // and the loads flat (which also count on the LDS counter)
@@ -115,8 +132,28 @@ __device__ __forceinline__ void load_lane_tw(LaneTw &t, const double *__restrict
     for (int k = 0; k < 6; k++) { t.re[k] = g[(2 * k) * 64 + lane]; t.im[k] = g[(2 * k + 1) * 64 + lane]; }
 }
 
+// The same bases with the products every transform needs (one for each G = 4 stage, three for each G = 8 stage: 8 per
+// transform), made ONCE: they depend on the lane only, so a kernel that runs many transforms fills this in front of its
+// loop and uses it for the forward and the inverse transform alike (12 + 16 doubles that stay in registers).
+struct LaneTwFull {
+    cplx w[6][4];
+    __device__ __forceinline__ void fill(const LaneTw &t) {
+#pragma unroll
+        for (int k = 0; k < 6; k++) {
+            const stage_tw_base b = t.stage(k);
+            w[k][0] = b.base();
+#pragma unroll
+            for (int u = 0; u < 3; u++) w[k][1 + u] = b.times_u(u);   // the ones no stage asks for are dropped as dead code
+        }
+    }
+    __device__ __forceinline__ stage_tw_ready stage(int k) const {
+        return stage_tw_ready{{w[k][0], w[k][1], w[k][2], w[k][3]}};
+    }
+};
+
 // forward: z[r] = point (lane + 64 r)  ->  z[c] = value at array index 16*lane + c
-__device__ __forceinline__ void fft_forward(cplx (&z)[16], double *lds, int lane, const LaneTw &tw) {
+template <class Tw>
+__device__ __forceinline__ void fft_forward(cplx (&z)[16], double *lds, int lane, const Tw &tw) {
     stages_uniform<false>(z, store_hook{slotA(lds, lane), z, 68, 0});             // slot A of register r: 68 r
     __builtin_amdgcn_wave_barrier();
     {
@@ -128,10 +165,10 @@ __device__ __forceinline__ void fft_forward(cplx (&z)[16], double *lds, int lane
         }
     }
     __builtin_amdgcn_wave_barrier();
-    stage_lane<false, 8>(z, tw.re[0], tw.im[0]);
-    stage_lane<false, 4>(z, tw.re[1], tw.im[1]);
-    stage_lane<false, 2>(z, tw.re[2], tw.im[2]);
-    stage_lane<false, 1>(z, tw.re[3], tw.im[3], store_hook{slotB(lds, lane), z, 4, 1});   // slot B: 4 p + (p >> 2)
+    stage_lane<false, 8>(z, tw.stage(0));
+    stage_lane<false, 4>(z, tw.stage(1));
+    stage_lane<false, 2>(z, tw.stage(2));
+    stage_lane<false, 1>(z, tw.stage(3), store_hook{slotB(lds, lane), z, 4, 1});   // slot B: 4 p + (p >> 2)
     __builtin_amdgcn_wave_barrier();
     {
         const cplx *rd = slotC(lds, lane);
@@ -142,18 +179,19 @@ __device__ __forceinline__ void fft_forward(cplx (&z)[16], double *lds, int lane
         }
     }
     __builtin_amdgcn_wave_barrier();
-    stage_lane<false, 2>(z, tw.re[4], tw.im[4]);
+    stage_lane<false, 2>(z, tw.stage(4));
 }
 // last forward stage; every finished point goes through the hook (publication + own-row half of the pointwise product)
-template <class Hook>
-__device__ __forceinline__ void fft_forward_last(cplx (&z)[16], const LaneTw &tw, const Hook &hook) {
-    stage_lane<false, 1>(z, tw.re[5], tw.im[5], hook);
+template <class Tw, class Hook>
+__device__ __forceinline__ void fft_forward_last(cplx (&z)[16], const Tw &tw, const Hook &hook) {
+    stage_lane<false, 1>(z, tw.stage(5), hook);
 }
 
 // inverse (unscaled): z[c] at array index 16*lane + c  ->  z[r] = point (lane + 64 r)
-__device__ __forceinline__ void fft_inverse(cplx (&z)[16], double *lds, int lane, const LaneTw &tw) {
-    stage_lane<true, 1>(z, tw.re[5], tw.im[5]);
-    stage_lane<true, 2>(z, tw.re[4], tw.im[4], store_hook{slotC(lds, lane), z, 1, 0});            // slot C: c
+template <class Tw>
+__device__ __forceinline__ void fft_inverse(cplx (&z)[16], double *lds, int lane, const Tw &tw) {
+    stage_lane<true, 1>(z, tw.stage(5));
+    stage_lane<true, 2>(z, tw.stage(4), store_hook{slotC(lds, lane), z, 1, 0});            // slot C: c
     __builtin_amdgcn_wave_barrier();
     {
         const cplx *rd = slotB(lds, lane);
@@ -161,10 +199,10 @@ __device__ __forceinline__ void fft_inverse(cplx (&z)[16], double *lds, int lane
         for (int p = 0; p < 16; p++) z[p] = rd[4 * p + (p >> 2)];
     }
     __builtin_amdgcn_wave_barrier();
-    stage_lane<true, 1>(z, tw.re[3], tw.im[3]);
-    stage_lane<true, 2>(z, tw.re[2], tw.im[2]);
-    stage_lane<true, 4>(z, tw.re[1], tw.im[1]);
-    stage_lane<true, 8>(z, tw.re[0], tw.im[0], store_hook{slotB(lds, lane), z, 4, 1});
+    stage_lane<true, 1>(z, tw.stage(3));
+    stage_lane<true, 2>(z, tw.stage(2));
+    stage_lane<true, 4>(z, tw.stage(1));
+    stage_lane<true, 8>(z, tw.stage(0), store_hook{slotB(lds, lane), z, 4, 1});
     __builtin_amdgcn_wave_barrier();
     {
         const cplx *rd = slotA(lds, lane);

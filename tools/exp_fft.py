@@ -47,20 +47,22 @@ INV6 = {
          "    a.r = u.r + v.r; a.i = u.i + v.i; b.r = u.r - v.r; b.i = u.i - v.i;\n"
          "}\n"
          "// Torus value (mod 2^64)")],
-    T: [("    stage_lane<true, 1>(z, tw.re[5], tw.im[5]);\n"
-         "    stage_lane<true, 2>(z, tw.re[4], tw.im[4], store_hook{slotC(lds, lane), z, 1, 0});            // slot C: c\n",
+    T: [("    stage_lane<true, 1>(z, tw.stage(5));\n"
+         "    stage_lane<true, 2>(z, tw.stage(4), store_hook{slotC(lds, lane), z, 1, 0});            // slot C: c\n",
          "    _Pragma(\"unroll\") for (int c = 0; c < 16; c += 2) bf_triv(z[c], z[c + 1]);\n"
          "    { const store_hook hk{slotC(lds, lane), z, 1, 0};\n"
          "      _Pragma(\"unroll\") for (int c = 0; c < 16; c += 4) { bf_triv(z[c], z[c + 2]); hk(c, c + 2); bf_triv(z[c + 1], z[c + 3]); hk(c + 1, c + 3); } }\n")],
-    K: [("            fft_inverse(z, my, lane, tw2);\n        }\n",
+    K: [("        fft_inverse(z, my, lane, tw);\n",
+         "        {\n"
          "            const double2_t *utab = reinterpret_cast<const double2_t *>(P.bsk_fft) + lane;\n"
+         "            double2_t ub[8];\n"
          "#pragma unroll\n"
-         "            for (int k = 0; k < 8; k++) kb[k] = utab[k * 64];\n"
-         "            fft_inverse(z, my, lane, tw2);\n"
+         "            for (int k = 0; k < 8; k++) ub[k] = utab[k * 64];\n"
+         "            fft_inverse(z, my, lane, tw);\n"
          "#pragma unroll\n"
          "            for (int r = 0; r < 16; r++) {\n"
-         "                z[r] = cmul(z[r], kb[r & 7].x, kb[r & 7].y);\n"
-         "                if (r < 8) kb[r] = utab[(r + 8) * 64];\n"
+         "                z[r] = cmul(z[r], ub[r & 7].x, ub[r & 7].y);\n"
+         "                if (r < 8) ub[r] = utab[(r + 8) * 64];\n"
          "            }\n"
          "        }\n")],
 }
@@ -108,12 +110,12 @@ PERMLANE = {T: [
      "        }\n"
      "    }\n"
      "    __builtin_amdgcn_wave_barrier();\n"
-     "    stage_lane<false, 8>(z, tw.re[0], tw.im[0]);\n",
+     "    stage_lane<false, 8>(z, tw.stage(0));\n",
      "    stages_uniform<false>(z, no_hook());\n"
      "    swap_round<32, 8>(z);\n"
-     "    stage_lane<false, 8>(z, tw.re[0], tw.im[0]);\n"
+     "    stage_lane<false, 8>(z, tw.stage(0));\n"
      "    swap_round<16, 4>(z);\n"),
-    ("    stage_lane<true, 8>(z, tw.re[0], tw.im[0], store_hook{slotB(lds, lane), z, 4, 1});\n"
+    ("    stage_lane<true, 8>(z, tw.stage(0), store_hook{slotB(lds, lane), z, 4, 1});\n"
      "    __builtin_amdgcn_wave_barrier();\n"
      "    {\n"
      "        const cplx *rd = slotA(lds, lane);\n"
@@ -122,7 +124,7 @@ PERMLANE = {T: [
      "    }\n"
      "    __builtin_amdgcn_wave_barrier();\n",
      "    swap_round<16, 4>(z);\n"
-     "    stage_lane<true, 8>(z, tw.re[0], tw.im[0]);\n"
+     "    stage_lane<true, 8>(z, tw.stage(0));\n"
      "    swap_round<32, 8>(z);\n"),
 ]}
 # the same with only ONE of the two swap rounds per transform (32 instead of 64 swap instructions): what the second costs
@@ -144,7 +146,7 @@ def merge(*vs):
 
 
 # inv6 with the untwist factors as constants (no table loads): isolates the effect of the lower FP64 count
-INV6C = {D: INV6[D], T: INV6[T], K: [(INV6[K][0][0], INV6[K][0][1].replace("kb[k] = utab[k * 64];", "kb[k] = double2_t{1.0 + k, 0.5};").replace("if (r < 8) kb[r] = utab[(r + 8) * 64];", ""))]}
+INV6C = {D: INV6[D], T: INV6[T], K: [(INV6[K][0][0], INV6[K][0][1].replace("ub[k] = utab[k * 64];", "ub[k] = double2_t{1.0 + k, 0.5};").replace("if (r < 8) ub[r] = utab[(r + 8) * 64];", ""))]}
 
 P1, P2, P0 = "__builtin_amdgcn_s_setprio(1);", "__builtin_amdgcn_s_setprio(2);", "__builtin_amdgcn_s_setprio(0);"
 TUNE = {
