@@ -4,7 +4,8 @@ rotation under them (test infrastructure; numpy only, nothing from oracle/ or th
 GGSW i is bits[i] * G + Z_i with G = diag(2^41) (one level, base 2^23) and Z_i two noise-free GLWE encryptions of zero
 (A, A * S) under S = X^js, A = c * X^k, c = (odd integer < 1024) * 2^41.  An external product with such a key is a few
 negacyclic rotations and scalings in wrapping uint64, so the references below use no transform at all.  Every key word
-is a multiple of 2^41: the 2^6 / 2^7 grid roundings at key load are the identity, every product is far inside the exact
+is a multiple of 2^41: the 2^6 / 2^7 grid roundings at key load are the identity (offgrid_material() below adds an
+offset to every word, so that they are not), every product is far inside the exact
 kernels' CRT range, and the low 41 bits of every accumulator coefficient never change -- a look-up table whose low 41
 bits sit on the decomposition's edges keeps its exact ties through every iteration of a row.
 
@@ -13,7 +14,13 @@ the transform, so the only difference is the f64 rounding of that product), meas
 and 4, bit-identical to the kernels) over the committed row set:
     mode 3 (f64 FFT)          max |mirror - reference| = 2^23.70
     mode 4 (f64 FFT, two-bit) max |mirror - reference| = 2^24.58
-T3 and T4 are 8 x those; a single wrong digit moves a coefficient by at least 2^41, more than 2^10 above either."""
+T3 and T4 are 8 x those; a single wrong digit moves a coefficient by at least 2^41, more than 2^10 above either.
+The same on the rows whose last step is their one product with a GGSW of uniformly random 64-bit words (class U of
+offgrid_material(); measured by tests/test_key_load.py against the integer reference):
+    mode 3 (f64 FFT)          max |mirror - reference| = 2^40.56
+    mode 4 (f64 FFT, two-bit) max |mirror - reference| = 2^41.78
+T3U and T4U are 8 x those.  A key word of 2^63 times a digit of 2^22 has an f64 ulp of 2^33: the bound is one on the
+rounding of a last product, as T3X / T4X, not on a digit."""
 import functools
 
 import numpy as np
@@ -107,9 +114,12 @@ def dense_product(key_g, d):
     return [out[0], out[1]]
 
 
-def _product(desc, g, d, dense=None, log=None):
+def _product(desc, g, d, dense=None, log=None, used=None):
     """Sparse external product of the digits d [2][2048] with GGSW g -> [2][2048]; GGSWs in `dense` {g: [2][2][2048]}
-    are multiplied out in full, and (g, d) is appended to `log`."""
+    are multiplied out in full, and (g, d) is appended to `log`.  used: a set that receives (g, row) for every GGSW
+    row that meets a non-zero digit."""
+    if used is not None:
+        used.update((g, row) for row in range(2) if d[row].any())
     if dense is not None and g in dense:
         if log is not None:
             log.append((g, np.stack(d)))
@@ -126,7 +136,7 @@ def _start(ms, lut):
     return [np.zeros(N, U), rot(np.asarray(lut, U), (2 * N - int(ms[LWE_N])) & (2 * N - 1))]
 
 
-def blind_rotate_ref(desc, ms, lut, digit=digit, ties=None, dense=None, log=None):
+def blind_rotate_ref(desc, ms, lut, digit=digit, ties=None, dense=None, log=None, used=None):
     """Classic blind rotation, ACC += GGSW_i (.) (X^a ACC - ACC) per mask element a = ms[i] != 0 -> [2, 2048].
     ties: a list that receives, per product, the number of body differences whose low 41 bits equal 2^40."""
     acc = _start(ms, lut)
@@ -137,12 +147,12 @@ def blind_rotate_ref(desc, ms, lut, digit=digit, ties=None, dense=None, log=None
         diff = [rot(acc[r], a) - acc[r] for r in range(2)]
         if ties is not None:
             ties.append(int(np.count_nonzero((diff[1] & U((1 << 41) - 1)) == U(1 << 40))))
-        p = _product(desc, i, [digit(x) for x in diff], dense, log)
+        p = _product(desc, i, [digit(x) for x in diff], dense, log, used)
         acc = [acc[c] + p[c] for c in range(2)]
     return np.stack(acc)
 
 
-def blind_rotate_mb2_ref(desc, ms, lut, digit=digit, dense=None, log=None):
+def blind_rotate_mb2_ref(desc, ms, lut, digit=digit, dense=None, log=None, used=None):
     """Two key bits per step: ACC += sum_t (X^e_t - 1) (K_t (.) ACC), t over (e1, e2, e1 + e2) -> [2, 2048]."""
     acc = _start(ms, lut)
     for p in range(LWE_N // 2):
@@ -152,7 +162,7 @@ def blind_rotate_mb2_ref(desc, ms, lut, digit=digit, dense=None, log=None):
         d = [digit(x) for x in acc]
         new = list(acc)
         for t, e in enumerate((e1, e2, (e1 + e2) & (2 * N - 1))):
-            pt = _product(desc, 3 * p + t, d, dense, log)
+            pt = _product(desc, 3 * p + t, d, dense, log, used)
             new = [new[c] + rot(pt[c], e) - pt[c] for c in range(2)]
         acc = new
     return np.stack(acc)
@@ -689,3 +699,194 @@ def true_magnitude(products):
     import math
     worst = max((abs(int(v)) for x_true, _ in products for v in x_true.ravel()), default=0)
     return math.log2(worst) if worst else float("-inf")
+
+
+# ---- keys that do not lie on the key grid ----------------------------------------------------------------------------
+#
+# Key load rounds every word of the bootstrapping key to the nearest multiple of 2^6 (ties up, modulo 2^64), and every
+# word of the pair key to 2^6 for the f64 arithmetic and -- from the ORIGINAL word -- to 2^7 for the exact one.  The keys
+# below are material()'s plus an offset per word, in three classes of GGSW (a pair triple is three):
+#   R "returns": every GGSW that is not M or U.  Offsets from R_OFFSETS; every word rounds back to material()'s word on
+#     both grids, so the rows that meet only such GGSWs keep the outputs of references().  -1 and -32 on a zero word are
+#     the words 2^64 - 1 and 2^64 - 32, which wrap to 0.
+#   M "moves": the GGSWs of three one-product rows and of two two-product rows, and the pair triples at the same
+#     positions (g // 2).  Offsets from M_OFFSETS: every word moves by +-2^6 or +-2^7 or stays, differently on the two
+#     grids, and "6 then 7" differs from 7 on +32, +33, +63 (and on 2^63 - 33).  The rounded polynomial is dense, the
+#     reference multiplies it out (dense= of _product).  Planted words: 2^64 - 32 and 2^64 - 1 (-> 0) in every
+#     polynomial, 2^63 - 32 and 2^63 - 33 (-> 2^63, centred -2^63; the latter -> 2^63 - 2^6 on the 2^6 grid) in the
+#     polynomials of GGSW row 0 only.  Row 0 meets the digits of the accumulator's mask, which are zero in the first
+#     product of a row: the rows with one product never multiply a word of magnitude 2^63, whose f64 product has an ulp
+#     of 2^33 and would leave T3 / T4 for the reason given at T3X; the second product of a two-product row and the
+#     sparse and full rows do multiply them, where the exact kernels answer in every word and the f64 kernels to their
+#     mirrors.
+#   U "uniform": three GGSWs and two pair triples of uniformly random 64-bit words, as a foreign key has them.  No row of
+#     material() but the full ones meets their mask elements, those are zeroed in the full rows here, and thirteen rows
+#     of their own hold one or two products with them, four of them after a first step with a GGSW of class R, and
+#     nothing else.  Where such a product is the row's only one with class U and its last step, the f64 arithmetics are
+#     bounded against the integer reference by T3U / T4U (the module's docstring has the measured figures).
+R_OFFSETS = (-32, -31, -1, 1, 31)
+M_OFFSETS = (32, 33, 63, -33, -63, -64, 64, 95, 96)
+M_PLANTS_WRAP = ((1 << 64) - 32, (1 << 64) - 1)
+M_PLANTS_TOP = ((1 << 63) - 32, (1 << 63) - 33)
+O_SEED = 0x0FF6E1D
+T3U = 8 * 2 ** 40.56
+T4U = 8 * 2 ** 41.78
+
+
+def round_grid(x, bits):
+    """The nearest multiple of 2^bits, ties up, modulo 2^64: what key load does to a key word."""
+    return (np.asarray(x, U) + U(1 << (bits - 1))) & ~U((1 << bits) - 1)
+
+
+def round_truncated(x, bits):
+    return np.asarray(x, U) & ~U((1 << bits) - 1)
+
+
+def round_ties_down(x, bits):
+    return (np.asarray(x, U) + U((1 << (bits - 1)) - 1)) & ~U((1 << bits) - 1)
+
+
+def round_6_then_7(x, bits):
+    """The pair key's exact form taken from the words already rounded for the f64 form (on the 2^6 grid: no change)."""
+    return round_grid(round_grid(x, 6), bits)
+
+
+def round_wrong_grid(x, bits):
+    """2^7 where 2^6 belongs, and the reverse."""
+    return round_grid(x, 13 - bits)
+
+
+# the mutants of the negative control (tests/test_key_load.py), as drop-in replacements of round_grid
+ROUND_MUTANTS = {"truncation": round_truncated, "ties down": round_ties_down, "6 then 7": round_6_then_7,
+                 "wrong grid": round_wrong_grid}
+
+
+class OffgridMaterial:
+    """bsk, bsk_mb2: the keys as they are loaded; desc, desc_mb2, luts: material()'s; m_dense, u_dense: the classic GGSWs
+    of class M and U, m_pairs, u_pairs: the pairs whose triples are; blocked: the mask elements of the U GGSWs; ks, ms,
+    lut_idx, kinds: material()'s rows (the full ones zero at `blocked`) and the "u" rows.  Row lists per arithmetic
+    (classic / _mb2): r_rows meet GGSWs of class R only, m_rows one of class M at least; one_m: the rows with ONE product, which is
+    with a GGSW of class M; one_u: the rows whose last step is their one product with a GGSW of class U."""
+
+
+def _triples(pairs):
+    return [3 * p + t for p in pairs for t in range(3)]
+
+
+@functools.lru_cache(maxsize=None)
+def offgrid_material():
+    base = material()
+    rng = np.random.default_rng(O_SEED)
+    x = OffgridMaterial()
+    x.desc, x.desc_mb2, x.luts = base.desc, base.desc_mb2, base.luts
+    n_base = len(base.ks)
+    first = lambda r: int(np.flatnonzero(base.ms[r, :LWE_N])[0])
+    singles = [first(r) for r in rows_of(base, "single")][:3]
+    doubles = [first(r) & ~1 for r in rows_of(base, "pair") if np.count_nonzero(base.ms[r, :LWE_N]) == 2][:2]
+    x.m_dense = tuple(singles + [g + k for g in doubles for k in range(2)])
+    x.m_pairs = tuple(sorted({g // 2 for g in x.m_dense}))
+    light = rows_of(base, "single", "pair", "sparse", "zero")
+    busy = (base.ms[light, :LWE_N] != 0).any(axis=0)
+    free = [p for p in range(LWE_N // 2) if not (busy[2 * p] or busy[2 * p + 1]) and p not in x.m_pairs]
+    x.u_pairs = tuple(free[:2])
+    x.u_dense = (2 * free[0], 2 * free[0] + 1, 2 * free[1])
+    x.blocked = tuple(2 * p + k for p in x.u_pairs for k in range(2))
+
+    def shifted(key, m_idx, u_idx):
+        raw = key + rng.choice(np.array(R_OFFSETS, np.int64), key.shape).view(U)
+        for g in m_idx:
+            raw[g] = key[g] + rng.choice(np.array(M_OFFSETS, np.int64), key[g].shape).view(U)
+            for row in range(2):
+                plants = (M_PLANTS_TOP + M_PLANTS_WRAP if row == 0 else M_PLANTS_WRAP + M_PLANTS_WRAP) * 2
+                for col in range(2):
+                    at = rng.choice(np.flatnonzero(key[g, row, col] == 0), len(plants), replace=False)
+                    raw[g, row, col, at] = np.array(plants, U)
+        for g in u_idx:
+            raw[g] = rng.integers(0, 1 << 64, key[g].shape, dtype=U)
+        return raw
+    x.bsk = shifted(base.bsk, x.m_dense, x.u_dense)
+    x.bsk_mb2 = shifted(base.bsk_mb2, _triples(x.m_pairs), _triples(x.u_pairs))
+
+    ks = base.ks.copy()
+    ks[:, list(x.blocked)] = 0                                   # changes the full rows only
+    (a0, a1, b0, b1), E = x.blocked, EXPONENTS
+    masks = [{g: E[(5 * k + 1) % 16]} for k, g in enumerate(x.u_dense * 2)] + [
+        {b1: 2048}, {a0: 65, a1: 2111}, {b0: 4095, b1: 1}]
+    # a first step with a GGSW of class R, so that GGSW row 0 of the U GGSW meets digits too.  These rows take the
+    # constant and the `msg` look-up table: under an edge table the f64 rounding of the first step would decide exact
+    # ties of the second, and the distance to the integer reference would be no rounding error (see T3X)
+    x.u_first = next(g for g in range(LWE_N) if g // 2 not in x.m_pairs + x.u_pairs)
+    two_step = [{x.u_first: E[(3 * k + 4) % 16], g: E[(7 * k + 2) % 16]} for k, g in enumerate(x.blocked)]
+    rows, lut_idx = [], []
+    for k, mask in enumerate(masks + two_step):
+        row = [0] * (LWE_N + 1)
+        for i, e in mask.items():
+            row[i] = _torus(e, k % 3)
+        row[LWE_N] = _torus(E[(3 * k + 2) % 16], (k + 1) % 3)
+        rows.append(np.array(row, dtype=U)); lut_idx.append(k & 1 if k < len(masks) else 2 + (k & 1))
+    x.ks = np.concatenate([ks, np.stack(rows)])
+    x.ms = mod_switch(x.ks)
+    x.lut_idx = np.concatenate([base.lut_idx, np.array(lut_idx, np.uint32)])
+    x.kinds = list(base.kinds) + ["u"] * len(rows)
+
+    on = x.ms[:, :LWE_N] != 0
+    on_pair = on[:, 0::2] | on[:, 1::2]
+    def split(on, m_idx, u_idx, one_kinds):
+        hits_m = on[:, list(m_idx)].any(axis=1)
+        r_rows = [r for r in range(n_base) if base.kinds[r] != "full" and not hits_m[r]]
+        m_rows = [r for r in range(n_base) if hits_m[r]]
+        one_m = [r for r in m_rows if base.kinds[r] in one_kinds]
+        # the rows whose last step is their one product with a GGSW of class U
+        one_u = [r for r in range(n_base, len(x.ks)) if on[r, list(u_idx)].sum() == 1 and int(np.flatnonzero(on[r])[-1]) in u_idx]
+        return r_rows, m_rows, one_m, one_u
+    x.r_rows, x.m_rows, x.one_m, x.one_u = split(on, x.m_dense, x.u_dense, ("single",))
+    x.r_rows_mb2, x.m_rows_mb2, x.one_m_mb2, x.one_u_mb2 = split(on_pair, x.m_pairs, x.u_pairs, ("single", "pair"))
+    for a in (x.bsk, x.bsk_mb2, x.ks, x.ms, x.lut_idx):
+        a.setflags(write=False)
+    return x
+
+
+def offgrid_dense(x, pair_key, bits, rounding=round_grid, ggsws=None):
+    """{g: the GGSW as key load leaves it on the 2^bits grid} for the GGSWs of class M and U of the classic key or the
+    pair key, or for the given ones."""
+    key = x.bsk_mb2 if pair_key else x.bsk
+    if ggsws is None:
+        ggsws = _triples(x.m_pairs + x.u_pairs) if pair_key else x.m_dense + x.u_dense
+    return {g: rounding(key[g], bits) for g in ggsws}
+
+
+def offgrid_row(x, r, pair_key, bits, rounding=round_grid, every=False, used=None):
+    """The accumulator [2, 2048] of row r under the off-grid key rounded to 2^bits by `rounding`.  every: all GGSWs that
+    the row meets are rounded from the loaded words and multiplied out (what a mutant needs, under which the words of
+    class R do not return), not those of class M and U alone."""
+    ggsws = None
+    if every:
+        on = np.flatnonzero(x.ms[r, :LWE_N])
+        ggsws = _triples(sorted({int(i) // 2 for i in on})) if pair_key else [int(i) for i in on]
+    dense = offgrid_dense(x, pair_key, bits, rounding, ggsws)
+    if pair_key:
+        return blind_rotate_mb2_ref(x.desc_mb2, x.ms[r], x.luts[x.lut_idx[r]], dense=dense, used=used)
+    return blind_rotate_ref(x.desc, x.ms[r], x.luts[x.lut_idx[r]], dense=dense, used=used)
+
+
+class OffgridReferences:
+    """acc (the classic key on the 2^6 grid), acc_mb2_6, acc_mb2_7 (the pair key on either grid) [R][2][2048]; out,
+    out_mb2_6, out_mb2_7 [R][2049]; used, used_mb2: the (GGSW, GGSW row) that met a non-zero digit on some row."""
+
+
+@functools.lru_cache(maxsize=None)
+def offgrid_references():
+    x = offgrid_material()
+    ref = OffgridReferences()
+    ref.used, ref.used_mb2 = set(), set()
+    dense, dense6, dense7 = offgrid_dense(x, False, 6), offgrid_dense(x, True, 6), offgrid_dense(x, True, 7)
+    rows = range(len(x.ks))
+    run = lambda r, dense, used: blind_rotate_mb2_ref(x.desc_mb2, x.ms[r], x.luts[x.lut_idx[r]], dense=dense, used=used)
+    ref.acc = np.stack([blind_rotate_ref(x.desc, x.ms[r], x.luts[x.lut_idx[r]], dense=dense, used=ref.used) for r in rows])
+    ref.acc_mb2_7 = np.stack([run(r, dense7, ref.used_mb2) for r in rows])
+    ref.acc_mb2_6 = np.stack([ref.acc_mb2_7[r] if r in x.r_rows_mb2 else run(r, dense6, None) for r in rows])
+    ref.out, ref.out_mb2_6, ref.out_mb2_7 = (np.stack([sample_extract(a) for a in acc])
+                                             for acc in (ref.acc, ref.acc_mb2_6, ref.acc_mb2_7))
+    for a in (ref.acc, ref.acc_mb2_6, ref.acc_mb2_7, ref.out, ref.out_mb2_6, ref.out_mb2_7):
+        a.setflags(write=False)
+    return ref
