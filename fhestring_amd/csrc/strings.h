@@ -1,6 +1,7 @@
 // String layer: host-side mirror of the reference's MyServerKey methods
 // (src/server_key/mod.rs, src/server_key/trim.rs, src/utils.rs:28-112) as DAG constructors.
 #pragma once
+#include <utility>
 #include <vector>
 
 #include "radix.h"
@@ -144,15 +145,30 @@ class Strings {
     typedef std::vector<Ref> Num;   // little-endian base-4 digits, clean (<= 3)
 
     // ---- single-block 0/1 flags (fused mode) ----
-    Ref and_tree(std::vector<Ref> flags);
-    Ref or_tree(std::vector<Ref> flags);
+    Ref flag_not(const Ref &x);                                       // 1 - x, a linear form
+    bool drop_trivial(std::vector<Ref> &flags, int absorbing) const;  // false: a trivial flag decides, the result is `absorbing`
+    Ref flag_tree(std::vector<Ref> flags, int absorbing);             // log_15-depth AND (absorbing = 0) or OR (1)
+    Ref and_tree(std::vector<Ref> flags) { return flag_tree(std::move(flags), 0); }
+    Ref or_tree(std::vector<Ref> flags) { return flag_tree(std::move(flags), 1); }
     Ref onehot_or(std::vector<Ref> flags);   // OR of flags of which at most one is set: noise-budget-wide groups
     std::vector<Ref> prefix_or(const std::vector<Ref> &f);            // exclusive: OR_{k<i}
     std::vector<Ref> suffix_or(const std::vector<Ref> &f);            // exclusive: OR_{k>i}
+    Ref lin_in_budget(Ref *const blk[4], const int64_t coef[4]);      // sum coef * blk, the sums among blk refreshed if it must
     std::vector<Ref> block_eq_flags(const FChar &a, const FChar &b);
+    std::vector<Ref> byte_eq_flags(const FChar &c, uint8_t byte, bool both_cases);   // the nibble flags of c == byte (either case)
     Ref window_match(const FStr &s, size_t at, const FStr &pat);
-    Ref char_nonzero(const FChar &c);                                 // 1 block: c != 0
     Ref char_zero_test(const FChar &c, bool want_zero);               // 1 block, 1 bootstrap: c == 0 / c != 0
+    struct NzMemo {                                                   // nz(i) = [s[i] != 0], made on first use and shared
+        Strings *str;
+        const FStr &s;
+        std::vector<Ref> made;
+        NzMemo(Strings *str_, const FStr &s_) : str(str_), s(s_), made(s_.size()) {}
+        Ref operator()(size_t i) {
+            if (!made[i]) made[i] = str->char_zero_test(s[i], false);
+            return made[i];
+        }
+        Ref zero(size_t i) { return str->flag_not((*this)(i)); }      // [s[i] == 0] = 1 - nz(i)
+    };
     Ref char_significant(const FChar &c);                             // 1 block: c is neither NUL nor whitespace
     Ref is_upper_flag(const FChar &c, bool lower);
     FChar ite_flag(const Ref &flag, const FChar &t, const FChar &f);
@@ -186,16 +202,22 @@ class Strings {
     // ---- fused forms of the tests, comparisons and maps ----
     FChar f_contains(const FStr &s, const FStr &needle);
     FChar f_ends_with(const FStr &s, const FStr &needle, std::vector<Ref> *pick_out);
+    // as written: 0/1 flag chars with trivial constants folded away (LIKE, regex)
+    int flag_const(const FChar &f) const;
+    FChar flag_and(const FChar &a, const FChar &b);
+    FChar flag_or(const FChar &a, const FChar &b);
+    FChar any_of(const std::vector<FChar> &flags, uint64_t set);
+    FChar class_test_as_written(const FChar &c, const RegexClass &cls);
     FChar like_as_written(const FStr &s, const std::vector<LikeTok> &pat, bool ignore_case);
     FChar f_like(const FStr &s, const std::vector<LikeTok> &pat, bool ignore_case);
-    FChar regex_as_written(const FStr &s, const RegexProgram &g, const RegexPlan &plan);
+    FChar regex_as_written(const FStr &s, const RegexProgram &g);
     FChar f_regex(const FStr &s, const RegexProgram &g, const RegexPlan &plan);
     Ref regex_step(std::vector<Ref> in, std::vector<Ref> preds);      // AND of the flags `in` AND (OR of `preds`)
     // fused class tests of f_regex / f_regex_starts: [class][index] -> one flag, or the two nibble flags of a BYTE class,
-    // where live[index] holds a position of that class; nz[index] = [s[index] != 0] is made on demand and shared
+    // where live[index] holds a position of that class
     std::vector<std::vector<std::vector<Ref>>> regex_class_tests(const FStr &s, const RegexProgram &g, const RegexPlan &plan,
-                                                                 const std::vector<uint64_t> &live, std::vector<Ref> &nz);
-    FStr regex_starts_as_written(const FStr &s, const RegexProgram &rev, const RegexPlan &plan);
+                                                                 const std::vector<uint64_t> &live, NzMemo &nz);
+    FStr regex_starts_as_written(const FStr &s, const RegexProgram &rev);
     std::vector<Ref> f_regex_starts(const FStr &s, const RegexProgram &rev, const RegexPlan &plan);
     FChar f_eq(const FStr &a, const FStr &b);
     FChar f_eq_ignore_case(const FStr &a, const FStr &b);

@@ -1,6 +1,6 @@
 """Multi-GPU string operations: thin Python glue over the library's own distributed layer (include/fhestring_hip.h
 "multi-GPU inside the library": fhs_dist_*).  One process per GPU; the RCCL communicator, the all-gathers (enqueued on
-the context's HIP stream) and the partial / combine DAGs all live in C++ (csrc/dist.cpp, capi_dist.cpp, strings.cpp);
+the context's HIP stream) and the partial / combine DAGs all live in C++ (csrc/dist.cpp, capi_dist.cpp, strings_compare.cpp, strings_positions.cpp);
 this module only hands the 128-byte communicator id around (torch.distributed, any backend) and mirrors the entry points.
 
 * window sharding: contains / find (src/server_key/mod.rs:170-177, :1010-1053) -- a rank holds its slice plus an

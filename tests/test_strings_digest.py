@@ -3,7 +3,9 @@ tools/gen_strings_digests.py): on planner contexts (no GPU) every scenario's pla
 statistics, the level widths and the launch groups hash to the committed digest.  Covers find / rfind / len / flag counts
 in their u8 and wide forms at every shape that takes another branch, the digit boundaries of the fused forms, the limits
 and the order of limit test and operand loading, char_at / substr / take / split_at with both kinds of position, constant
-folding on trivial characters, and every other string entry point of the C ABI once, each in as-written and fused mode.
+folding on trivial characters, every other string entry point of the C ABI once, and the pattern languages -- like_clear,
+map_clear / class_flags / find_class, regex_clear, regex_find_clear / regex_starts_clear, with the user tables they apply
+renamed by first appearance and hashed by content -- each in as-written and fused mode.
 A digest that moves means that an entry point builds another DAG."""
 import json
 import os

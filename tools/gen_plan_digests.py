@@ -8,7 +8,11 @@ WOULD run.  A digest is SHA-256 over, in this order:
   1. the plan trace (fhs_debug_plan_trace / fhs_debug_plan_read), every block token replaced by the index of its first
      appearance -- the fixture pins the plan, not the planner's fake-pointer numbering;
   2. fhs_debug_char_terms of the result handles, under the same renaming;
-  3. fhs_get_stats;  4. fhs_level_widths;  5. fhs_launch_groups.
+  3. fhs_get_stats;  4. fhs_level_widths;  5. fhs_launch_groups;
+  6. only where the trace names a user table (luts.h: ids from fhs_lut_catalogue_count() up are handed out process-wide in
+     order of first registration): every such id in a row is replaced by the catalogue count plus the rank of its first
+     appearance in the scenario, and the SHA-256 of each table's polynomial (fhs_debug_lut_poly), in that order, is hashed
+     last -- the fixture pins which table a row applies, not what the process registered before.
 
 The fhs_flush_plan / fhs_flush_level_exec / fhs_flush_level_commit walk writes no trace: its digest covers the per-level
 (width, cap), the statistics after every exec, the level widths and the launch groups.
@@ -66,6 +70,31 @@ def _trace_token_mask(t):
         else:
             raise ValueError("bad plan trace word %d at %d" % (tag, i))
     return mask
+
+
+def _rename_user_tables(sk, t):
+    """the `lut` word of every TR_ROW that names a user table -> catalogue count + rank of first appearance, in place;
+    returns the content hashes of those tables in that order ([] when the trace names none)"""
+    L = sk.ctx._L
+    n_cat = L.fhs_lut_catalogue_count()
+    words = t.tolist()
+    rank, hashes = {}, []
+    i = 0
+    while i < len(words):
+        tag = words[i]
+        if tag == TR_ROW:
+            lut = words[i + 2]
+            if lut >= n_cat:
+                if lut not in rank:
+                    poly = np.zeros(2048, np.uint64)
+                    assert L.fhs_debug_lut_poly(lut, poly.ctypes.data_as(C.c_void_p)) == 0
+                    rank[lut] = len(rank)
+                    hashes.append(hashlib.sha256(poly.tobytes()).hexdigest())
+                t[i + 2] = n_cat + rank[lut]
+            i += 5 + 2 * words[i + 4]
+        else:
+            i += {TR_UPLOAD: 2, TR_EXT: 4, TR_GROUP_END: 2}[tag]
+    return hashes
 
 
 def _terms_token_mask(t):
@@ -140,11 +169,13 @@ def record(body, mode=1, setup=None):
         except OverflowError:
             error = [{"error": FHS_ERR_LIMIT}]
         trace = _read_words(sk, L.fhs_debug_plan_read)            # flushes
+        tables = _rename_user_tables(sk, trace)
         parts = [(trace, _trace_token_mask(trace))]
         for ch in _chars_of(result):
             t = _read_words(sk, L.fhs_debug_char_terms, C.c_uint64(ch.h))
             parts.append((t, _terms_token_mask(t)))
-        return _hash(_rename(parts).tobytes(), sk.stats(), sk.level_widths(), sk.launch_groups(), *error)
+        return _hash(_rename(parts).tobytes(), sk.stats(), sk.level_widths(), sk.launch_groups(), *error,
+                     *([{"user_tables": tables}] if tables else []))
     finally:
         sk.close()
 

@@ -7,6 +7,11 @@ still go wrong, in as-written and fused mode (suffix _aw / _f).  A digest is gen
 result terms, statistics, level widths and launch groups of one scenario on a planner context (no GPU); a scenario that
 ends in an error digests the error code with what was recorded up to it.
 
+Sections 7 to 10 pin the pattern languages -- like_clear, map_clear / class_flags / find_class, regex_clear and
+regex_find_clear / regex_starts_clear.  Fused, these apply user tables, whose ids are process-wide; record() renames them
+by first appearance within the scenario and hashes their contents, so a digest is the same whatever the process
+registered before: alone, in this file's order, or in pytest's sorted order.
+
 The fixture was recorded from the library as it was BEFORE the string layer was refactored and is not regenerated for
 a change that only moves code: a digest that moves means that an entry point records other rows, or the same rows in
 another order.
@@ -163,6 +168,79 @@ add("replace_5_1_2", lambda sk: sk.replace(sk.dummy_string(5), sk.dummy_string(1
 add("replacen_5_2_1", lambda sk: sk.replacen(sk.dummy_string(5), sk.dummy_string(2), sk.dummy_string(1), sk.dummy_string(1)[0]))
 add("repeat_5", lambda sk: sk.repeat(sk.dummy_string(5), sk.dummy_string(1)[0]))
 add("repeat_clear_5_2", lambda sk: sk.repeat_clear(sk.dummy_string(5), 2))
+
+
+# ---- 7. LIKE against clear patterns ----
+def _like(n, pattern, **kw):
+    return lambda sk: sk.like_clear(sk.dummy_string(n), pattern, **kw)
+
+
+LIKE = (("empty", "", {}), ("any", "%", {}), ("lit", "a", {}), ("one", "_", {}), ("anchored", "a_%", {}),
+        ("contains", "%ab%", {}), ("middle", "a%b%c", {}),                 # a middle segment: the inclusive prefix OR
+        ("any_any", "%%a", {}), ("ilike", "%aB%", {"ignore_case": True}),
+        ("escape", "a!%%!_b", {"escape": "!"}),                            # the literals % and _ around an ANY
+        ("refused", "ab!", {"escape": "!"}))                               # a dangling escape: FHS_ERR_ARG
+for _tag, _pattern, _kw in LIKE:
+    for _n in (0, 1, 5, 17):
+        add("like_%s_%d" % (_tag, _n), _like(_n, _pattern, **_kw))
+for _n in (9, 17):                     # 16 nibble flags and extras: the chunked AND of the window
+    add("like_window16_%d" % _n, _like(_n, "%abcdefgh"))
+add("like_half_trivial_17", lambda sk: sk.like_clear(_text(sk, 17, 2), "%ab%c"))
+
+
+# ---- 8. clear tables and classes ----
+def _tables():
+    import gen_map_plan
+    return gen_map_plan.TABLES, gen_map_plan.CLASSES
+
+
+def _map(n, name):
+    return lambda sk: sk.map_clear(sk.dummy_string(n), _tables()[0][name])
+
+
+def _class(op, n, name):
+    return lambda sk: getattr(sk, op)(sk.dummy_string(n), b"a" if name == "one_byte" else _tables()[1][name])
+
+
+for _n in (1, 5):
+    # identity: PASS; constant: CONST; to_upper: one table on a digit; the others factor into PICK and LINES plans
+    for _name in ("identity", "constant", "to_upper", "mask_digits", "rot13", "bit_reversal", "random"):
+        add("map_clear_%s_%d" % (_name, _n), _map(_n, _name))
+    for _name in ("one_byte", "digits", "hex", "identifier", "whitespace"):   # one byte, a range, sets that need LINES
+        for _op in ("class_flags", "find_class"):
+            add("%s_%s_%d" % (_op, _name, _n), _class(_op, _n, _name))
+for _op in ("find_class", "find_class_wide"):
+    add("%s_identifier_17" % _op, _class(_op, 17, "identifier"))
+add("limit_find_class_257", _class("find_class", 257, "digits"))
+
+
+# ---- 9. regular expressions against clear patterns ----
+def _regex(op, n, pattern, **kw):
+    return lambda sk: getattr(sk, op)(sk.dummy_string(n), pattern, **kw)
+
+
+REGEX = (("abc", b"abc", {}),                                              # BYTE classes; a literal costs L steps
+         ("a_icase", b"a", {"ignore_case": True}), ("dot", b".", {}), ("table", b"[a-c]x", {}),
+         ("dead", rb"a\0", {}), ("nullable", b"a*", {}),
+         ("preds", b"(ab|c)+d", {}),                                       # k >= 2 predecessors: a threshold table
+         ("search", b"ab", {"search": True}), ("search_preds", b"(ab|c)+d", {"search": True}))
+for _tag, _pattern, _kw in REGEX:
+    for _n in (0, 1, 5, 17):
+        add("regex_%s_%d" % (_tag, _n), _regex("regex_clear", _n, _pattern, **_kw))
+add("regex_five_preds_5", _regex("regex_clear", 5, b"(a|b|c|d|e)+f"))      # 6 * 2 + 5 > 15: or_tree first in regex_step
+add("regex_half_trivial_17", lambda sk: sk.regex_clear(_text(sk, 17, 2), b"a+"))
+add("regex_refused", _regex("regex_clear", 5, b"a$"))
+
+# ---- 10. where a regular expression matches ----
+FIND_OPS = (("regex_find", "regex_find_clear"), ("regex_find_wide", "regex_find_clear_wide"), ("regex_starts", "regex_starts_clear"))
+for _tag, _pattern in (("abc", b"abc"), ("nullable", b"a*"), ("table", b"[a-c]+x"), ("preds", b"(ab|c)+d")):
+    for _n in (0, 1, 5, 17):
+        for _name, _op in FIND_OPS:
+            add("%s_%s_%d" % (_name, _tag, _n), _regex(_op, _n, _pattern))
+for _name, _op in FIND_OPS:
+    for _tag, _pattern in (("byte", b"a+x"), ("table", b"[a-c]+x")):
+        add("%s_half_trivial_%s_17" % (_name, _tag), lambda sk, op=_op, p=_pattern: getattr(sk, op)(_text(sk, 17, 2), p))
+add("limit_regex_find_257", _regex("regex_find_clear", 257, b"abc"))
 
 
 def main():

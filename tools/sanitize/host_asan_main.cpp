@@ -1,6 +1,6 @@
 // ASan/UBSan driver of the product's HOST-ONLY code (no device is touched): client keygen / encrypt / decrypt /
 // key files (client.cpp), public-key encryption and its expansion (pk_host.cpp), the exact host NTT (host_ntt.cpp), the twiddle and key transforms (ntt_tables.cpp, fft_tables.cpp), and the whole DAG layer --
-// engine.cpp graph logic, radix.cpp, strings.cpp, capi_*.cpp -- through a planner context (fhs_ctx_create_planner),
+// engine.cpp graph logic, radix.cpp, strings*.cpp, capi_*.cpp -- through a planner context (fhs_ctx_create_planner),
 // which records and levelises every string op of the C ABI without executing anything.
 // Built by `make -C fhestring_amd/csrc asan`; run by tests/test_sanitizers.py.  CPU only.
 #include <algorithm>

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
 """Host planning time of the engine on planner contexts (CPU only): the time from the first recorded op to the end of
-flush() for replace 1025 / 5 / 5 (131 405 bootstraps), le on 4097 + 4097 characters, find_wide on 4097 / 4 and split_at
-with a u8 position on 512 characters, one JSON line per process.
+flush() for replace 1025 / 5 / 5 (131 405 bootstraps), le on 4097 + 4097 characters, find_wide on 4097 / 4, split_at
+with a u8 position on 512 characters, and like_clear, regex_clear and regex_find_clear on 256 characters, one JSON line
+per process.
 
-A/B of two builds of the library (profiles/r10_engine_refactor_ab.json, profiles/r17_strings_refactor_ab.json): run this
+A/B of two builds of the library (profiles/r10_engine_refactor_ab.json, profiles/r17_strings_refactor_ab.json,
+profiles/r25_strings_flag_algebra_ab.json): run this
 in alternating fresh processes with FHS_LIB_PATH pointing at one build or the other.
 """
 import json
@@ -21,6 +23,9 @@ def main():
         "le_4097": lambda sk: (sk.le, (sk.dummy_string(4097), sk.dummy_string(4097))),
         "find_wide_4097_4": lambda sk: (sk.find_wide, (sk.dummy_string(4097), sk.dummy_string(4))),
         "split_at_u8_512": lambda sk: (sk.split_at, (sk.dummy_string(512), sk.dummy_string(1)[0])),
+        "like_clear_256": lambda sk: (sk.like_clear, (sk.dummy_string(256), "%quick%br_wn%fox")),
+        "regex_clear_256": lambda sk: (sk.regex_clear, (sk.dummy_string(256), b"[A-Z]{2}-[0-9]+ (error|warn).*timeout")),
+        "regex_find_clear_256": lambda sk: (sk.regex_find_clear, (sk.dummy_string(256), b"(error|warn): [a-z]+")),
     }
     out = {}
     for name, make in scenarios.items():
